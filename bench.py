@@ -3,7 +3,7 @@
 bench.py -- forward+backward Mpixels/s of the rasterizer on BASELINE.json's headline workload:
 synthetic 800x800, 1M Gaussians, SH degree 3 (config "C3").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 N > 1 runs one process per GPU.  Under `python -m torch.distributed.run --nproc-per-node N` (the driver's form) this process
 is one of the ranks (RANK / LOCAL_RANK / WORLD_SIZE from the environment).  Started bare (`python bench.py --gpus N`, no
@@ -25,6 +25,10 @@ The JSON line also carries
                   forward+backward byte budget B = 340 N + 596 Nv + 128 D + 16 Tn + 44 P;
   cpu_baseline -- the CPU oracle (a single-thread C restatement of the reference kernels; Warp's CPU
                   backend is also one serial loop) on the same scene and view, rank 0, N=1 only.
+
+--dump-outputs DIR writes what the LAST timed step returned to its caller on rank 0 (the forward's image, depth_image and
+buffers, the backward's gradients) as DIR/<name>.npy, so that two builds can be compared output for output on the same seeded
+inputs; see dump_plan() for the sampling that keeps it under 64 MB.
 """
 import argparse
 import importlib
@@ -114,6 +118,55 @@ def stage_bytes(N, Nv, D, P, Tn, depth_passes=4):
     }
 
 
+DUMP_BYTES = 64_000_000     # --dump-outputs: at most this much in all
+
+
+def public_outputs(img, depth, buf, grads):
+    """What a caller of the timed path receives: render_gaussians()' image, inverse-depth image and buffers, backward()'s
+    gradients (its private `_arena` / `_view_payload` left out)."""
+    out = {"image": img, "depth_image": depth, **buf, **grads}
+    return {k: v for k, v in out.items() if v is not None and not k.startswith("_")}
+
+
+def output_rows(name, v, N, H, W):
+    """An output as rows, the unit --dump-outputs samples: pixels for the (H, W, ...) images, Gaussians for dL_dshs (16 SH rows
+    each), else its first axis."""
+    if v.dim() >= 2 and tuple(v.shape[:2]) == (H, W):
+        return v.reshape(H * W, *v.shape[2:])
+    return v.reshape(N, 16, 3) if name == "dL_dshs" else v
+
+
+def dump_plan(torch, outputs, N, H, W):
+    """--dump-outputs, planned on the untimed first step: name -> (shape, pick).  pick is None when the output is written whole;
+    when writing every output whole would pass DUMP_BYTES, each keeps at most `cap` rows (the same cap for all), a sorted sample
+    drawn with a fixed seed, one draw per row count (so the per-Gaussian arrays share their rows, the per-pixel ones theirs).
+    Floats are written as float32, integers as float64 (exact); 256 bytes per file cover the .npy header."""
+    rows = {k: output_rows(k, v, N, H, W) for k, v in outputs.items()}
+    width = {k: (4 if r.is_floating_point() else 8) * (r.numel() // max(1, len(r))) for k, r in rows.items()}
+    size = lambda cap: sum(min(len(r), cap) * width[k] + 256 for k, r in rows.items())
+    cap = max(len(r) for r in rows.values())
+    while cap > 0 and size(cap) > DUMP_BYTES:
+        cap //= 2
+    picks = {}
+    for r in rows.values():
+        if len(r) > cap and len(r) not in picks:
+            pick = np.sort(np.random.default_rng(0).choice(len(r), cap, replace=False))
+            picks[len(r)] = torch.from_numpy(pick).to(r.device)
+    return {k: (tuple(outputs[k].shape), picks.get(len(r))) for k, r in rows.items()}
+
+
+def dump_snapshot(torch, outputs, plan, N, H, W):
+    """The planned rows of the timed path's outputs, copied on the device in stream order (a later step may reuse the memory)."""
+    snap = {}
+    for k, (shape, pick) in plan.items():
+        v = outputs[k]
+        assert tuple(v.shape) == shape, f"--dump-outputs: {k} is {tuple(v.shape)} in the last timed step, {shape} in the first"
+        if pick is not None:
+            v = output_rows(k, v, N, H, W).index_select(0, pick)
+        snap[k] = v.to(torch.float32 if v.is_floating_point() else torch.float64, copy=True)
+    return snap
+
+
 def measure_exchange(gsr, dist, torch, args, world, N, means, step, exchange):
     """N > 1 only, AFTER the timed region (nothing here is part of `value`): what the gradient exchange costs on this rank.
     (1) ten more steps with the exchange's own events on: the compute stream's stalls at the two collectives and the rebuild
@@ -178,7 +231,11 @@ def main():
     ap.add_argument("--preheat-steps", type=int, default=100, help="untimed steps before the --warmup steps, so that a short warm-up "
                     "still starts from steady clocks (about 60 ms of load at C3)")
     ap.add_argument("--dump-steps", default=None, help="write every timed step's device time (ms, rank 0) to this file, one per line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the outputs of the last timed step (rank 0) as "
+                    "DIR/<name>.npy, float32 / float64, at most 64 MB in all (a fixed, seeded sample of rows when larger)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher.  Nothing here has touched the GPU (torch is not even
@@ -253,7 +310,7 @@ def main():
             grads.update(exchange.finish(grads, means, 3, average=True, out=sh_out))
         elif world > 1:
             gsr.dist.reduce_gradients(grads["_arena"], world)
-        return buf, grads
+        return img, depth, buf, grads
 
     vps = max(1, args.views_per_step) if world == 1 else 1
     if vps > 1:
@@ -283,12 +340,13 @@ def main():
     marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
     for m in marks:
         m.record()
-    buf, grads = step()
+    img, depth, buf, grads = step()
     torch.cuda.synchronize()
     D = int(buf["point_list"].shape[0])
     Nv = int((buf["radii"] > 0).sum().item())
     depth_passes = depth_passes_needed(buf["depths"].view(-1), buf["radii"].view(-1))
-    del buf, grads
+    plan = dump_plan(torch, public_outputs(img, depth, buf, grads), N, H, W) if args.dump_outputs and rank == 0 else None
+    del img, depth, buf, grads
     import gc
     gc.collect()
     gc.disable()
@@ -310,13 +368,18 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for k in range(args.steps):
-        step()
+        if k + 1 < args.steps:
+            step()
+        else:
+            last = step()       # kept for --dump-outputs; every earlier step's outputs are dropped at once
         marks[k + 1].record()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    snapshot = dump_snapshot(torch, public_outputs(*last), plan, N, H, W) if plan is not None else None
+    del last
     gc.enable()
     # the per-stage table comes from a SECOND, untimed loop with the library's stage events on every step
     stages, nrec = ({}, 0)
@@ -434,7 +497,7 @@ def main():
             t_all = time.perf_counter() - t0
             del pi, pd, pb, pgeom
             # the same frame is also a full-size parity check of the timed path (the oracle as checker, outside the timed region)
-            gb, gg = step()
+            _, _, gb, gg = step()
             torch.cuda.synchronize()
             gi = gsr.render_gaussians(**fkw)[0].cpu().numpy()
             sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -468,6 +531,10 @@ def main():
                                                  "kind": "port over threads (bands of Gaussians and of tile rows; the sort stays serial): NOT reference-equivalent, "
                                                          "a courtesy figure beside the single-thread baseline", "sample": f"the same frame, forward + backward {t_all:.2f} s"},
                                    "parity_full_size": {k: (round(v, 8) if isinstance(v, float) else v) for k, v in par.items()}}
+        if snapshot is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for k, v in snapshot.items():
+                np.save(os.path.join(args.dump_outputs, k + ".npy"), v.cpu().numpy())
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
