@@ -268,20 +268,17 @@ int check_count(const void *ws, int64_t N, int64_t D)
     return -1;
 }
 
-bool fwd_order_wanted(int tiles) { return tiles > 0 && tiles <= GSR_FO_MAX_TILES && !gsr_fwd_no_order && !gsr_fwd_xcd_map; }
+bool fwd_order_wanted(int tiles) { return tiles > 0 && tiles <= GSR_FO_MAX_TILES && !(gsr_debug_flags & 8192); } // GSR_DEBUG bit 13: row-major (tests)
 
 std::once_flag g_tuning_once;
 void read_tuning()
 {
     std::call_once(g_tuning_once, [] {
         if (const char *e = getenv("GSR_DEBUG")) gsr_debug_flags = atoi(e) & GSR_DEBUG_ALLOWED;
-        if (const char *e = getenv("GSR_BWD_BLOCK")) gsr_bwd_block = atoi(e);
-        if (const char *e = getenv("GSR_BWD_XCD")) gsr_bwd_xcd_map = atoi(e);
-        if (const char *e = getenv("GSR_FWD_XCD")) gsr_fwd_xcd_map = atoi(e) != 0;
-        if (const char *e = getenv("GSR_BWD_NO_ORDER")) gsr_bwd_no_order = atoi(e) != 0;
-        if (const char *e = getenv("GSR_NO_DEPTH_PACK")) gsr_no_depth_pack = atoi(e) != 0;
-        if (const char *e = getenv("GSR_NO_NARROWING")) gsr_no_narrowing = atoi(e) != 0;
-        if (const char *e = getenv("GSR_FWD_NO_ORDER")) gsr_fwd_no_order = atoi(e) != 0;
+        if (const char *e = getenv("GSR_BWD_BLOCK")) {
+            const int px = atoi(e);
+            gsr_bwd_block = (px == 32 || px == 64) ? px : 0;
+        }
     });
 }
 
@@ -300,7 +297,6 @@ GeomWs gsr_carve_geom(void *base, int64_t N)
     w.depth_ctl = w.blk_minmax ? w.blk_minmax + 4 * (size_t)gsr_div_up(N, 256) : nullptr; // the uint4 behind the last block's (preprocess clears it)
     w.rect_sorted = c.take<TileRect>((size_t)N);
     w.cnt_sorted = c.take<int32_t>((size_t)N);
-    w.doff = c.take<int32_t>((size_t)N);
     w.scan_tmp = c.take<int32_t>((size_t)gsr_div_up(N, 256) + 4);
     w.hist = c.take<int32_t>(256 * ((size_t)gsr_radix_blocks(N) + 1));
     w.acc[0] = c.take<int32_t>(3 * gsr_radix_acc_ints(N)); // the accumulators of both pass parities and of the first active pass, contiguous: preprocess clears them in one go
@@ -350,7 +346,7 @@ size_t gsr_block_order_ints(int32_t W, int32_t H)
     if (W <= 0 || H <= 0) return 0;
     const int64_t tiles = (int64_t)((W + GSR_TILE - 1) / GSR_TILE) * ((H + GSR_TILE - 1) / GSR_TILE);
     // images of more than GSR_BO_MAX_TILES tiles are never filed (gsr_internal.h): only the header (counters + the `filed` flag) is touched
-    return tiles > GSR_BO_MAX_TILES ? (size_t)GSR_BO_HEADER : gsr_bo_ints((int)tiles, (W + GSR_TILE - 1) / GSR_TILE);
+    return tiles > GSR_BO_MAX_TILES ? (size_t)GSR_BO_HEADER : gsr_bo_ints((int)tiles);
 }
 
 int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, void *geom_ws, size_t geom_ws_bytes,
@@ -386,13 +382,13 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     HIP_TRY(hipEventRecord(rb->ev, s));
     // Work that does not need D goes out before the host waits: Gaussians by depth bits (stable from id order, four 8-bit
     // passes over the high word, ending back in depth_item; the last one also carries each Gaussian's tile rectangle and
-    // tile count to its sorted position) and the depth-order offsets (exclusive scan of those counts).
+    // tile count to its sorted position).
     // How many of the four 8-bit passes this frame needs is decided on the device (DepthCtl); the host launches as many as the
     // previous frame in this workspace needed (its guess; four the first time).  If the guess turns out too low the launched
     // passes leave the data alone and all four are launched once the readback has said so.
     const int guess = (gsr_debug_flags & 256) ? 4 : depth_pass_guess(geom_ws);
     // (packed depth items, scan_sort.hip: the tile grid at 6 bits per coordinate, the ids in 24)
-    const int pack_ok = (!gsr_no_depth_pack && cam.grid_x <= 63 && cam.grid_y <= 63 && N <= (1 << 24)) ? 1 : 0;
+    const int pack_ok = (!(gsr_debug_flags & 2048) && cam.grid_x <= 63 && cam.grid_y <= 63 && N <= (1 << 24)) ? 1 : 0;
     HIP_TRY(gsr_launch_depth_sort(ws, N, s, guess, pack_ok));
     HIP_TRY(hipEventSynchronize(rb->ev)); // D (and the pass count) are on the host; the GPU keeps sorting
     const int32_t last = *rb->pinned;
@@ -407,9 +403,8 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     }
     if (needed > guess && !gsr_small_depth_path(N)) HIP_TRY(gsr_launch_depth_sort(ws, N, s, 4, pack_ok));
     mark(st, 3, s);
-    // (the depth-order offsets are made by gsr_forward_render, next to their one reader -- the expansion; the alternative path of
-    // GSR_DEBUG bit 9 scans them here, into ws.doff)
-    if ((gsr_debug_flags & 512) && !gsr_small_depth_path(N)) HIP_TRY(gsr_launch_scan(ws.cnt_sorted, nullptr, ws.doff, ws.scan_tmp, N, 2, nullptr, false, s));
+    // (the depth-order offsets -- the exclusive scan of those counts -- are made by gsr_forward_render, next to their one reader,
+    // the expansion)
     *num_rendered = (int64_t)last;
     if (last < 0 || (int64_t)last > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
     note_count(geom_ws, N, (int64_t)last, needed);
@@ -473,22 +468,15 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
     int32_t *order = binning->block_masks ? binning->block_order : nullptr;
     // (and not for a frame whose backward will take 8x8 blocks, which run in band order: the `filed` flag then stays 0)
     const bool file_order = order && tiles <= GSR_BO_MAX_TILES && gsr_bwd_block_px(N, D, tiles) == 32;
-    const bool by_gaussian = (gsr_debug_flags & 512) != 0; // GSR_DEBUG bit 9: the expansion by Gaussian + the first pass's own histogram kernel (tests, A/B)
     // the forward blend's tiles by last frame's cost classes (gsr_internal.h "forward tile order"): the table was made by the spare
     // workgroup of this frame's preprocess (gsr_forward_count, same condition), so it is never stale or foreign
     const bool use_fwd_order = fwd_order_wanted(tiles);
-    if (by_gaussian) {
-        mark(st, 5, s);
-        HIP_TRY(gsr_launch_expand(gw.id_sorted, gw.doff, gw.rect_sorted, bw.tile_a, N, cam.grid_x, D, id_shift, item_bytes, binning->ranges, 2 * tiles, bw.acc[0],
-                                  (int)gsr_radix_acc_ints(D), order, order ? GSR_BO_HEADER : 0, file_order ? 1 : 0, s));
-    } else {
-        // one offset per 256 depth-sorted Gaussians (stage "depth_scan"), then one workgroup per radix block of the item array,
-        // which also leaves the first partition pass's block histograms
-        HIP_TRY(gsr_launch_depth_block_offsets(gw, N, binning->ranges, 2 * tiles, bw.acc[0], (int)gsr_radix_acc_ints(D), order, order ? GSR_BO_HEADER : 0,
-                                               file_order ? 1 : 0, s));
-        mark(st, 5, s);
-        HIP_TRY(gsr_launch_expand_blocks(gw, bw.tile_a, N, cam.grid_x, D, id_shift, item_bytes, pass_bits(0, 0), bw.hist, bw.acc[0], s));
-    }
+    // one offset per 256 depth-sorted Gaussians (stage "depth_scan"), then one workgroup per radix block of the item array,
+    // which also leaves the first partition pass's block histograms
+    HIP_TRY(gsr_launch_depth_block_offsets(gw, N, binning->ranges, 2 * tiles, bw.acc[0], (int)gsr_radix_acc_ints(D), order, order ? GSR_BO_HEADER : 0,
+                                           file_order ? 1 : 0, s));
+    mark(st, 5, s);
+    HIP_TRY(gsr_launch_expand_blocks(gw, bw.tile_a, N, cam.grid_x, D, id_shift, item_bytes, pass_bits(0, 0), bw.hist, bw.acc[0], s));
     mark(st, 6, s);
     // 4. stable partition by tile id
     void *tsrc = bw.tile_a, *tdst = bw.tile_b;
@@ -496,10 +484,10 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
     // 6 + 23): the first pass writes 32-bit items and the second recovers the first digit from the item's position
     // (scan_sort.hip ScatterFinal) -- 4 instead of 8 bytes per item through the second histogram and the final scatter.
     const int bits0 = pass_bits(0, 0);
-    const bool narrowing = !narrow && npass == 2 && (tb - bits0) + id_bits <= 32 && !gsr_no_narrowing;
+    const bool narrowing = !narrow && npass == 2 && (tb - bits0) + id_bits <= 32 && !(gsr_debug_flags & 4096);
     for (int pass = 0, shift = 0; pass < npass; ++pass) {
         const int bits = pass_bits(pass, shift);
-        const bool hist_ready = pass == 0 && !by_gaussian;
+        const bool hist_ready = pass == 0;
         if (pass + 1 < npass) {
             HIP_TRY(gsr_launch_radix_pass(tsrc, tdst, bw.hist, bw.acc[pass & 1], D, id_shift + shift, bits, item_bytes, bw.acc[(pass + 1) & 1], s, hist_ready,
                                           narrowing ? id_bits : 0, narrowing ? bw.acc[pass & 1] : nullptr));

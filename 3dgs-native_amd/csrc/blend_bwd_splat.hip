@@ -9,7 +9,7 @@
 //     R_k = prod_{deeper j <= k} 1/(1 - alpha_j)      ->  T_k = T_final * R_k          (backward.py:658)
 //     Q_k = sum_{deeper j <  k} alpha_j T_j (c_j . dL_dpixel)  ( = T_k (1-alpha_k) accum_rec . dL_dpixel, :667-671)
 // so that dL_dalpha_k = T_k (c_k . dL_dpixel) - (Q_k + T_final bg . dL_dpixel) / (1 - alpha_k)   (:671-680).
-// One single-wave workgroup per 8x4 pixel block (8 per tile, 20 000 at 800x800; 8x8 and 4x4 are also
+// One single-wave workgroup per 8x4 pixel block (8 per tile, 20 000 at 800x800; 8x8 is also
 // instantiated) replays its tile's list back to front.  Most entries of a tile's list cannot touch a given block, so the wave first
 // COMPACTS the stream: 64 candidates at a time are tested against the block rectangle (exact convex
 // minimum of the conic over the rectangle vs ln(255 o), conservative) and survivors are queued in an
@@ -205,7 +205,7 @@ __device__ __forceinline__ float power_ref_order(float ca2, float cb2, float tc,
 constexpr int FILL_K = GSR_FILL_K;
 // GSR_BWD_BUCKET: entries per bucket -- 32 (the product), 64 (rounds 2-3) or 16.  A bucket of at most 32 entries runs TWO pixels per
 // step (each 32-lane half holds the bucket against its own pixel; scans of five DPP steps instead of six), one of at most 16
-// FOUR (GSR_BWD_FOUR: 16-lane rows, four-step scans) -- the "16-entry x 4-pixel lane layout" of round 3's notes, here as the form
+// FOUR (16-lane rows, four-step scans) -- the "16-entry x 4-pixel lane layout" of round 3's notes, here as the form
 // the LAST bucket of a block takes.  Fewer scan steps per (entry, pixel) pair against more buckets (record gather, LDS transpose,
 // flush per bucket).  Round 4, rocprofv3 kernel averages over 60 launches, three interleaved runs per build on one box
 // (profiles/r04_d_bwd_bucket_kernel_averages.txt -- the kernel's run-to-run spread is +-4 %, so single A/B pairs mislead):
@@ -214,12 +214,6 @@ constexpr int FILL_K = GSR_FILL_K;
 #ifndef GSR_BWD_BUCKET
 #define GSR_BWD_BUCKET 32
 #endif
-#ifndef GSR_BWD_FOUR
-#define GSR_BWD_FOUR 1      // 1: a bucket of at most 16 entries runs four pixels per step (16-lane rows, four-step scans)
-#endif
-#ifndef GSR_BWD_SKIP2
-#define GSR_BWD_SKIP2 1     // 1: the two-pixel form skips a step when both pixels' replays have ended
-#endif
 #ifndef GSR_BWD_BUCKET_WIDE
 #define GSR_BWD_BUCKET_WIDE GSR_BWD_BUCKET   // the same for the 8x8 blocks (A/B)
 #endif
@@ -227,7 +221,7 @@ constexpr int BUCKET = GSR_BWD_BUCKET;
 constexpr int QCAP = 128;                 // ring of compacted entries (power of two, >= 63 + 64): a chunk is consumed only while it fits
 
 // USE_MASKS: the per-block hit masks the forward wrote (GsrBinning.block_masks) replace the compaction's own test.  They are
-// per 8x4 block; an 8x8 block ORs the bits of its two halves, a 4x4 block keeps its own (finer) test.
+// per 8x4 block; an 8x8 block ORs the bits of its two halves.
 template <int BW, int BH, bool USE_MASKS>
 __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, int grid_x, float bg0, float bg1, float bg2,
                                                                   const int32_t *__restrict__ ranges,
@@ -236,7 +230,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
                                                                   const float *__restrict__ final_T,
                                                                   const int32_t *__restrict__ n_contrib,
                                                                   const float *__restrict__ dL_dpixels,
-                                                                  const uint8_t *__restrict__ block_masks, GradRec *__restrict__ acc, int dbg, int xcd_map, int n_blocks,
+                                                                  const uint8_t *__restrict__ block_masks, GradRec *__restrict__ acc, int dbg, int n_blocks,
                                                                   const int32_t *__restrict__ block_order, int bo_cap)
 {
     constexpr int NPIX = BW * BH;            // pixels of the block this wave owns
@@ -252,24 +246,17 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
 
     const int lane = threadIdx.x;
     // Workgroup ids are handed to the eight XCDs round-robin, so consecutive ids -- the PER_TILE blocks of one tile, which read
-    // the same list, masks and records -- land on eight different L2s.  xcd_map != 0: XCD x takes the x-th eighth of the blocks
-    // instead, so that a tile's blocks run on ONE XCD, next to each other in its queue (grid = 8 * ceil(blocks / 8)).
-    // xcd_map 2: XCD x takes the tiles t with t % 8 == x (interleaved: every XCD gets the same mix of deep and shallow tiles,
-    // where the bands of map 1 give the XCDs holding the image centre more work than the others).
+    // the same list, masks and records -- would land on eight different L2s.  Unless the forward filed the blocks, XCD x takes the
+    // x-th eighth of the blocks instead, so that a tile's blocks run on ONE XCD, next to each other in its queue
+    // (grid = 8 * ceil(blocks / 8)).
     int bid = blockIdx.x;
     const bool ordered = block_order && block_order[GSR_BO_FLAG] != 0; // the forward filed the blocks (it skips large images)
-    if (ordered) {
-    } else if (xcd_map == 1 || block_order) {
+    if (!ordered) {
         const int per = (n_blocks + 7) >> 3, k = blockIdx.x >> 3; // (the grid of the ordered path may be larger than this needs)
         if (k >= per) return;
         bid = (blockIdx.x & 7) * per + k;
         if (bid >= n_blocks) return;
-    } else if (xcd_map == 2) {
-        const int k = blockIdx.x >> 3; // position in this XCD's queue
-        bid = ((k / PER_TILE) * 8 + (blockIdx.x & 7)) * PER_TILE + (k % PER_TILE);
-        if (bid >= n_blocks) return;
-    }
-    if (ordered) {
+    } else {
         // The forward filed every block under (band of its tile, cost class) -- gsr_internal.h "block order".  Launch slot
         // blockIdx.x runs on XCD blockIdx.x % 8 as the (blockIdx.x / 8)-th workgroup of that XCD's queue: it takes the band's
         // k-th block counting from the heaviest class down.  Lane c looks at class CLASSES - 1 - c.
@@ -400,7 +387,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         const int n = min(bucket, qn);
         // A bucket of at most 32 entries (every block's last one, half of the time) runs TWO pixels per step: lanes 0-31 hold
         // the entries against pixel 2s, lanes 32-63 the same entries against pixel 2s + 1, and the scans stay inside each half.
-        const bool four = n <= 16 && BW % 4 == 0 && GSR_BWD_FOUR; // ... and one of at most 16 FOUR pixels per step, a 16-lane row each
+        const bool four = n <= 16; // ... and one of at most 16 FOUR pixels per step, a 16-lane row each
         const bool two = !four && n <= 32 && (NPIX % 2 == 0);
         const int elane = four ? (lane & 15) : two ? (lane & 31) : lane; // which entry of the bucket this lane holds
         const bool valid = elane < n;
@@ -505,9 +492,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
                     const int q = q2 + sub;
                     const float4 pb = s_pb[q];
                     const int pkept = __float_as_int(pb.w);
-#if GSR_BWD_SKIP2
                     if (__ballot(pkept > idx_min) == 0ull) continue; // both pixels' replays end before every entry of the bucket
-#endif
                     TL_COUNT(7, 1ull)
                     GSR_PIXEL_STEP(q, half_scan_mul, half_scan_add, (lane & 31) == 31)
                 }
@@ -599,8 +584,6 @@ extern "C" int gsr_debug_bwd_phases(unsigned long long *out /* [waves][12] */, i
 #endif
 
 int gsr_bwd_block = 0;    // GSR_BWD_BLOCK: 0 = by the frame's tile pairs per Gaussian (see the launcher)
-int gsr_bwd_no_order = 0;  // GSR_BWD_NO_ORDER: ignore the forward's block order (A/B)
-int gsr_bwd_xcd_map = 1;   // GSR_BWD_XCD (see the kernel): on by default, 171 -> 165 us at C3
 int gsr_debug_flags = 0; // see gsr_internal.h
 
 hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *ranges, const int32_t *point_list, const BlendRec *rec,
@@ -612,25 +595,22 @@ hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *range
 #define LAUNCH(BW, BH, M)                                                                                                     \
     do {                                                                                                                      \
         const int nblk = tiles * (256 / ((BW) * (BH)));                                                                       \
-        const int ppt = 256 / ((BW) * (BH)); /* map 2 walks whole groups of 8 tiles: grid = 8 * ppt * ceil(tiles / 8) */        \
-        const int32_t *bo = ((M) && (BW) == 8 && (BH) == 4 && !gsr_bwd_no_order) ? block_order : nullptr; /* 8x4 blocks only */    \
-        const int bo_cap = gsr_bo_cap(tiles, cam.grid_x);                                                                                 \
-        const int grid = bo ? 8 * 8 * gsr_bo_tiles_per_band(tiles, cam.grid_x) : gsr_bwd_xcd_map == 2 ? 8 * ppt * ((tiles + 7) / 8) : gsr_bwd_xcd_map ? 8 * ((nblk + 7) / 8) : nblk; \
+        const int32_t *bo = ((M) && (BH) == 4) ? block_order : nullptr; /* 8x4 blocks only */                                 \
+        const int grid = bo ? 8 * 8 * gsr_bo_tiles_per_band(tiles) : 8 * ((nblk + 7) / 8);                                   \
         hipLaunchKernelGGL((blend_backward_splat_kernel<BW, BH, M>), dim3(grid), dim3(64), 0, s, cam.W, cam.H, cam.grid_x,    \
                            cam.bg[0], cam.bg[1], cam.bg[2], ranges, point_list, rec, img.final_T, img.n_contrib, dL_dpixels,  \
-                           block_masks, acc, gsr_debug_flags, gsr_bwd_xcd_map, nblk, bo, bo_cap);                             \
+                           block_masks, acc, gsr_debug_flags, nblk, bo, gsr_bo_cap(tiles));                                   \
     } while (0)
     // Pixels per wave.  The block masks discard an entry for a whole block, so small splats (few tile pairs per Gaussian) want the
     // finer 8x4 blocks; splats that cover their tiles anyway want 8x8, which stages every entry in half as many waves.  Measured
     // over D / N from 2.7 to 262 (tools/bwd_block_sweep.py, profiles/r04_q_bwd_block_size_sweep.txt): at 800 x 800 the curves
     // cross at D / N of 18-22 (8x4 is 10-25 % faster below 13, 8x8 is 14-24 % faster above 40); images of more than
     // GSR_BO_MAX_TILES tiles, whose 8x4 blocks the forward does not file by cost, cross at 4-5 already (1080p: 8x8 is 5-24 %
-    // faster from 5.4 up).  GSR_BWD_BLOCK = 32, 64 or 16 (4x4) forces one size.
-    const int block_px = gsr_bwd_block_px(N, D, tiles);
-    switch (block_px) {
-    case 16: LAUNCH(4, 4, false); break;
-    case 64: if (block_masks) LAUNCH(8, 8, true); else LAUNCH(8, 8, false); break;
-    default: if (block_masks) LAUNCH(8, 4, true); else LAUNCH(8, 4, false); break;
+    // faster from 5.4 up).  GSR_BWD_BLOCK = 32 or 64 forces one size.
+    if (gsr_bwd_block_px(N, D, tiles) == 64) {
+        if (block_masks) LAUNCH(8, 8, true); else LAUNCH(8, 8, false);
+    } else {
+        if (block_masks) LAUNCH(8, 4, true); else LAUNCH(8, 4, false);
     }
 #undef LAUNCH
     return hipGetLastError();

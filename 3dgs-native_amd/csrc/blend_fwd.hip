@@ -61,12 +61,9 @@ __device__ const int *g_fwd_order = nullptr; // experiment (tools/residency.py -
 
 namespace {
 
-// What a wave leaves for the next frame's tile order (gsr_internal.h "forward tile order"): 1 = its measured life in 100 MHz ticks
-// (the product since late round 4: C3 blend_fwd 98.0 -> 96.3 us in two same-box A/B rounds, the Lego trainer's 52.4 -> 49.0 us per
-// iteration, profiles/r04_s_fwd_cost_is_wave_life.txt), 0 = entries walked and staged (max of walked + staged / 2 ranked the tiles)
-#ifndef GSR_FWD_COST_LIFE
-#define GSR_FWD_COST_LIFE 1
-#endif
+// What a wave leaves for the next frame's tile order (gsr_internal.h "forward tile order"): its measured life in 100 MHz ticks
+// (since late round 4, in place of the entries it walked and staged: C3 blend_fwd 98.0 -> 96.3 us in two same-box A/B rounds, the
+// Lego trainer's 52.4 -> 49.0 us per iteration, profiles/r04_s_fwd_cost_is_wave_life.txt)
 constexpr int BATCH = 256;
 constexpr int NWAVES = 4;
 
@@ -121,7 +118,7 @@ struct StagedRec {
 // walk loop as well (70 VGPRs, 7 workgroups per CU instead of 8) and the kernel goes from 105 to 132 us; as a call made once per
 // wave, with next to nothing live across it, the kernel keeps its 64 VGPRs / 73 SGPRs and needs no scratch.
 __device__ __attribute__((noinline)) void file_blocks(const uint8_t *__restrict__ block_masks, int32_t *__restrict__ block_order, int bo_cap,
-                                                      int n_tiles, int grid_x, int tile, int start, int last)
+                                                      int n_tiles, int tile, int start, int last)
 {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int kept = last;
@@ -146,8 +143,8 @@ __device__ __attribute__((noinline)) void file_blocks(const uint8_t *__restrict_
 #pragma unroll
     for (int d = 16; d >= 1; d >>= 1) hits += __shfl_xor(hits, d, 64);
     if ((lane & 31) == 0) {
-        const int band = gsr_bo_band(tile, n_tiles, grid_x);
-        const int q = (band * GSR_BO_CLASSES + gsr_bo_class(hits)) * GSR_BO_SHARDS + ((tile - band * gsr_bo_tiles_per_band(n_tiles, grid_x)) & (GSR_BO_SHARDS - 1));
+        const int band = gsr_bo_band(tile, n_tiles);
+        const int q = (band * GSR_BO_CLASSES + gsr_bo_class(hits)) * GSR_BO_SHARDS + ((tile - band * gsr_bo_tiles_per_band(n_tiles)) & (GSR_BO_SHARDS - 1));
         const int pos = atomicAdd(&block_order[q], 1);
         if (pos < bo_cap) block_order[GSR_BO_HEADER + (size_t)q * bo_cap + pos] = tile * 8 + blk;
     }
@@ -158,7 +155,7 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
                                                             const int32_t *__restrict__ point_list,
                                                             const BlendRec *__restrict__ rec, float *__restrict__ image,
                                                             float *__restrict__ inv_depth, float *__restrict__ final_T,
-                                                            int32_t *__restrict__ n_contrib, uint8_t *__restrict__ block_masks, int xcd_map,
+                                                            int32_t *__restrict__ n_contrib, uint8_t *__restrict__ block_masks,
                                                             int n_tiles, int32_t *__restrict__ block_order, int bo_cap,
                                                             float4 *__restrict__ clear4, long long clear_n4, int clear_wgs,
                                                             const int32_t *__restrict__ tile_order, int32_t *__restrict__ tile_cost)
@@ -178,15 +175,8 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
     __shared__ uint16_t s_list[NWAVES][BATCH + LIST_PAD];  // per wave: byte offsets (into s_rec) of its live entries, in list order
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // xcd_map: workgroup ids go to the eight XCDs round-robin; with the map XCD x renders the x-th eighth of the tiles (a band
-    // of rows), so neighbouring tiles -- which share most of their Gaussians -- share an L2 (grid = 8 * ceil(tiles / 8))
     int tile = blockIdx.x;
-    if (xcd_map) {
-        tile = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
-        if (tile >= n_tiles) return;
-    } else if (tile_order) {
-        tile = tile_order[blockIdx.x]; // heaviest class first, by what the tiles cost a frame ago (gsr_internal.h "forward tile order")
-    }
+    if (tile_order) tile = tile_order[blockIdx.x]; // heaviest class first, by what the tiles cost a frame ago (gsr_internal.h "forward tile order")
 #ifdef GSR_CENSUS
     if (g_fwd_order) tile = g_fwd_order[blockIdx.x];
 #endif
@@ -197,9 +187,7 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
     const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     const int my_bits = 5 << ((wv >> 1) * 4 + (wv & 1)); // this wave's 8x8 block = the 8x4 blocks k0 and k0 + 2
 
-#if GSR_FWD_COST_LIFE
     const unsigned long long t_born = wall_clock64();
-#endif
     const int2 range = *reinterpret_cast<const int2 *>(ranges + 2 * tile);
     const int start = range.x, end = range.y;
 
@@ -219,8 +207,7 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
     // the batch that was prefetched with it, then goes: the others' next wait for it falls under their walk of that batch.
     __shared__ int s_alive;
     if (tid == 0) s_alive = 0xF;
-    [[maybe_unused]] int walked = 0;
-    int alive_cur = 0xF; // walked: list entries this wave blended (its share of the tile's cost, for the next frame's order)
+    int alive_cur = 0xF;
     const int wv_u = __builtin_amdgcn_readfirstlane(wv); // wave-uniform copy: the bookkeeping below stays in scalar registers
     auto rank_in = [&](int set) { return __popc(set & ((1 << wv_u) - 1)); };
     int nid = (start + tid < end) ? point_list[start + tid] : -1;
@@ -231,7 +218,6 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
         na = rp[0]; nb = rp[1];
         ncd = *reinterpret_cast<const float2 *>(rp + 2);
     }
-    [[maybe_unused]] int staged = 0; // list entries staged by the time this wave leaves
     for (int base = start; base < end;) {
         __syncthreads(); // every surviving wave has walked the last batch (LDS reuse) and the leavers' bits are cleared
         TL(0)
@@ -303,7 +289,6 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         TL(4) // list build
         TL_COUNT(7, (unsigned long long)n)
-        walked += n;
 
         // walk the list; two-deep software pipeline: the offset of entry k+2 and the record of entry k+1 are in flight while
         // entry k is blended
@@ -364,7 +349,6 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
         done = pixf_x == PARKED_X;
         TL(5)
         base += cnt;
-        staged = base - start;
         alive_cur = alive_next;
         if (__all(done) && base < end) {
             if (lane == 0) atomicAnd(&s_alive, ~(1 << wv_u)); // the next top barrier is behind this
@@ -379,12 +363,8 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
         image[3 * px + 2] = cb + T * bg2;
         inv_depth[px] = cd;
     }
-#if GSR_FWD_COST_LIFE
     if (tile_cost && lane == 0) tile_cost[tile * 4 + wv] = (int)min((unsigned long long)0x7FFF, wall_clock64() - t_born) << 16;
-#else
-    if (tile_cost && lane == 0) tile_cost[tile * 4 + wv] = (min(walked, 0x7FFF) << 16) | min(staged, 0xFFFF);
-#endif
-    if (block_order) file_blocks(block_masks, block_order, bo_cap, n_tiles, grid_x, tile, start, last);
+    if (block_order) file_blocks(block_masks, block_order, bo_cap, n_tiles, tile, start, last);
     TL(6)
     TL_FLUSH
 }
@@ -415,26 +395,19 @@ extern "C" int gsr_debug_fwd_phases(unsigned long long *out /* [waves][8] */, in
 }
 #endif
 
-int gsr_fwd_xcd_map = 0; // GSR_FWD_XCD (see the kernel)
-int gsr_fwd_no_order = 0; // GSR_FWD_NO_ORDER: row-major dispatch instead of last frame's cost classes
-
 hipError_t gsr_launch_blend_forward(const CamK &cam, const int32_t *ranges, const int32_t *point_list, const BlendRec *rec,
                                     const GsrImage &img, uint8_t *block_masks, int32_t *block_order, void *clear, size_t clear_bytes,
                                     hipStream_t s, const int32_t *tile_order, int32_t *tile_cost)
 {
     const int tiles = cam.grid_x * cam.grid_y;
     if (tiles <= 0) return hipSuccess;
-    // the clear is part of the call's contract (gsr.h GsrBinning.backward_ws): when this launch cannot host the spare workgroups
-    // (the XCD map derives the tile from gridDim.x) it is a memset in front of the kernel instead
-    if (clear && gsr_fwd_xcd_map) {
-        if (hipError_t e = hipMemsetAsync(clear, 0, clear_bytes, s)) return e;
-    }
-    const long long clear_n4 = (clear && !gsr_fwd_xcd_map) ? (long long)(clear_bytes / 16) : 0;
+    // the clear is part of the call's contract (gsr.h GsrBinning.backward_ws): the kernel's spare workgroups do it
+    const long long clear_n4 = clear ? (long long)(clear_bytes / 16) : 0;
     const int clear_wgs = (int)std::min<long long>(2048, (clear_n4 + 255) / 256);
-    const int grid = (gsr_fwd_xcd_map ? 8 * ((tiles + 7) / 8) : tiles) + clear_wgs;
+    const int grid = tiles + clear_wgs;
     hipLaunchKernelGGL(blend_forward_kernel, dim3(grid), dim3(256), 0, s, cam.W, cam.H, cam.grid_x, cam.bg[0], cam.bg[1], cam.bg[2],
-                       ranges, point_list, rec, img.image, img.inv_depth, img.final_T, img.n_contrib, block_masks, gsr_fwd_xcd_map, tiles,
-                       block_masks ? block_order : nullptr, gsr_bo_cap(tiles, cam.grid_x), reinterpret_cast<float4 *>(clear), clear_n4, clear_wgs,
-                       gsr_fwd_xcd_map ? nullptr : tile_order, tile_cost);
+                       ranges, point_list, rec, img.image, img.inv_depth, img.final_T, img.n_contrib, block_masks, tiles,
+                       block_masks ? block_order : nullptr, gsr_bo_cap(tiles), reinterpret_cast<float4 *>(clear), clear_n4, clear_wgs,
+                       tile_order, tile_cost);
     return hipGetLastError();
 }

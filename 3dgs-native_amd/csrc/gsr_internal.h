@@ -48,7 +48,6 @@ struct GeomWs {
     void *depth_ctl;      // DepthCtlRaw (scan_sort.hip), the uint4 behind the last block's extremes: this frame's visible depth range and count
     TileRect *rect_sorted; // [N] tile rectangles in depth order (written by the last depth-sort pass)
     int32_t *cnt_sorted;  // [N] tile counts in depth order (same pass)
-    int32_t *doff;        // [N] exclusive tile-pair offsets in depth order
     int32_t *scan_tmp;    // [N / 256 + 4] partial sums for the scans (preprocess writes one per 256 Gaussians)
     int32_t *hist;        // [nb(N)][256] radix block histograms
     int32_t *acc[2];      // [gsr_radix_acc_ints(N)] each: digit + super-block totals of a pass; consecutive passes alternate
@@ -93,10 +92,9 @@ hipError_t gsr_launch_scan(const int32_t *in, const uint64_t *items, int32_t *ou
                            const uint32_t *blk_minmax = nullptr, void *depth_ctl = nullptr /* mode 0: also derive the depth sort's DepthCtl */);
 hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, hipStream_t s, int launch_passes = 4 /* the last `launch_passes` of the four */,
                                  int pack_ok = 0 /* the sizes allow packed depth items (scan_sort.hip) */);
-extern int gsr_no_depth_pack; // GSR_NO_DEPTH_PACK: the last depth pass always gathers the rectangles by id (A/B, tests)
 hipError_t gsr_launch_scan_ctl_hist(const int32_t *tiles_touched, int32_t *point_offsets, const GeomWs &ws, int64_t n, int32_t *total_out, hipStream_t s);
 #define GSR_SMALL_SORT_N 8192          // up to this many Gaussians one workgroup sorts, carries and scans (scan_sort.hip)
-bool gsr_small_depth_path(int64_t n); // true: gsr_launch_depth_sort also writes the depth-order offsets (no separate scan)
+bool gsr_small_depth_path(int64_t n); // true: gsr_launch_depth_sort sorts in one workgroup
 
 // One stable LSD radix pass by the `bits`-wide (4..8) digit at `shift`; items are uint64 (item_bytes 8) or uint32 (4).
 #ifndef GSR_RADIX_CHUNK
@@ -154,11 +152,7 @@ hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *a
                                        int low_bits = 0 /* ... and digit width */);
 
 // Tile items are (tile << id_shift | gaussian id): uint64 with id_shift = 32, or uint32 when tile bits + id bits <= 32.
-hipError_t gsr_launch_expand(const uint32_t *id_sorted, const int32_t *doff, const TileRect *rect, void *tile_items,
-                             int64_t n, int grid_x, int64_t D, int id_shift, int item_bytes, int32_t *ranges, int ranges_n,
-                             int32_t *zero_acc, int zero_n /* accumulators of the first partition pass, cleared here */,
-                             int32_t *zero_b, int zero_b_n /* the block-order header, or NULL */, int bo_flag /* its `filed` flag */, hipStream_t s);
-// The product path of the expansion (scan_sort.hip): one prefix per 256 depth-sorted Gaussians (into ws.scan_tmp; also clears the
+// The expansion (scan_sort.hip): one prefix per 256 depth-sorted Gaussians (into ws.scan_tmp; also clears the
 // ranges, the first partition pass's accumulators and the block-order header), then one workgroup per radix block of the output,
 // which also leaves the first partition pass's histograms (launch that pass with hist_ready).
 // ---- forward tile order (round 4) ----
@@ -168,13 +162,11 @@ hipError_t gsr_launch_expand(const uint32_t *id_sorted, const int32_t *doff, con
 // is known before the blend, from 113 to 108 (rank correlation 0.05-0.16 with the life: saturation cuts every deep list at about the
 // same depth).  What does predict a tile's work is the tile's work a frame ago: a trainer comes back to its views, a viewer moves
 // its camera smoothly.  So every wave of the forward blend leaves behind its cost -- its measured life in 100 MHz ticks since late
-// round 4, the entries it walked and staged before (blend_fwd.hip GSR_FWD_COST_LIFE) -- (fwd_cost, 4 ints per tile, in
+// round 4 -- (fwd_cost, 4 ints per tile, in
 // the caller's geom workspace, which persists between frames as long as the caller keeps it), and the next forward on that
 // workspace dispatches the tiles by cost class, heaviest first (fwd_order, made by a spare workgroup of preprocess_kernel
 // every frame from whatever fwd_cost holds -- garbage in a fresh workspace gives some permutation, never a wrong one).  Execution
 // order only: every tile computes what it always did.  Not for images of more than GSR_FO_MAX_TILES tiles (many rounds, no tail).
-extern int gsr_fwd_no_order; // GSR_FWD_NO_ORDER: plain row-major dispatch (A/B)
-extern int gsr_no_narrowing; // GSR_NO_NARROWING: the second tile pass keeps 64-bit items where the first could narrow them (A/B, tests)
 hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *ranges, int ranges_n, int32_t *zero_acc, int zero_n, int32_t *zero_b,
                                           int zero_b_n, int bo_flag, hipStream_t s);
 hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t n, int grid_x, int64_t D, int id_shift, int item_bytes, int bits0,
@@ -190,7 +182,8 @@ hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t 
 // (Also built and measured: the same filing beside the clearing of the accumulators, in one kernel at the start of
 // gsr_backward -- the filing workgroups' chains of dependent loads crawl under that kernel's 64 MB of stores: 13 -> 36 us at C3,
 // 48 -> 140 us at C5, more than the blend gains.)
-// Layout, int32: [GSR_BO_BANDS][GSR_BO_CLASSES][GSR_BO_SHARDS] counters, a `filed` flag (+ 3 pad) -- written by the forward's expand_kernel --
+// Layout, int32: [GSR_BO_BANDS][GSR_BO_CLASSES][GSR_BO_SHARDS] counters, a `filed` flag (+ 3 pad) -- cleared and flagged by the
+// forward's depth_block_offsets_kernel --
 // then [GSR_BO_BANDS][GSR_BO_CLASSES][GSR_BO_SHARDS][cap] block ids (tile * 8 + block), cap = 8 * ceil(tiles per band / shards).
 // A (band, class) queue is split over 16 shards by tile (tile % 16) because the filing takes its slot with a RETURNED atomic:
 // 20 000 of them onto 256 addresses serialise at the memory side; onto 4 096 they do not.
@@ -204,32 +197,12 @@ hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t 
 // rounds, 164 -> 154 us for 5 us more in the forward); at 1920x1080 (65 280 blocks, 8 rounds) the blend gains 2 % and the filing
 // costs the forward more than that, so larger images keep the plain band order.
 #define GSR_BO_MAX_TILES 4096
-// Which band (= XCD) a tile belongs to.  GSR_BO_ROWS = 0: eight bands of consecutive tiles (an eighth of the image each: the XCDs
-// holding the image centre get more work than the others); GSR_BO_ROWS = G > 0: groups of G tile rows dealt to the bands in turn.
-#ifndef GSR_BO_ROWS
-#define GSR_BO_ROWS 0
-#endif
-__host__ __device__ static inline int gsr_bo_tiles_per_band(int tiles, int grid_x)
-{
-#if GSR_BO_ROWS > 0
-    const int grid_y = (tiles + grid_x - 1) / grid_x;
-    return ((grid_y + GSR_BO_BANDS * GSR_BO_ROWS - 1) / (GSR_BO_BANDS * GSR_BO_ROWS)) * GSR_BO_ROWS * grid_x; // an upper bound
-#else
-    (void)grid_x;
-    return (tiles + GSR_BO_BANDS - 1) / GSR_BO_BANDS;
-#endif
-}
-__host__ __device__ static inline int gsr_bo_band(int tile, int tiles, int grid_x)
-{
-#if GSR_BO_ROWS > 0
-    (void)tiles;
-    return ((tile / grid_x) / GSR_BO_ROWS) % GSR_BO_BANDS;
-#else
-    return tile / gsr_bo_tiles_per_band(tiles, grid_x);
-#endif
-}
-static inline int gsr_bo_cap(int tiles, int grid_x) { return 8 * ((gsr_bo_tiles_per_band(tiles, grid_x) + GSR_BO_SHARDS - 1) / GSR_BO_SHARDS); }
-static inline size_t gsr_bo_ints(int tiles, int grid_x) { return GSR_BO_HEADER + (size_t)GSR_BO_QUEUES * (size_t)gsr_bo_cap(tiles, grid_x); }
+// Which band (= XCD) a tile belongs to: eight bands of consecutive tiles (an eighth of the image each: the XCDs holding the image
+// centre get more work than the others).
+__host__ __device__ static inline int gsr_bo_tiles_per_band(int tiles) { return (tiles + GSR_BO_BANDS - 1) / GSR_BO_BANDS; }
+__host__ __device__ static inline int gsr_bo_band(int tile, int tiles) { return tile / gsr_bo_tiles_per_band(tiles); }
+static inline int gsr_bo_cap(int tiles) { return 8 * ((gsr_bo_tiles_per_band(tiles) + GSR_BO_SHARDS - 1) / GSR_BO_SHARDS); }
+static inline size_t gsr_bo_ints(int tiles) { return GSR_BO_HEADER + (size_t)GSR_BO_QUEUES * (size_t)gsr_bo_cap(tiles); }
 // class of a block that keeps `hits` entries: four classes per octave from 8 entries up (class 0: fewer than 8)
 __host__ __device__ static inline int gsr_bo_class(int hits)
 {
@@ -264,26 +237,28 @@ hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const G
 
 // tuning knobs (read once from the environment by api.hip; defaults are the measured best)
 hipError_t gsr_launch_view_payload(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *payload, hipStream_t s);
-// GSR_DEBUG (environment, read once): bit 5 forces 64-bit tile items, bit 6 the large-n radix chunks, bit 7 the scanned
-// super-block rows of many-block radix passes (radix_superscan_kernel), bit 8 all four depth-sort passes whatever the depth
-// range, bit 9 the expansion by Gaussian (a wave per 64 or 8 of them, from a device-wide scan of the depth-order offsets, followed
-// by the first partition pass's own histogram kernel) instead of the expansion by output block; bit 10 switches the
-// one-workgroup depth stage of small scenes OFF (so small test scenes also run the multi-kernel chain) -- same results by
-// other code paths (tests/test_gpu_alt_paths.py).  Bits 0-3 are timing ablations that give WRONG results (skip the atomics,
-// one pixel per bucket, no SH fetch, no stores); they exist only in the separate ablation build (`make ablate` ->
-// libgsr_hip_ablate.so, -DGSR_ABLATE, used by tools/stage_bench.sh) and are compiled out of libgsr_hip.so.
+// GSR_DEBUG (environment, read once by api.hip): every bit forces at any size a path that some frame size takes anyway, so the
+// oracle comparison covers it -- same results by other code paths (tests/test_gpu_alt_paths.py):
+//   bit  5 (32)    64-bit tile items (tile bits + id bits > 32)
+//   bit  6 (64)    the large-n radix chunks (N > 4 M)
+//   bit  7 (128)   the scanned super-block rows of many-block radix passes (radix_superscan_kernel; D > 8.4 M)
+//   bit  8 (256)   all four depth-sort passes whatever the depth range
+//   bit 10 (1024)  the one-workgroup depth stage of small scenes OFF (small scenes run the multi-kernel chain; N > 8 192)
+//   bit 11 (2048)  plain depth items and the rectangle gather in the last depth pass (four-pass frames, grids over 63 tiles)
+//   bit 12 (4096)  the second tile pass keeps 64-bit items where the first could narrow them (N > 2^24)
+//   bit 13 (8192)  row-major forward dispatch instead of last frame's cost classes (images of more than GSR_FO_MAX_TILES tiles)
+// Bit 9 is retired (it selected an expansion that no size takes) and stays unused.  Bits 0-3 are timing ablations that give
+// WRONG results (skip the atomics, one pixel per bucket, no SH fetch, no stores); they exist only in the separate ablation build
+// (`make ablate` -> libgsr_hip_ablate.so, -DGSR_ABLATE, used by tools/stage_bench.sh) and are compiled out of libgsr_hip.so.
 #ifdef GSR_ABLATE
-#define GSR_DEBUG_ALLOWED (1 | 2 | 4 | 8 | 32 | 64 | 128 | 256 | 512 | 1024)
+#define GSR_DEBUG_ALLOWED (1 | 2 | 4 | 8 | 32 | 64 | 128 | 256 | 1024 | 2048 | 4096 | 8192)
 #define GSR_ABL(flags, bit) (((flags) & (bit)) != 0)
 #else
-#define GSR_DEBUG_ALLOWED (32 | 64 | 128 | 256 | 512 | 1024)
+#define GSR_DEBUG_ALLOWED (32 | 64 | 128 | 256 | 1024 | 2048 | 4096 | 8192)
 #define GSR_ABL(flags, bit) false
 #endif
 extern int gsr_debug_flags;
-extern int gsr_fwd_xcd_map;        // GSR_FWD_XCD: neighbouring tiles of the forward blend on one XCD (blend_fwd.hip)
-extern int gsr_bwd_no_order;
-extern int gsr_bwd_xcd_map;        // GSR_BWD_XCD: a tile's blocks of the backward blend on one XCD (blend_bwd_splat.hip)
-extern int gsr_bwd_block;          // GSR_BWD_BLOCK: pixels per wave in the Gaussian-parallel backward (64, 32, 16); 0 = per frame
+extern int gsr_bwd_block;          // GSR_BWD_BLOCK: pixels per wave in the Gaussian-parallel backward (64 or 32); 0 = per frame
 #define GSR_BWD_WIDE_PAIRS 20         // D / N from which the backward blend takes 8x8 blocks instead of 8x4 ...
 #define GSR_BWD_WIDE_PAIRS_UNFILED 5  // ... and for images of more than GSR_BO_MAX_TILES tiles (no block order for 8x4 there)
 // pixels per backward-blend wave for a frame of N Gaussians, D tile pairs, `tiles` tiles (blend_bwd_splat.hip, the launcher): the

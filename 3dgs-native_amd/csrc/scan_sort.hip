@@ -851,79 +851,7 @@ __global__ __launch_bounds__(1024) void ranges_fixup_kernel(const int32_t *__res
 }
 
 // ---------------------------------------------------------------------------------------------
-// expansion: depth-ordered Gaussians -> (tile << 32 | id) items, row-major tile walk
-// (same walk as reference forward.py:546-548: y outer, x inner)
-// ---------------------------------------------------------------------------------------------
-// Load-balanced: a wave owns 64 consecutive depth-sorted Gaussians, whose output range
-// [doff[k0], doff[k0+64]) is contiguous.  Lanes walk that range 64 items at a time (fully coalesced
-// 8-byte stores) and find each item's owner by a 6-step binary search over the wave's 64 offsets in
-// LDS, so a Gaussian covering thousands of tiles costs no more per item than one covering four.
-// G = Gaussians per wave: 64 when a Gaussian expands to a handful of tiles (C3: 7.75), 8 when it expands to dozens or hundreds
-// (the reference trainer's initial point set: 5 000 Gaussians of scale 0.1 cover 130 tiles each -- at 64 per wave that was 78 waves
-// for 649 k items on a 256-CU chip, 48 us; api.hip picks G from D / N).
-template <typename ItemT, int G>
-__global__ __launch_bounds__(256) void expand_kernel(const uint32_t *__restrict__ id_sorted, const int32_t *__restrict__ doff,
-                                                     const TileRect *__restrict__ rect, ItemT *__restrict__ tile_items, int64_t n,
-                                                     int grid_x, int64_t D, int id_shift, int32_t *__restrict__ ranges, int ranges_n,
-                                                     int32_t *__restrict__ zero_acc, int zero_n, int32_t *__restrict__ zero_b, int zero_b_n, int bo_flag)
-{
-    // the accumulators of the first partition pass (radix_hist_kernel) are cleared here, like the ranges below
-    for (int64_t z = (int64_t)blockIdx.x * 256 + threadIdx.x; z < zero_n; z += (int64_t)gridDim.x * 256) zero_acc[z] = 0;
-    // ... and the counters of the block-order queues the forward blend fills (GsrBinning.block_order)
-    // (and the header's `filed` flag: will the forward blend file them?)
-    for (int64_t z = (int64_t)blockIdx.x * 256 + threadIdx.x; z < zero_b_n; z += (int64_t)gridDim.x * 256) zero_b[z] = (z == GSR_BO_FLAG) ? bo_flag : 0;
-    // also clears the tile ranges (filled later by ranges_kernel; untouched tiles must read (0,0)): saves a memset launch
-    for (int64_t z = (int64_t)blockIdx.x * 256 + threadIdx.x; z < ranges_n; z += (int64_t)gridDim.x * 256) ranges[z] = 0;
-    __shared__ int s_off[4][G];
-    __shared__ TileRect s_rect[4][G];
-    __shared__ uint32_t s_gid[4][G];
-    __shared__ float s_inv[4][G]; // 1 / (rectangle width in tiles)
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const int64_t k0 = ((int64_t)blockIdx.x * 4 + w) * G;
-    const int64_t k = k0 + lane;
-    int off = (int)D;
-    TileRect rc = {0, 0, 0, 0};
-    uint32_t id = 0;
-    // (requested with the wave's other loads: read where it is used, after the barrier, it was a second serial round trip)
-    int next_off = (k0 + G < n) ? doff[k0 + G] : (int)D;
-    asm volatile("" : "+v"(next_off));
-    if (lane < G && k < n) {
-        id = id_sorted[k];
-        off = doff[k];
-        rc = rect[k]; // rectangles arrive in depth order (carried by the last sort pass); culled Gaussians have empty ones
-    }
-    if (lane < G) {
-        s_off[w][lane] = off;
-        s_rect[w][lane] = rc;
-        s_gid[w][lane] = id;
-        s_inv[w][lane] = rc.x1 > rc.x0 ? 1.0f / (float)((int)rc.x1 - (int)rc.x0) : 0.0f;
-    }
-    __syncthreads();
-    if (k0 >= n) return;
-    const int begin = s_off[w][0];
-    // never write past the caller's D, even if it under-reports the count gsr_forward_count returned
-    const int end = min((int)D, next_off);
-    for (int j = begin + lane; j < end; j += 64) {
-        int lo = 0; // last k with off[k] <= j (zero-count Gaussians share their successor's offset)
-#pragma unroll
-        for (int step = G / 2; step >= 1; step >>= 1)
-            if (s_off[w][lo + step] <= j) lo += step;
-        const TileRect r = s_rect[w][lo];
-        const int t = j - s_off[w][lo];
-        const int wd = (int)r.x1 - (int)r.x0;
-        // row-major walk: y = t / wd, x = t % wd (reference forward.py:546-548).  t < 2^24 (a rectangle has at most
-        // 4096 x 4096 tiles), so the quotient comes from one float multiply by the Gaussian's 1/wd and a +-1 correction
-        // instead of the ~25-instruction integer division
-        int y = (int)((float)t * s_inv[w][lo]);
-        int x = t - y * wd;
-        if (x < 0) { --y; x += wd; }
-        else if (x >= wd) { ++y; x -= wd; }
-        tile_items[j] = (ItemT)(((ItemT)(uint32_t)(((int)r.y0 + y) * grid_x + (int)r.x0 + x) << id_shift) | (ItemT)s_gid[w][lo]);
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// expansion, by OUTPUT block (the product path; the kernel above is the alternative path of GSR_DEBUG bit 9)
+// expansion: depth-ordered Gaussians -> (tile << id_shift | id) items, by OUTPUT block
 // ---------------------------------------------------------------------------------------------
 // The depth-order offsets are an exclusive scan of the sorted tile counts.  As a device-wide scan that was two launches
 // (12 us at C3 for 4 MB) whose output, 4 bytes per Gaussian, the expansion read straight back.  Now one small streaming kernel
@@ -970,7 +898,7 @@ __global__ __launch_bounds__(1024) void depth_block_offsets_kernel(const int32_t
 
 // One workgroup per radix block of the OUTPUT: workgroup b writes the items [b * chunk, (b + 1) * chunk) -- whatever Gaussians
 // they belong to -- so (1) the work per workgroup is the same whether a Gaussian covers four tiles or four thousand (the
-// wave-per-64-Gaussians kernel above needed a second shape for the trainer's initial point set), and (2) the workgroup has seen
+// wave-per-64-Gaussians kernel of rounds 1-4 needed a second shape for the trainer's initial point set), and (2) the workgroup has seen
 // exactly one block of the first partition pass and leaves that pass's histogram row and super-block sums behind: the pass's
 // histogram kernel, which re-read all D items, is not launched.  It finds the 256-Gaussian block holding its first item by a
 // two-level search of pre256 (two dependent loads), then walks blocks of 256 Gaussians: rectangle -> count -> offsets by a
@@ -1129,14 +1057,14 @@ __global__ __launch_bounds__(256) void expand_blocks_kernel(const uint32_t *__re
 // Up to GSR_SMALL_SORT_N Gaussians (the reference trainer starts with 5 000): ten launches of 5 us each -- four histogram /
 // scatter pairs and the two-kernel depth-order scan -- to order a few thousand items is all latency.  One 1024-thread workgroup
 // does the same stable LSD radix passes with both item buffers in LDS (8-bit digits of the reduced key, only the passes the
-// depth range needs: the extremes are reduced in the kernel itself), then carries rectangle and count to the sorted position and
-// scans the counts into the depth-order offsets.  (A bitonic network over the items -- they are distinct, so their ascending
-// order as 64-bit integers IS the stable order -- was tried first: 91 barrier-separated LDS sweeps on one CU, 85 us.)
+// depth range needs: the extremes are reduced in the kernel itself), then carries rectangle and count to the sorted position.
+// (A bitonic network over the items -- they are distinct, so their ascending order as 64-bit integers IS the stable order --
+// was tried first: 91 barrier-separated LDS sweeps on one CU, 85 us.)
 constexpr int SMALL_SORT_MAX = GSR_SMALL_SORT_N;
 constexpr int SMALL_ROUNDS = SMALL_SORT_MAX / 1024; // items per thread
 __global__ __launch_bounds__(1024) void depth_sort_small_kernel(const uint64_t *__restrict__ items, int n, const TileRect *__restrict__ rect,
                                                                 uint32_t *__restrict__ id_sorted, TileRect *__restrict__ rect_sorted,
-                                                                int32_t *__restrict__ cnt_sorted, int32_t *__restrict__ doff)
+                                                                int32_t *__restrict__ cnt_sorted)
 {
     __shared__ uint64_t s_buf[2][SMALL_SORT_MAX];
     __shared__ int s_wcnt[16][256]; // per-wave digit counts -> per-wave start offsets within the digit
@@ -1219,34 +1147,19 @@ __global__ __launch_bounds__(1024) void depth_sort_small_kernel(const uint64_t *
         __syncthreads();
         cur ^= 1;
     }
-    // carry + exclusive scan of the tile counts in sorted order: thread t owns the positions [t * per, t * per + per)
+    // carry: thread t owns the sorted positions [t * per, t * per + per)
     const int per = (n + 1023) >> 10;
-    int cnt[SMALL_ROUNDS], sum = 0;
 #pragma unroll
     for (int q = 0; q < SMALL_ROUNDS; ++q) {
         const int pos = tid * per + q;
-        cnt[q] = 0;
         if (q < per && pos < n) {
             const uint32_t id = (uint32_t)s_buf[cur][pos];
             const unsigned long long r = reinterpret_cast<const unsigned long long *>(rect)[id];
             const int x0 = (int)(r & 0xFFFF), y0 = (int)((r >> 16) & 0xFFFF), x1 = (int)((r >> 32) & 0xFFFF), y1 = (int)(r >> 48);
-            cnt[q] = (x1 - x0) * (y1 - y0);
             id_sorted[pos] = id;
             reinterpret_cast<unsigned long long *>(rect_sorted)[pos] = r;
-            cnt_sorted[pos] = cnt[q];
+            cnt_sorted[pos] = (x1 - x0) * (y1 - y0);
         }
-        sum += cnt[q];
-    }
-    const int incl = wave_incl_scan(sum);
-    if (lane == 63) s_wsum[w] = incl;
-    __syncthreads();
-    int base = incl - sum;
-    for (int k = 0; k < w; ++k) base += s_wsum[k];
-#pragma unroll
-    for (int q = 0; q < SMALL_ROUNDS; ++q) {
-        const int pos = tid * per + q;
-        if (q < per && pos < n) doff[pos] = base;
-        base += cnt[q];
     }
 }
 
@@ -1372,9 +1285,6 @@ hipError_t gsr_launch_radix_pass(const void *in, void *out, int32_t *hist, int32
     return radix_pass_any<uint64_t, false>((const uint64_t *)in, (uint64_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready);
 }
 
-int gsr_no_narrowing = 0; // GSR_NO_NARROWING (gsr_internal.h)
-int gsr_no_depth_pack = 0; // GSR_NO_DEPTH_PACK (gsr_internal.h)
-
 // The LAST pass of the tile partition: histogram, then a scatter that writes point_list and the in-sight range boundaries
 // directly (ScatterFinal), and the edge fix-up.  `edge` holds 3 * (1 << bits) * nb int32 (gsr_radix_blocks(n) = nb).
 hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
@@ -1416,9 +1326,9 @@ hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, hipStream_t s, int
 {
     if (n <= 0) return hipSuccess;
     launch_passes = std::min(4, std::max(1, launch_passes));
-    if (gsr_small_depth_path(n)) { // sorts, carries AND scans: the caller skips the depth-order scan
+    if (gsr_small_depth_path(n)) { // sorts and carries in one workgroup
         hipLaunchKernelGGL(depth_sort_small_kernel, dim3(1), dim3(1024), 0, s, ws.depth_item, (int)n, ws.rect, ws.id_sorted, ws.rect_sorted,
-                           ws.cnt_sorted, ws.doff);
+                           ws.cnt_sorted);
         return hipGetLastError();
     }
     const int zero_n = (int)gsr_radix_acc_ints(n);
@@ -1442,22 +1352,7 @@ hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, hipStream_t s, int
     return hipGetLastError();
 }
 
-hipError_t gsr_launch_expand(const uint32_t *id_sorted, const int32_t *doff, const TileRect *rect, void *tile_items, int64_t n,
-                             int grid_x, int64_t D, int id_shift, int item_bytes, int32_t *ranges, int ranges_n, int32_t *zero_acc, int zero_n,
-                             int32_t *zero_b, int zero_b_n, int bo_flag, hipStream_t s)
-{
-    if (n <= 0 || D <= 0) return hipSuccess;
-    const bool few = D / n >= 32;
-#define EXPAND(T, G)                                                                                                          \
-    hipLaunchKernelGGL((expand_kernel<T, G>), dim3((unsigned)gsr_div_up(n, 4 * (G))), dim3(256), 0, s, id_sorted, doff, rect, (T *)tile_items, n, grid_x, D, \
-                       id_shift, ranges, ranges_n, zero_acc, zero_n, zero_b, zero_b_n, bo_flag)
-    if (item_bytes == 4) { if (few) EXPAND(uint32_t, 8); else EXPAND(uint32_t, 64); }
-    else { if (few) EXPAND(uint64_t, 8); else EXPAND(uint64_t, 64); }
-#undef EXPAND
-    return hipGetLastError();
-}
-
-// The product path of the expansion: gsr_launch_depth_block_offsets, then gsr_launch_expand_blocks (see the kernels).
+// The expansion: gsr_launch_depth_block_offsets, then gsr_launch_expand_blocks (see the kernels).
 hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *ranges, int ranges_n, int32_t *zero_acc, int zero_n, int32_t *zero_b,
                                           int zero_b_n, int bo_flag, hipStream_t s)
 {

@@ -19,10 +19,8 @@ from .config import TILE_M, TILE_N
 # process never pays for it); the first training step's backward clears for itself.
 PRECLEAR_BACKWARD = not bool(int(os.environ.get("GSR_NO_PRECLEAR", "0")))
 _backward_seen = False          # set by backward.backward()
-_NO_SH_DIR = bool(int(os.environ.get("GSR_NO_SH_DIR", "0")))
-_NO_RECORD_VIEWS = bool(int(os.environ.get("GSR_NO_RECORD_VIEWS", "0")))
+_NO_RECORD_VIEWS = bool(int(os.environ.get("GSR_NO_RECORD_VIEWS", "0")))    # A/B switch: packed xy / conic_opacity / colors arrays beside the records
 _NO_COV_RECOMPUTE = bool(int(os.environ.get("GSR_NO_COV_RECOMPUTE", "0")))   # A/B switch: backward() always reads cov3Ds back
-_NO_BLOCK_ORDER = bool(int(os.environ.get("GSR_NO_BLOCK_ORDER", "0")))     # A/B switch: the forward does not file the backward's blocks by cost   # A/B switch: packed xy / conic_opacity / colors arrays beside the records   # A/B switch: backward reads the SH rows itself (same results)
 
 
 def render_gaussians(background, means3D, colors=None, opacity=None, scales=None, rotations=None, scale_modifier=1.0,
@@ -63,7 +61,7 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
     # Only worth its 36 bytes per Gaussian when the caller's SH / position tensors can be recognised again by backward(), i.e.
     # when they are device tensors used in place.
     in_place = lambda given, used: isinstance(given, torch.Tensor) and given.is_cuda and given.data_ptr() == used.data_ptr()
-    sh_dir = e((N, 9), f32) if (N > 0 and in_place(sh, shs) and in_place(means3D, means) and not _NO_SH_DIR) else None
+    sh_dir = e((N, 9), f32) if (N > 0 and in_place(sh, shs) and in_place(means3D, means)) else None
     arr = (lambda t: _host.ptr(t)) if _NO_RECORD_VIEWS else (lambda t: None)
     geom = _lib.GsrGeom(_host.ptr(radii), _host.ptr(tiles_touched), _host.ptr(point_offsets), arr(xy), _host.ptr(depths),
                         _host.ptr(cov3Ds), arr(rgb), arr(conic_opacity), _host.ptr(clamped_state), _host.ptr(records), _host.ptr(sh_dir))
@@ -86,7 +84,7 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
         # backward reads them 16 at a time)
         block_masks = e((D + 16,), torch.uint8)[:D]
         # the backward blend's blocks filed by cost, heaviest first (GsrBinning.block_order): filled by the forward blend from the masks
-        block_order = None if _NO_BLOCK_ORDER else e((int(L.gsr_block_order_ints(W, H)),), i32)
+        block_order = e((int(L.gsr_block_order_ints(W, H)),), i32)
         # The backward's workspace, one per call: its accumulator records are what backward() returns dL_dcolor / dL_dmean2D /
         # dL_dconic as views of, so it must not be shared between calls.  Handed to the forward, its records are cleared by the
         # blend kernel's spare workgroups.

@@ -2,15 +2,16 @@
 # usage (GPU box, repo root): bash tools/ab_median.sh REPS "ENV=..." ["ENV=..." ...]
 # Alternates environment settings of the one product library; no stage events (kernels back to back, as in production); prints
 # ms_per_step and the step_ms median / p10 per run and the minimum and median over runs per setting.  Extra bench flags: AB_ARGS.
+set -o pipefail   # a failed bench run fails its line, and the first failure ends the script
 reps=${1:-5}; shift 1
 for i in $(seq $reps); do
   for e in "$@"; do
     env $e timeout -k 10 200 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-stage-events $AB_ARGS 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
-print('$e', d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10'])" || echo "$e FAILED"
+print('$e', d['ms_per_step'], d['step_ms']['median'], d['step_ms']['p10'])" || { echo "$e FAILED (status $?): no further runs" >&2; exit 1; }
   done
-done | tee /tmp/abm_runs.txt
+done | tee /tmp/abm_runs.txt || exit 1
 python - <<'PY'
 from collections import defaultdict
 import statistics

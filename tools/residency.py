@@ -120,7 +120,7 @@ if "--lpt" in sys.argv:
         print(f"   {label:60s} span us: " + " ".join(f"{x:.1f}" for x in spans))
         assert L.gsr_debug_bwd_order(C.c_void_p(0)) == 0
 
-    print("== backward blend, dispatch-order experiment (GSR_BWD_XCD as set in the environment applies only to the first line)")
+    print("== backward blend, dispatch-order experiment (the first line is the shipped dispatch: filed blocks, else the XCD bands)")
     timed(None, "as shipped")
     ident = np.arange(nblk)
     timed(ident, "identity table (cost of the indirection)")
@@ -135,7 +135,7 @@ if "--lpt" in sys.argv:
     tab2 = np.empty(nblk, np.int64)
     for x in range(8):
         tab2[x::8] = np.arange(x * per, (x + 1) * per)
-    timed(tab2, "bands, natural order (= GSR_BWD_XCD=1 through the table)")
+    timed(tab2, "bands, natural order (= the shipped unfiled dispatch, through the table)")
     # staggered starts: the first round of a band (1024 wave slots per XCD) ends all at once when it is uniformly heavy (a dip to 22
     # of 32 resident waves per CU at 40 % of the span): every second / fourth slot of the first round takes a LIGHT block instead
     for every in (2, 4):
@@ -247,8 +247,8 @@ if "--fwd-order" in sys.argv:
     gx = (W + 15) // 16
     gy = tiles // gx
     timed_fwd(np.concatenate([np.arange(r, gy, 8) for r in range(8)])[:, None].repeat(gx, 1).__mul__(gx).__add__(np.arange(gx)[None, :]).reshape(-1), "tile rows interleaved by 8 (row r, r + 8, ...)")
-    # what the entry-count predictors would see (4 ints per tile: walked << 16 | staged): needs a census build made with
-    # EXTRA=-DGSR_FWD_COST_LIFE=0 -- the product's waves leave their measured life in the `walked` field since late round 4
+    # what the entry-count predictors would see (4 ints per tile: walked << 16 | staged) -- the encoding of rounds up to late round 4,
+    # gone from the library since; the product's waves leave their measured life in the `walked` field and 0 in `staged`
     host = importlib.import_module("3dgs-native_amd._host")
     ws = [t for (kind, _, _), t in host._ws.items() if kind == "bin"][0]
     raw = ws[:16 * tiles].view(torch.int32).cpu().numpy().reshape(tiles, 4)
