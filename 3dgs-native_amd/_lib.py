@@ -8,6 +8,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSR_LIB", os.path.join(_HERE, "libgsr_hip.so"))   # GSR_LIB: A/B runs of two builds on one box
 
+MAX_RENDERED = 1 << 30      # GSR_MAX_RENDERED
 GSR_OK, GSR_E_NULL, GSR_E_DIMS, GSR_E_OVERFLOW, GSR_E_WORKSPACE, GSR_E_HIP, GSR_E_CAPACITY, GSR_E_ALIGN = 0, -1, -2, -3, -4, -5, -6, -7
 
 vp = C.c_void_p
@@ -98,6 +99,12 @@ EXPORTS = {
     "gsr_stage_times": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_int)]),
 }
 
+# include/gsr_capacity.h: the capacity-mode forward (its own header, so its own table)
+CAPACITY_EXPORTS = {
+    "gsr_forward_capacity": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                       C.POINTER(GsrImage), vp, C.c_size_t, vp, C.c_size_t, C.c_int64, vp]),
+}
+
 STAGES = ["preprocess", "scan", "depth_sort", "host_gap", "depth_scan", "expand", "tile_sort", "ranges", "blend_fwd",
           "bwd_prep", "blend_bwd", "geom_bwd"]
 
@@ -112,7 +119,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(hipcc --offload-arch=gfx950).  There is no fallback path.")
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in EXPORTS.items():
+        for name, (res, args) in list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

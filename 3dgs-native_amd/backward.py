@@ -89,6 +89,9 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     # conic_opacity or another run's ranges / n_contrib gets the self-contained block test instead.
     masks, order = None, None
     cleared_tag = getattr(point_list, "_gsr_cleared_ws", None)     # "the forward cleared the backward workspace's accumulators"
+    # a capacity-mode point_list (forward.py): K entries, the first D valid; GsrBinning.D is then the forward's shape hint
+    # (include/gsr_capacity.h), so both sides pick the same blend block shape
+    cap_tag = getattr(point_list, "_gsr_capacity", None)
     mask_tag = getattr(point_list, "_gsr_block_masks", None)
     if mask_tag is not None:
         m_t, owners, o_t = mask_tag
@@ -134,6 +137,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     n_contrib = _host.to_dev(n_contrib, i32, dev, (H, W))
     point_list = _host.to_dev(point_list, i32, dev, (-1,))
     D = point_list.shape[0]
+    D_bin = D if cap_tag is None else cap_tag[1]
 
     scene = _lib.GsrScene(N, _host.ptr(means), _host.ptr(sc), _host.ptr(rot), _host.ptr(op), _host.ptr(sh), int(degree),
                           float(scale_modifier), 1)
@@ -186,7 +190,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
             packed = _host.ptr
         grads = _lib.GsrGrads(_host.ptr(dL_dmean3D), _host.ptr(dL_dscale), _host.ptr(dL_drot), _host.ptr(dL_dopacity),
                               _host.ptr(dL_dsh), packed(dL_dcolor), packed(dL_dmean2D), packed(dL_dconic), _host.ptr(payload))
-        binning = _lib.GsrBinning(D, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(masks), _host.ptr(order),
+        binning = _lib.GsrBinning(D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(masks), _host.ptr(order),
                                   _host.ptr(ws) if cleared else None, 1 if cleared else 0)
         backward.last_call_skipped_the_clear = cleared     # for tests and debugging
         if on_payload is not None and payload is not None:

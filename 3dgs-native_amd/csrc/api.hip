@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "gsr_capacity.h"
 #include "gsr_internal.h"
 
 namespace {
@@ -411,47 +412,37 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     return GSR_OK;
 }
 
-int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
-                       const GsrImage *image, void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, void *stream)
-{
-    read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (!binning || !image || !image->image || !image->inv_depth || !image->final_T || !image->n_contrib || !binning->ranges)
-        return GSR_E_NULL;
-    const int64_t N = scene->N, D = binning->D;
-    if (D < 0 || D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
-    hipStream_t s = (hipStream_t)stream;
-    const CamK cam = make_cam(camera);
-    const size_t P = (size_t)cam.W * cam.H;
-    const int tiles = cam.grid_x * cam.grid_y;
-    if (D == 0 || N == 0) { // reference skips the blend: zeros, not background (forward.py:830, quirk Q10)
-        t_fwd_record = -1;  // a sampled record that ends here stays incomplete and is dropped by gsr_stage_times
-        HIP_TRY(hipMemsetAsync(binning->ranges, 0, sizeof(int32_t) * 2 * tiles, s));
-        HIP_TRY(hipMemsetAsync(image->image, 0, P * 3 * sizeof(float), s));
-        HIP_TRY(hipMemsetAsync(image->inv_depth, 0, P * sizeof(float), s));
-        HIP_TRY(hipMemsetAsync(image->final_T, 0, P * sizeof(float), s));
-        HIP_TRY(hipMemsetAsync(image->n_contrib, 0, P * sizeof(int32_t), s));
-        // the accumulator clear of GsrBinning.backward_ws is promised whenever the workspace is handed over, blend or no blend
-        if (binning->backward_ws && N > 0) {
-            if (!gsr_aligned16(binning->backward_ws)) return GSR_E_ALIGN;
-            HIP_TRY(hipMemsetAsync(carve_bwd(binning->backward_ws, N).acc, 0, sizeof(GradRec) * (size_t)N, s));
-        }
-        return GSR_OK;
-    }
-    if (!geom_ok(geom) || !binning->point_list) return GSR_E_NULL;
-    if (!geom_aligned(geom) || !gsr_aligned16(geom_ws) || !gsr_aligned16(bin_ws) || !gsr_aligned16(binning->point_list) ||
-        !gsr_aligned16(binning->ranges) || !gsr_aligned16(binning->block_order) || !gsr_aligned16(image->image) || !gsr_aligned16(image->inv_depth) ||
-        !gsr_aligned16(image->final_T) || !gsr_aligned16(image->n_contrib))
-        return GSR_E_ALIGN;
-    if (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N)) return GSR_E_WORKSPACE;
-    if (!bin_ws || bin_ws_bytes < gsr_binning_workspace_bytes(N, D, cam.W, cam.H)) return GSR_E_WORKSPACE;
-    // D must be the count gsr_forward_count returned for the items now in geom_ws (see CountNote above)
-    if (check_count(geom_ws, N, D) != 1) return GSR_E_CAPACITY;
-    const GeomWs gw = gsr_carve_geom(geom_ws, N);
-    const BinWs bw = carve_bin(bin_ws, N, D);
+} // extern "C"
 
-    const int st = t_fwd_record;
-    t_fwd_record = -1;
+namespace {
+
+// what gsr_forward_render enqueues for a frame without pairs: zeros, not background (quirk Q10), and the promised clear of the
+// backward workspace's accumulators
+int empty_frame(const GsrBinning *binning, const GsrImage *image, int64_t N, int tiles, size_t P, hipStream_t s)
+{
+    HIP_TRY(hipMemsetAsync(binning->ranges, 0, sizeof(int32_t) * 2 * tiles, s));
+    HIP_TRY(hipMemsetAsync(image->image, 0, P * 3 * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(image->inv_depth, 0, P * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(image->final_T, 0, P * sizeof(float), s));
+    HIP_TRY(hipMemsetAsync(image->n_contrib, 0, P * sizeof(int32_t), s));
+    // the accumulator clear of GsrBinning.backward_ws is promised whenever the workspace is handed over, blend or no blend
+    if (binning->backward_ws && N > 0) {
+        if (!gsr_aligned16(binning->backward_ws)) return GSR_E_ALIGN;
+        HIP_TRY(hipMemsetAsync(carve_bwd(binning->backward_ws, N).acc, 0, sizeof(GradRec) * (size_t)N, s));
+    }
+    return GSR_OK;
+}
+
+// The D-dependent half of the forward: expansion, tile partition, blend.  Sized path: d_count = NULL and D is the count
+// gsr_forward_count returned.  Capacity mode (gsr_forward_capacity): D is the capacity K, which sizes every launch and every
+// buffer, the kernels read the real count at d_count, and `shape_D` (the caller's hint) stands in for the count in the one
+// choice the host still makes from it, the block filing for the backward's 8x4 blocks.
+int enqueue_render(const GsrScene *scene, const CamK &cam, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                   const GeomWs &gw, const BinWs &bw, const int32_t *d_count, int64_t shape_D, hipStream_t s, int st)
+{
+    const int64_t N = scene->N, D = binning->D;
+    const int tiles = cam.grid_x * cam.grid_y;
+    if (!d_count) shape_D = D;
     mark(st, 4, s); // (stage 3 -> 4: the host between the two calls -- the wait for D, the caller's allocations)
     // 3. expansion of the depth-sorted Gaussians (gsr_forward_count) to (tile << id_shift | id) items.  When the tile
     //    bits and the id bits fit one 32-bit word (800x800 with 1M Gaussians: 12 + 20) the items are uint32, which
@@ -467,7 +458,7 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
     // the block order (forward -> backward scratch): header cleared here; filed by the blend below unless the image is large
     int32_t *order = binning->block_masks ? binning->block_order : nullptr;
     // (and not for a frame whose backward will take 8x8 blocks, which run in band order: the `filed` flag then stays 0)
-    const bool file_order = order && tiles <= GSR_BO_MAX_TILES && gsr_bwd_block_px(N, D, tiles) == 32;
+    const bool file_order = order && tiles <= GSR_BO_MAX_TILES && gsr_bwd_block_px(N, shape_D, tiles) == 32;
     // the forward blend's tiles by last frame's cost classes (gsr_internal.h "forward tile order"): the table was made by the spare
     // workgroup of this frame's preprocess (gsr_forward_count, same condition), so it is never stale or foreign
     const bool use_fwd_order = fwd_order_wanted(tiles);
@@ -476,7 +467,7 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
     HIP_TRY(gsr_launch_depth_block_offsets(gw, N, binning->ranges, 2 * tiles, bw.acc[0], (int)gsr_radix_acc_ints(D), order, order ? GSR_BO_HEADER : 0,
                                            file_order ? 1 : 0, s));
     mark(st, 5, s);
-    HIP_TRY(gsr_launch_expand_blocks(gw, bw.tile_a, N, cam.grid_x, D, id_shift, item_bytes, pass_bits(0, 0), bw.hist, bw.acc[0], s));
+    HIP_TRY(gsr_launch_expand_blocks(gw, bw.tile_a, N, cam.grid_x, D, id_shift, item_bytes, pass_bits(0, 0), bw.hist, bw.acc[0], s, d_count));
     mark(st, 6, s);
     // 4. stable partition by tile id
     void *tsrc = bw.tile_a, *tdst = bw.tile_b;
@@ -490,15 +481,15 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
         const bool hist_ready = pass == 0;
         if (pass + 1 < npass) {
             HIP_TRY(gsr_launch_radix_pass(tsrc, tdst, bw.hist, bw.acc[pass & 1], D, id_shift + shift, bits, item_bytes, bw.acc[(pass + 1) & 1], s, hist_ready,
-                                          narrowing ? id_bits : 0, narrowing ? bw.acc[pass & 1] : nullptr));
+                                          narrowing ? id_bits : 0, narrowing ? bw.acc[pass & 1] : nullptr, d_count));
         } else if (narrowing) {
             HIP_TRY(gsr_launch_radix_final_pass(tsrc, bw.hist, bw.acc[pass & 1], D, id_bits, bits, 4, id_bits, binning->point_list, binning->ranges, bw.edge, s,
-                                                false, bw.acc[(pass + 1) & 1], bits0));
+                                                false, bw.acc[(pass + 1) & 1], bits0, d_count));
         } else {
             // 5. the last pass writes point_list and the tile ranges itself (reference forward.py:806-824, :561-586) instead of
             //    sorted items that a further kernel would re-read
             HIP_TRY(gsr_launch_radix_final_pass(tsrc, bw.hist, bw.acc[pass & 1], D, id_shift + shift, bits, item_bytes, id_shift, binning->point_list,
-                                                binning->ranges, bw.edge, s, hist_ready));
+                                                binning->ranges, bw.edge, s, hist_ready, nullptr, 0, d_count));
         }
         shift += bits;
         void *t = tsrc; tsrc = tdst; tdst = t;
@@ -516,9 +507,86 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
         clear_bytes = sizeof(GradRec) * (size_t)N;
     }
     HIP_TRY(gsr_launch_blend_forward(cam, binning->ranges, binning->point_list, geom->blend_records ? (const BlendRec *)geom->blend_records : gw.rec, *image, binning->block_masks, file_order ? order : nullptr,
-                                     clear, clear_bytes, s, use_fwd_order ? gw.fwd_order : nullptr, tiles <= GSR_FO_MAX_TILES ? gw.fwd_cost : nullptr));
+                                     clear, clear_bytes, s, use_fwd_order ? gw.fwd_order : nullptr, tiles <= GSR_FO_MAX_TILES ? gw.fwd_cost : nullptr,
+                                     d_count, D));
     mark(st, 9, s);
     return GSR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
+                       const GsrImage *image, void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, void *stream)
+{
+    read_tuning();
+    if (int rc = check_scene_cam(scene, camera)) return rc;
+    if (!binning || !image || !image->image || !image->inv_depth || !image->final_T || !image->n_contrib || !binning->ranges)
+        return GSR_E_NULL;
+    const int64_t N = scene->N, D = binning->D;
+    if (D < 0 || D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
+    hipStream_t s = (hipStream_t)stream;
+    const CamK cam = make_cam(camera);
+    const size_t P = (size_t)cam.W * cam.H;
+    const int tiles = cam.grid_x * cam.grid_y;
+    if (D == 0 || N == 0) { // reference skips the blend: zeros, not background (forward.py:830, quirk Q10)
+        t_fwd_record = -1;  // a sampled record that ends here stays incomplete and is dropped by gsr_stage_times
+        return empty_frame(binning, image, N, tiles, P, s);
+    }
+    if (!geom_ok(geom) || !binning->point_list) return GSR_E_NULL;
+    if (!geom_aligned(geom) || !gsr_aligned16(geom_ws) || !gsr_aligned16(bin_ws) || !gsr_aligned16(binning->point_list) ||
+        !gsr_aligned16(binning->ranges) || !gsr_aligned16(binning->block_order) || !gsr_aligned16(image->image) || !gsr_aligned16(image->inv_depth) ||
+        !gsr_aligned16(image->final_T) || !gsr_aligned16(image->n_contrib))
+        return GSR_E_ALIGN;
+    if (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N)) return GSR_E_WORKSPACE;
+    if (!bin_ws || bin_ws_bytes < gsr_binning_workspace_bytes(N, D, cam.W, cam.H)) return GSR_E_WORKSPACE;
+    // D must be the count gsr_forward_count returned for the items now in geom_ws (see CountNote above)
+    if (check_count(geom_ws, N, D) != 1) return GSR_E_CAPACITY;
+    const int st = t_fwd_record;
+    t_fwd_record = -1;
+    return enqueue_render(scene, cam, geom, binning, image, gsr_carve_geom(geom_ws, N), carve_bin(bin_ws, N, D), nullptr, D, s, st);
+}
+
+int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                         void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, int64_t shape_hint, void *stream)
+{
+    read_tuning();
+    // every argument is checked before anything is enqueued (include/gsr_capacity.h)
+    if (int rc = check_scene_cam(scene, camera)) return rc;
+    if (!binning || !image || !image->image || !image->inv_depth || !image->final_T || !image->n_contrib || !binning->ranges)
+        return GSR_E_NULL;
+    const int64_t N = scene->N, K = binning->D;
+    if (K < 0 || K > GSR_MAX_RENDERED || shape_hint < 0 || shape_hint > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
+    if (K > 0 && !binning->point_list) return GSR_E_NULL;
+    if (N > 0 && !geom_ok(geom)) return GSR_E_NULL;
+    if ((geom && !geom_aligned(geom)) || !gsr_aligned16(geom_ws) || !gsr_aligned16(bin_ws) || !gsr_aligned16(binning->point_list) ||
+        !gsr_aligned16(binning->ranges) || !gsr_aligned16(binning->block_masks) || !gsr_aligned16(binning->block_order) ||
+        !gsr_aligned16(binning->backward_ws) || !gsr_aligned16(image->image) || !gsr_aligned16(image->inv_depth) || !gsr_aligned16(image->final_T) ||
+        !gsr_aligned16(image->n_contrib))
+        return GSR_E_ALIGN;
+    const CamK cam = make_cam(camera);
+    if (N > 0 && (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N))) return GSR_E_WORKSPACE;
+    if (N > 0 && (!bin_ws || bin_ws_bytes < gsr_binning_workspace_bytes(N, K, cam.W, cam.H))) return GSR_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int tiles = cam.grid_x * cam.grid_y;
+    if (N == 0) return empty_frame(binning, image, N, tiles, (size_t)cam.W * cam.H, s);
+    const GeomWs gw = gsr_carve_geom(geom_ws, N);
+    const int st = timer_open(true);
+    mark(st, 0, s);
+    HIP_TRY(gsr_launch_preprocess(*scene, cam, *geom, gw, s, fwd_order_wanted(tiles)));
+    mark(st, 1, s);
+    // the same scan as gsr_forward_count, minus the pinned host words: D stays in point_offsets[N-1], where every D-dependent
+    // kernel below reads it
+    if (gsr_small_depth_path(N)) HIP_TRY(gsr_launch_scan(geom->tiles_touched, nullptr, geom->point_offsets, gw.scan_tmp, N, 0, nullptr, true, s, gw.blk_minmax, gw.depth_ctl));
+    else HIP_TRY(gsr_launch_scan_ctl_hist(geom->tiles_touched, geom->point_offsets, gw, N, nullptr, s));
+    mark(st, 2, s);
+    // All four depth passes: with no readback there is no guess to check, and the device plan (DepthCtl) makes the passes this
+    // frame does not need return at once -- one or two launches of early-exit workgroups, a few microseconds of GPU time.
+    const int pack_ok = (!(gsr_debug_flags & 2048) && cam.grid_x <= 63 && cam.grid_y <= 63 && N <= (1 << 24)) ? 1 : 0;
+    HIP_TRY(gsr_launch_depth_sort(gw, N, s, 4, pack_ok));
+    mark(st, 3, s);
+    return enqueue_render(scene, cam, geom, binning, image, gw, carve_bin(bin_ws, N, K), geom->point_offsets + (N - 1), shape_hint, s, st);
 }
 
 // first half: accumulator clear, record (re)pack, blend backward, optional view payload

@@ -369,6 +369,25 @@ __global__ __launch_bounds__(256) void blend_forward_kernel(int W, int H, int gr
     TL_FLUSH
 }
 
+// Capacity mode (gsr_internal.h): the host no longer knows D, so a frame whose list is empty on the device -- min(D, K) == 0 --
+// is decided here, behind the blend: it gives what gsr_forward_render gives for D == 0, zeros instead of background (quirk Q10).
+// (The blend kernel's spare workgroups have cleared the backward accumulators either way.)  On every other frame each workgroup
+// reads one word and leaves.
+__global__ __launch_bounds__(256) void empty_frame_cap_kernel(const int32_t *__restrict__ d_count, long long capacity, float *__restrict__ image,
+                                                              float *__restrict__ inv_depth, float *__restrict__ final_T, int32_t *__restrict__ n_contrib,
+                                                              long long P)
+{
+    if (gsr_capped_count(d_count, capacity) != 0) return;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256) {
+        final_T[i] = 0.0f;
+        n_contrib[i] = 0;
+        inv_depth[i] = 0.0f;
+        image[3 * i] = 0.0f;
+        image[3 * i + 1] = 0.0f;
+        image[3 * i + 2] = 0.0f;
+    }
+}
+
 } // namespace
 
 #ifdef GSR_CENSUS
@@ -397,7 +416,7 @@ extern "C" int gsr_debug_fwd_phases(unsigned long long *out /* [waves][8] */, in
 
 hipError_t gsr_launch_blend_forward(const CamK &cam, const int32_t *ranges, const int32_t *point_list, const BlendRec *rec,
                                     const GsrImage &img, uint8_t *block_masks, int32_t *block_order, void *clear, size_t clear_bytes,
-                                    hipStream_t s, const int32_t *tile_order, int32_t *tile_cost)
+                                    hipStream_t s, const int32_t *tile_order, int32_t *tile_cost, const int32_t *d_count, int64_t capacity)
 {
     const int tiles = cam.grid_x * cam.grid_y;
     if (tiles <= 0) return hipSuccess;
@@ -409,5 +428,10 @@ hipError_t gsr_launch_blend_forward(const CamK &cam, const int32_t *ranges, cons
                        ranges, point_list, rec, img.image, img.inv_depth, img.final_T, img.n_contrib, block_masks, tiles,
                        block_masks ? block_order : nullptr, gsr_bo_cap(tiles), reinterpret_cast<float4 *>(clear), clear_n4, clear_wgs,
                        tile_order, tile_cost);
+    if (d_count) {
+        const long long P = (long long)cam.W * cam.H;
+        hipLaunchKernelGGL(empty_frame_cap_kernel, dim3((unsigned)std::min<long long>(512, (P + 255) / 256)), dim3(256), 0, s, d_count, (long long)capacity,
+                           img.image, img.inv_depth, img.final_T, img.n_contrib, P);
+    }
     return hipGetLastError();
 }

@@ -96,6 +96,18 @@ hipError_t gsr_launch_scan_ctl_hist(const int32_t *tiles_touched, int32_t *point
 #define GSR_SMALL_SORT_N 8192          // up to this many Gaussians one workgroup sorts, carries and scans (scan_sort.hip)
 bool gsr_small_depth_path(int64_t n); // true: gsr_launch_depth_sort sorts in one workgroup
 
+// ---- capacity mode (include/gsr_capacity.h) ----
+// The D-dependent launches of the forward are sized from the caller's capacity K instead of the count the host read back: the
+// launcher's item count is K, and `d_count` points at the frame's real count on the device (point_offsets[N-1], the id-order
+// scan's last element).  Each kernel works on min(D, K) items, read when it starts; workgroups past that do the clearing they owe
+// (accumulators, empty histogram rows, empty edge-table runs) and return.  A NULL d_count is the sized path, whose kernels are
+// not changed by any of this (the capacity kernels are separate instantiations of the same bodies).
+__device__ __forceinline__ int64_t gsr_capped_count(const int32_t *d_count, int64_t cap)
+{
+    const int64_t d = (int64_t)*d_count; // a 32-bit scan: a negative value is a wrapped count, i.e. an overflow: no items
+    return d < 0 ? 0 : d < cap ? d : cap;
+}
+
 // One stable LSD radix pass by the `bits`-wide (4..8) digit at `shift`; items are uint64 (item_bytes 8) or uint32 (4).
 #ifndef GSR_RADIX_CHUNK
 #define GSR_RADIX_CHUNK 4096
@@ -142,14 +154,15 @@ hipError_t gsr_launch_radix_pass(const void *in, void *out, int32_t *hist /*[nb]
                                  int64_t n, int shift, int bits, int item_bytes, int32_t *zero_acc /* next pass's, or NULL */, hipStream_t s,
                                  bool hist_ready = false /* hist and acc were filled by gsr_launch_expand_blocks */,
                                  int narrow_id_bits = 0 /* 64-bit items only: > 0 = write 32-bit items (tile >> bits) << narrow_id_bits | id ... */,
-                                 int32_t *totals_out = nullptr /* ... and leave the digit totals here for the final pass (scan_sort.hip ScatterFinal) */);
+                                 int32_t *totals_out = nullptr /* ... and leave the digit totals here for the final pass (scan_sort.hip ScatterFinal) */,
+                                 const int32_t *d_count = nullptr /* capacity mode (below): n is the capacity K */);
 
 // Last pass of the tile partition: writes point_list and ranges instead of the sorted items (scan_sort.hip, ScatterFinal).
 // `edge`: 3 * 256 * (gsr_radix_blocks(n) + 1) int32 of scratch.
 hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
                                        int id_shift, int32_t *point_list, int32_t *ranges /* pre-zeroed */, int32_t *edge, hipStream_t s,
                                        bool hist_ready = false, const int32_t *low_totals = nullptr /* narrowed items: the first pass's digit totals */,
-                                       int low_bits = 0 /* ... and digit width */);
+                                       int low_bits = 0 /* ... and digit width */, const int32_t *d_count = nullptr /* capacity mode: n is K */);
 
 // Tile items are (tile << id_shift | gaussian id): uint64 with id_shift = 32, or uint32 when tile bits + id bits <= 32.
 // The expansion (scan_sort.hip): one prefix per 256 depth-sorted Gaussians (into ws.scan_tmp; also clears the
@@ -170,7 +183,7 @@ hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *a
 hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *ranges, int ranges_n, int32_t *zero_acc, int zero_n, int32_t *zero_b,
                                           int zero_b_n, int bo_flag, hipStream_t s);
 hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t n, int grid_x, int64_t D, int id_shift, int item_bytes, int bits0,
-                                    int32_t *hist, int32_t *acc, hipStream_t s);
+                                    int32_t *hist, int32_t *acc, hipStream_t s, const int32_t *d_count = nullptr /* capacity mode: D is K */);
 // ---- block order (GsrBinning.block_order): the backward blend's 8x4-pixel blocks, heaviest first ---------------------------
 // The backward's waves live 40-90 us of a 165-us kernel, so what starts last decides when the kernel ends.  How many list
 // entries the backward's compaction will keep for a block (mask hits up to the block's last contributor) is the one cheap
@@ -215,7 +228,9 @@ hipError_t gsr_launch_blend_forward(const CamK &cam, const int32_t *ranges, cons
                                     const BlendRec *rec, const GsrImage &img, uint8_t *block_masks /* optional out */,
                                     int32_t *block_order /* optional out, with block_masks */,
                                     void *clear, size_t clear_bytes /* optional: memory its spare workgroups zero (16-byte units) */, hipStream_t s,
-                                    const int32_t *tile_order = nullptr /* optional: launch slot -> tile */, int32_t *tile_cost = nullptr /* optional out: 4 per tile */);
+                                    const int32_t *tile_order = nullptr /* optional: launch slot -> tile */, int32_t *tile_cost = nullptr /* optional out: 4 per tile */,
+                                    const int32_t *d_count = nullptr /* capacity mode: a frame with no pairs then gives zeros, as gsr_forward_render's D == 0 */,
+                                    int64_t capacity = 0);
 
 // backward
 struct __attribute__((aligned(16))) GradRec { // 64 B accumulator per Gaussian (atomics target)

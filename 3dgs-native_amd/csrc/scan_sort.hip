@@ -264,7 +264,10 @@ __global__ __launch_bounds__(256) void scan_final_kernel(const int32_t *__restri
 // (DepthCtl above), which pass this is decides the digit and which of the two ping-pong buffers is the input, and a pass the
 // frame does not need returns at once -- all read from device memory, so the host launches the same four passes every frame.
 struct DepthPass {
-    const DepthCtlRaw *ctl;
+    union {
+        const DepthCtlRaw *ctl;
+        const int32_t *count; // capacity-mode tile passes (radix_scatter_kernel CAP, never DEPTH): the frame's pair count D on the device
+    };
     int force_npass;     // GSR_DEBUG bit 8 (tests): four passes whatever the range
     int pass;            // 0 .. 3
     uint64_t *buf[2];    // ping-pong buffers; the first ACTIVE pass reads buf[0]
@@ -367,6 +370,14 @@ __global__ __launch_bounds__(256) void radix_hist_kernel(const ItemT *__restrict
         if ((int64_t)blockIdx.x * CHUNK >= n) return;
     }
     radix_hist_block<RADIX_ITEMS, BITS, ItemT, DEPTH>(in, hist, acc, n, shift, sb, (int)blockIdx.x, kmin, krange, false);
+}
+// capacity mode (gsr_internal.h): n is the capacity K, the items are the first min(*d_count, K); a block past them counts nothing
+// and leaves an empty histogram row
+template <int RADIX_ITEMS, int BITS, typename ItemT>
+__global__ __launch_bounds__(256) void radix_hist_cap_kernel(const ItemT *__restrict__ in, int32_t *__restrict__ hist, int32_t *__restrict__ acc,
+                                                             int64_t n, int shift, int sb, const int32_t *__restrict__ d_count)
+{
+    radix_hist_block<RADIX_ITEMS, BITS, ItemT, false>(in, hist, acc, gsr_capped_count(d_count, n), shift, sb, (int)blockIdx.x, 0u, 0u, false);
 }
 
 // The id-order scan behind preprocess (scan_final_kernel<0, 4>), the depth sort's pass plan (its control workgroup) and the
@@ -490,8 +501,10 @@ struct ScatterFinal {
 
 // PACKCAP (DEPTH, not CARRY): the host allows packed depth items (DepthPass.pack_ok), so this pass may be the one that packs them and
 // needs the rectangles' LDS image -- 32 KB at 4096-item chunks, which a frame that cannot pack (C5's 120 x 68 grid) must not pay for.
+// CAP (capacity mode, tile partition only -- never DEPTH): n is the capacity K, the pass moves the first min(D, K) items, D read
+// through dp.count (gsr_internal.h "capacity mode").
 template <int RADIX_ITEMS, int BITS, typename ItemT, bool CARRY = false, bool FINAL = false, bool DEPTH = false, int THREADS = 256, bool LOWREC = false,
-          bool PACKCAP = false>
+          bool PACKCAP = false, bool CAP = false>
 __global__ __launch_bounds__(THREADS) void radix_scatter_kernel(const ItemT *__restrict__ in, ItemT *__restrict__ out,
                                                             const int32_t *__restrict__ hist, const int32_t *__restrict__ acc,
                                                             int64_t n, int shift, int nb, int sb, bool prefixed, int32_t *__restrict__ zero_acc,
@@ -533,6 +546,14 @@ __global__ __launch_bounds__(THREADS) void radix_scatter_kernel(const ItemT *__r
     bool drop_culled = false;
     bool packed = false, pack_now = false, unpack = false; // DEPTH: "packed depth items" above (all wave-uniform)
     int64_t n_load = n; // items readable in `in` (the index clamp of the loads)
+    if constexpr (CAP) {
+        n = n_load = gsr_capped_count(dp.count, n);
+        if (block_base >= n) { // past the frame's items (its accumulator share is cleared above): for the final pass, empty runs
+            if constexpr (FINAL)
+                for (int d = tid; d < RADIX; d += THREADS) fin.edge_first[(size_t)d * nb + blockIdx.x] = -1;
+            return;
+        }
+    }
     if constexpr (DEPTH) {
         const DepthCtl c = depth_ctl_load(dp.ctl, dp.force_npass);
         if (dp.pass < c.first || c.first < dp.launched_first) return;
@@ -903,13 +924,21 @@ __global__ __launch_bounds__(1024) void depth_block_offsets_kernel(const int32_t
 // histogram kernel, which re-read all D items, is not launched.  It finds the 256-Gaussian block holding its first item by a
 // two-level search of pre256 (two dependent loads), then walks blocks of 256 Gaussians: rectangle -> count -> offsets by a
 // block scan on top of pre256[B], and every thread places items by an 8-step search of the 256 offsets in LDS.
-template <typename ItemT>
-__global__ __launch_bounds__(256) void expand_blocks_kernel(const uint32_t *__restrict__ id_sorted, const int32_t *__restrict__ cnt_sorted,
-                                                            const int32_t *__restrict__ pre256, const int32_t *__restrict__ sum4096, int nsum,
-                                                            const TileRect *__restrict__ rect, ItemT *__restrict__ tile_items, int64_t n, int grid_x,
-                                                            int64_t D, int id_shift, int chunk, int digit_mask, int32_t *__restrict__ hist,
-                                                            int32_t *__restrict__ acc, int sb)
+// CAP (capacity mode): D is the capacity K, the items are the first min(*d_count, K) of the list.
+template <typename ItemT, bool CAP>
+__device__ __forceinline__ void expand_blocks_body(const uint32_t *__restrict__ id_sorted, const int32_t *__restrict__ cnt_sorted,
+                                                   const int32_t *__restrict__ pre256, const int32_t *__restrict__ sum4096, int nsum,
+                                                   const TileRect *__restrict__ rect, ItemT *__restrict__ tile_items, int64_t n, int grid_x,
+                                                   int64_t D, int id_shift, int chunk, int digit_mask, int32_t *__restrict__ hist,
+                                                   int32_t *__restrict__ acc, int sb, const int32_t *__restrict__ d_count)
 {
+    if constexpr (CAP) {
+        D = gsr_capped_count(d_count, D);
+        if ((int64_t)blockIdx.x * chunk >= D) { // no items of this block: an empty histogram row for the first partition pass
+            if ((int)threadIdx.x <= digit_mask) hist[(size_t)blockIdx.x * (digit_mask + 1) + threadIdx.x] = 0;
+            return;
+        }
+    }
     __shared__ int s_off[257]; // [256] = the end of the block's items
     __shared__ TileRect s_rect[256];
     __shared__ uint32_t s_gid[256];
@@ -1049,6 +1078,27 @@ __global__ __launch_bounds__(256) void expand_blocks_kernel(const uint32_t *__re
         hist[(size_t)blockIdx.x * (digit_mask + 1) + tid] = c;
         if (c) atomicAdd(&acc[256 + ((int)blockIdx.x / sb) * 256 + tid], c);
     }
+}
+
+template <typename ItemT>
+__global__ __launch_bounds__(256) void expand_blocks_kernel(const uint32_t *__restrict__ id_sorted, const int32_t *__restrict__ cnt_sorted,
+                                                            const int32_t *__restrict__ pre256, const int32_t *__restrict__ sum4096, int nsum,
+                                                            const TileRect *__restrict__ rect, ItemT *__restrict__ tile_items, int64_t n, int grid_x,
+                                                            int64_t D, int id_shift, int chunk, int digit_mask, int32_t *__restrict__ hist,
+                                                            int32_t *__restrict__ acc, int sb)
+{
+    expand_blocks_body<ItemT, false>(id_sorted, cnt_sorted, pre256, sum4096, nsum, rect, tile_items, n, grid_x, D, id_shift, chunk, digit_mask, hist, acc, sb,
+                                     nullptr);
+}
+template <typename ItemT>
+__global__ __launch_bounds__(256) void expand_blocks_cap_kernel(const uint32_t *__restrict__ id_sorted, const int32_t *__restrict__ cnt_sorted,
+                                                                const int32_t *__restrict__ pre256, const int32_t *__restrict__ sum4096, int nsum,
+                                                                const TileRect *__restrict__ rect, ItemT *__restrict__ tile_items, int64_t n, int grid_x,
+                                                                int64_t K, int id_shift, int chunk, int digit_mask, int32_t *__restrict__ hist,
+                                                                int32_t *__restrict__ acc, int sb, const int32_t *__restrict__ d_count)
+{
+    expand_blocks_body<ItemT, true>(id_sorted, cnt_sorted, pre256, sum4096, nsum, rect, tile_items, n, grid_x, K, id_shift, chunk, digit_mask, hist, acc, sb,
+                                    d_count);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1208,9 +1258,40 @@ static PassGeom pass_geom(int64_t n)
 
 template <int BITS, typename ItemT, bool CARRY, bool FINAL, bool DEPTH = false, bool LOWREC = false, bool PACKCAP = false>
 static void radix_pass_launch(const ItemT *in, ItemT *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int32_t *zero_acc, int zero_n,
-                              const ScatterCarry &carry, const ScatterFinal &fin, hipStream_t s, const DepthPass &dp = DepthPass{}, bool hist_ready = false)
+                              const ScatterCarry &carry, const ScatterFinal &fin, hipStream_t s, const DepthPass &dp = DepthPass{}, bool hist_ready = false,
+                              const int32_t *d_count = nullptr)
 {
     const PassGeom g = pass_geom(n);
+    if constexpr (!CARRY && !DEPTH && !PACKCAP) {
+        if (d_count) { // capacity mode: the same launches, sized from the capacity n = K; the kernels read the real count
+            DepthPass cdp{};
+            cdp.count = d_count;
+            if (hist_ready) {
+            } else if (g.tier == 0) {
+                hipLaunchKernelGGL((radix_hist_cap_kernel<GSR_RADIX_TINY_CHUNK / 256, BITS, ItemT>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
+            } else if (g.tier == 1) {
+                hipLaunchKernelGGL((radix_hist_cap_kernel<GSR_RADIX_SMALL_CHUNK / 256, BITS, ItemT>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
+            } else {
+                hipLaunchKernelGGL((radix_hist_cap_kernel<GSR_RADIX_CHUNK / 256, BITS, ItemT>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
+            }
+            // (the super-block scan needs no count: the rows of super-blocks past the items were cleared and nothing added to them)
+            if (g.prefixed) hipLaunchKernelGGL(radix_superscan_kernel, dim3(4), dim3(1024), 0, s, acc, (g.nb + g.sb - 1) / g.sb, dp);
+            if (g.tier == 0) {
+                hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_TINY_CHUNK / 256, BITS, ItemT, false, FINAL, false, 256, LOWREC, false, true>), dim3(g.nb), dim3(256), 0, s, in, out, hist, acc, n,
+                                   shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, ScatterCarry{}, fin, cdp);
+            } else if (g.tier == 1) {
+                hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_SMALL_CHUNK / GSR_RADIX_SMALL_WG, BITS, ItemT, false, FINAL, false, GSR_RADIX_SMALL_WG, LOWREC, false, true>), dim3(g.nb),
+                                   dim3(GSR_RADIX_SMALL_WG), 0, s, in, out, hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, ScatterCarry{}, fin, cdp);
+            } else {
+                hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_CHUNK / GSR_RADIX_WG, BITS, ItemT, false, FINAL, false, GSR_RADIX_WG, LOWREC, false, true>), dim3(g.nb), dim3(GSR_RADIX_WG), 0, s,
+                                   in, out, hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, ScatterCarry{}, fin, cdp);
+            }
+            if constexpr (FINAL) // (empty runs of blocks past the items are marked by those blocks: the fix-up walks all g.nb)
+                hipLaunchKernelGGL(ranges_fixup_kernel, dim3(1 << BITS), dim3(1024), 0, s, fin.edge_first, fin.edge_last, fin.edge_pos, acc, g.nb, 1 << BITS,
+                                   fin.ranges);
+            return;
+        }
+    }
     // (a skipped depth pass leaves its accumulator rows zero: the super-block scan of a many-block pass then scans zeros)
     // hist_ready: the kernel that produced `in` left this pass's block histograms and super-block sums (expand_blocks_kernel)
     if (hist_ready) {
@@ -1239,29 +1320,29 @@ static void radix_pass_launch(const ItemT *in, ItemT *out, int32_t *hist, int32_
 
 template <typename ItemT, bool FINAL>
 static hipError_t radix_pass_any(const ItemT *in, ItemT *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int32_t *zero_acc,
-                                 int zero_n, const ScatterFinal &fin, hipStream_t s, bool hist_ready)
+                                 int zero_n, const ScatterFinal &fin, hipStream_t s, bool hist_ready, const int32_t *d_count)
 {
     const ScatterCarry nc{};
     const DepthPass nd{};
     if constexpr (FINAL && sizeof(ItemT) == 4) {
         if (fin.low_bits) { // narrowed items: the kernel that also recovers the first pass's digit (ScatterFinal)
             switch (bits) {
-            case 4: radix_pass_launch<4, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-            case 5: radix_pass_launch<5, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-            case 6: radix_pass_launch<6, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-            case 7: radix_pass_launch<7, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-            case 8: radix_pass_launch<8, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
+            case 4: radix_pass_launch<4, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+            case 5: radix_pass_launch<5, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+            case 6: radix_pass_launch<6, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+            case 7: radix_pass_launch<7, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+            case 8: radix_pass_launch<8, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
             default: return hipErrorInvalidValue;
             }
             return hipGetLastError();
         }
     }
     switch (bits) {
-    case 4: radix_pass_launch<4, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-    case 5: radix_pass_launch<5, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-    case 6: radix_pass_launch<6, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-    case 7: radix_pass_launch<7, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
-    case 8: radix_pass_launch<8, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready); break;
+    case 4: radix_pass_launch<4, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+    case 5: radix_pass_launch<5, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+    case 6: radix_pass_launch<6, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+    case 7: radix_pass_launch<7, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
+    case 8: radix_pass_launch<8, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -1273,7 +1354,7 @@ static hipError_t radix_pass_any(const ItemT *in, ItemT *out, int32_t *hist, int
 // `acc`: this pass's accumulators (gsr_radix_acc_ints(n) ints, zero when the pass's first kernel runs); `zero_acc`: the
 // accumulators of the NEXT pass over the same n, cleared by this pass's scatter (or NULL).
 hipError_t gsr_launch_radix_pass(const void *in, void *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
-                                 int32_t *zero_acc, hipStream_t s, bool hist_ready, int narrow_id_bits, int32_t *totals_out)
+                                 int32_t *zero_acc, hipStream_t s, bool hist_ready, int narrow_id_bits, int32_t *totals_out, const int32_t *d_count)
 {
     if (n <= 0) return hipSuccess;
     const int zero_n = zero_acc ? (int)gsr_radix_acc_ints(n) : 0;
@@ -1281,21 +1362,22 @@ hipError_t gsr_launch_radix_pass(const void *in, void *out, int32_t *hist, int32
     opt.narrow_id_bits = item_bytes == 8 ? narrow_id_bits : 0; // 64-bit items in, 32-bit items out (see ScatterFinal)
     opt.totals = opt.narrow_id_bits ? totals_out : nullptr;
     if (item_bytes == 4)
-        return radix_pass_any<uint32_t, false>((const uint32_t *)in, (uint32_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready);
-    return radix_pass_any<uint64_t, false>((const uint64_t *)in, (uint64_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready);
+        return radix_pass_any<uint32_t, false>((const uint32_t *)in, (uint32_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready, d_count);
+    return radix_pass_any<uint64_t, false>((const uint64_t *)in, (uint64_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready, d_count);
 }
 
 // The LAST pass of the tile partition: histogram, then a scatter that writes point_list and the in-sight range boundaries
 // directly (ScatterFinal), and the edge fix-up.  `edge` holds 3 * (1 << bits) * nb int32 (gsr_radix_blocks(n) = nb).
 hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
                                        int id_shift, int32_t *point_list, int32_t *ranges, int32_t *edge, hipStream_t s, bool hist_ready,
-                                       const int32_t *low_totals, int low_bits)
+                                       const int32_t *low_totals, int low_bits, const int32_t *d_count)
 {
     if (n <= 0) return hipSuccess;
     const size_t per = ((size_t)1 << bits) * (size_t)gsr_radix_blocks(n);
     const ScatterFinal fin{point_list, ranges, edge, edge + per, edge + 2 * per, acc, id_shift, 0, low_totals, low_totals ? low_bits : 0};
-    if (item_bytes == 4) return radix_pass_any<uint32_t, true>((const uint32_t *)in, (uint32_t *)nullptr, hist, acc, n, shift, bits, nullptr, 0, fin, s, hist_ready);
-    return radix_pass_any<uint64_t, true>((const uint64_t *)in, (uint64_t *)nullptr, hist, acc, n, shift, bits, nullptr, 0, fin, s, hist_ready);
+    if (item_bytes == 4)
+        return radix_pass_any<uint32_t, true>((const uint32_t *)in, (uint32_t *)nullptr, hist, acc, n, shift, bits, nullptr, 0, fin, s, hist_ready, d_count);
+    return radix_pass_any<uint64_t, true>((const uint64_t *)in, (uint64_t *)nullptr, hist, acc, n, shift, bits, nullptr, 0, fin, s, hist_ready, d_count);
 }
 
 // The id-order scan of tiles_touched into point_offsets (D to the pinned host word), the depth sort's pass plan and the first
@@ -1334,7 +1416,7 @@ hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, hipStream_t s, int
     const int zero_n = (int)gsr_radix_acc_ints(n);
     const ScatterCarry carry{ws.rect, ws.rect_sorted, ws.cnt_sorted, ws.id_sorted, n};
     for (int pass = 4 - launch_passes; pass < 4; ++pass) {
-        const DepthPass dp{(const DepthCtlRaw *)ws.depth_ctl, (gsr_debug_flags & 256) ? 4 : 0, pass, {ws.depth_item, ws.sort_tmp}, ws.acc_first, 4 - launch_passes, pack_ok};
+        const DepthPass dp{{(const DepthCtlRaw *)ws.depth_ctl}, (gsr_debug_flags & 256) ? 4 : 0, pass, {ws.depth_item, ws.sort_tmp}, ws.acc_first, 4 - launch_passes, pack_ok};
         // pass p accumulates into acc[p & 1] (both cleared by preprocess) and clears the other one for pass p + 1 -- except the
         // first ACTIVE pass, whose histogram and sums were made beside the id-order scan (gsr_launch_scan_ctl_hist) in acc_first.
         // The first LAUNCHED pass is either skipped by the plan or the first active one: its histogram kernel is not launched.
@@ -1365,11 +1447,20 @@ hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *
 // `bits0`: the digit width of the first partition pass over the D items (its digit = the low bits0 bits of the tile id); `hist`,
 // `acc`: that pass's block histograms and (zeroed) accumulators, which this kernel fills -- launch the pass with hist_ready.
 hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t n, int grid_x, int64_t D, int id_shift, int item_bytes, int bits0,
-                                    int32_t *hist, int32_t *acc, hipStream_t s)
+                                    int32_t *hist, int32_t *acc, hipStream_t s, const int32_t *d_count)
 {
     if (n <= 0 || D <= 0) return hipSuccess;
     const PassGeom g = pass_geom(D);
     const int chunk = g.chunk, nsum = (int)gsr_div_up(n, 256);
+    if (d_count) { // capacity mode: D is the capacity K (the grid), the kernel reads the real count
+        if (item_bytes == 4)
+            hipLaunchKernelGGL(expand_blocks_cap_kernel<uint32_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted,
+                               (uint32_t *)tile_items, n, grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb, d_count);
+        else
+            hipLaunchKernelGGL(expand_blocks_cap_kernel<uint64_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted,
+                               (uint64_t *)tile_items, n, grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb, d_count);
+        return hipGetLastError();
+    }
     if (item_bytes == 4)
         hipLaunchKernelGGL(expand_blocks_kernel<uint32_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted, (uint32_t *)tile_items, n,
                            grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb);

@@ -4,6 +4,7 @@ MI355X library.  Same keyword arguments, same (image, depth, dict) return with t
 arrays come back as torch tensors on the GPU instead of wp.array (callers do `.cpu().numpy()`).
 """
 import ctypes as C
+import operator
 import os
 import weakref
 
@@ -25,9 +26,18 @@ _NO_COV_RECOMPUTE = bool(int(os.environ.get("GSR_NO_COV_RECOMPUTE", "0")))   # A
 
 def render_gaussians(background, means3D, colors=None, opacity=None, scales=None, rotations=None, scale_modifier=1.0,
                      viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256,
-                     sh=None, degree=3, campos=None, prefiltered=False, antialiasing=False, clamped=True, debug=False):
+                     sh=None, degree=3, campos=None, prefiltered=False, antialiasing=False, clamped=True, debug=False, *,
+                     capacity=None, capacity_hint=None, capacity_buffers=None):
     """Render 3D Gaussians.  `colors`, `prefiltered`, `antialiasing` are accepted and ignored exactly as in
-    the reference.  Returns (image (H,W,3) f32, inverse-depth (H,W) f32, buffers)."""
+    the reference.  Returns (image (H,W,3) f32, inverse-depth (H,W) f32, buffers).
+
+    capacity=K (an int, 0 <= K <= 2^30) selects capacity mode (include/gsr_capacity.h): the whole forward is enqueued without
+    waiting for the pair count D.  `point_list` then has K entries, of which the first D are valid, and the frame is to be
+    trusted only once rendered_count(buffers) has said D <= K.  capacity_hint: the last D the caller knows (default K), which
+    picks the backward's blend block shape; backward() passes the same value.  capacity_buffers: optional caller-owned
+    {"point_list": int32 [K], "block_masks": uint8 view [K] of >= K + 16 bytes, "binning_ws": uint8 >= gsr_binning_workspace_bytes}."""
+    if capacity is not None:
+        capacity, capacity_hint = _check_capacity(capacity, capacity_hint)
     L = _lib.lib()
     dev = _host.device_of(means3D, sh, opacity, scales, rotations)
     H, W = int(image_height), int(image_width)
@@ -73,29 +83,33 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
 
     with _host.on_device(dev):
         gws = _host.workspace("geom", L.gsr_geom_workspace_bytes(N), dev, stream)
-        D = C.c_int64(0)
-        _lib.check(L.gsr_forward_count(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
-                                       C.byref(D), stream))
-        D = D.value
-        if debug:
-            print(f"gsr: {W}x{H}, N={N}, D={D}, SH degree {degree}")
-        point_list = e((D,), i32)
-        # per-entry 8x4-block hit masks: written by the forward blend, read by backward() (allocated with 16 spare bytes: the
-        # backward reads them 16 at a time)
-        block_masks = e((D + 16,), torch.uint8)[:D]
-        # the backward blend's blocks filed by cost, heaviest first (GsrBinning.block_order): filled by the forward blend from the masks
-        block_order = e((int(L.gsr_block_order_ints(W, H)),), i32)
-        # The backward's workspace, one per call: its accumulator records are what backward() returns dL_dcolor / dL_dmean2D /
-        # dL_dconic as views of, so it must not be shared between calls.  Handed to the forward, its records are cleared by the
-        # blend kernel's spare workgroups.
-        bwd_ws = None
-        if PRECLEAR_BACKWARD and _backward_seen and N > 0 and D > 0:
-            bwd_ws = e((int(L.gsr_backward_workspace_bytes(N, D, W, H)),), torch.uint8)
-        binning = _lib.GsrBinning(D, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(block_masks), _host.ptr(block_order),
-                                  _host.ptr(bwd_ws), 0)
-        bws = _host.workspace("bin", L.gsr_binning_workspace_bytes(N, D, W, H), dev, stream)
-        _lib.check(L.gsr_forward_render(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img),
-                                        _host.ptr(gws), gws.numel(), _host.ptr(bws), bws.numel(), stream))
+        if capacity is not None:
+            point_list, block_masks, block_order, bwd_ws = _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev,
+                                                                            stream, capacity, capacity_hint, capacity_buffers or {})
+        else:
+            D = C.c_int64(0)
+            _lib.check(L.gsr_forward_count(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
+                                           C.byref(D), stream))
+            D = D.value
+            if debug:
+                print(f"gsr: {W}x{H}, N={N}, D={D}, SH degree {degree}")
+            point_list = e((D,), i32)
+            # per-entry 8x4-block hit masks: written by the forward blend, read by backward() (allocated with 16 spare bytes: the
+            # backward reads them 16 at a time)
+            block_masks = e((D + 16,), torch.uint8)[:D]
+            # the backward blend's blocks filed by cost, heaviest first (GsrBinning.block_order): filled by the forward blend from the masks
+            block_order = e((int(L.gsr_block_order_ints(W, H)),), i32)
+            # The backward's workspace, one per call: its accumulator records are what backward() returns dL_dcolor / dL_dmean2D /
+            # dL_dconic as views of, so it must not be shared between calls.  Handed to the forward, its records are cleared by the
+            # blend kernel's spare workgroups.
+            bwd_ws = None
+            if PRECLEAR_BACKWARD and _backward_seen and N > 0 and D > 0:
+                bwd_ws = e((int(L.gsr_backward_workspace_bytes(N, D, W, H)),), torch.uint8)
+            binning = _lib.GsrBinning(D, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(block_masks), _host.ptr(block_order),
+                                      _host.ptr(bwd_ws), 0)
+            bws = _host.workspace("bin", L.gsr_binning_workspace_bytes(N, D, W, H), dev, stream)
+            _lib.check(L.gsr_forward_render(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img),
+                                            _host.ptr(gws), gws.numel(), _host.ptr(bws), bws.numel(), stream))
     # Let a following backward() use the records as they are: the tag rides on the means2D view (the reference's callers re-pack
     # the dicts by hand, train.py:986-1000) and is honoured when backward() is handed these very three views, unwritten since
     # (views share their base's version counter, so a write through any of them, or into the records, is seen).
@@ -125,3 +139,72 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
         "cov3Ds": cov3Ds, "conic_opacity": conic_opacity, "point_list": point_list, "ranges": ranges,
         "final_Ts": final_Ts, "n_contrib": n_contrib, "clamped_state": clamped_state,
     }
+
+
+def _check_capacity(capacity, hint):
+    """Capacity-mode arguments, checked before anything touches the GPU."""
+    out = []
+    for name, v in (("capacity", capacity), ("capacity_hint", hint)):
+        if v is None and name == "capacity_hint":
+            out.append(None)
+            continue
+        if isinstance(v, bool):
+            raise TypeError(f"{name} must be an integer (got bool)")
+        try:
+            v = operator.index(v)
+        except TypeError:
+            raise TypeError(f"{name} must be an integer (got {type(v).__name__})") from None
+        if not 0 <= v <= _lib.MAX_RENDERED:
+            raise ValueError(f"{name} must lie in [0, 2^30] (got {v})")
+        out.append(v)
+    return out[0], out[1]
+
+
+def _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev, stream, K, hint, bufs):
+    """gsr_forward_capacity: buffers for K pairs, no wait for D.  The count is copied (non-blocking) into pinned memory behind an
+    event; it rides on the point_list tensor (`_gsr_capacity`) for rendered_count() and backward()."""
+    e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+    point_list = bufs.get("point_list")
+    if point_list is None:
+        point_list = e((K,), torch.int32)
+    block_masks = bufs.get("block_masks")
+    if block_masks is None:
+        block_masks = e((K + 16,), torch.uint8)[:K]
+    if point_list.numel() < K or block_masks.numel() < K:
+        raise ValueError("capacity_buffers: point_list and block_masks need K entries")
+    block_order = e((int(L.gsr_block_order_ints(W, H)),), torch.int32)
+    bwd_ws = None
+    if PRECLEAR_BACKWARD and _backward_seen and N > 0:      # (D is not known here: the clear is promised for an empty frame too)
+        bwd_ws = e((int(L.gsr_backward_workspace_bytes(N, K, W, H)),), torch.uint8)
+    # the shape hint: the backward skips its blend for D = 0, so a frame that may hold pairs passes at least 1
+    hint = (K if hint is None else hint) if K > 0 else 0
+    hint = max(1, hint) if K > 0 else 0
+    binning = _lib.GsrBinning(K, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(block_masks), _host.ptr(block_order), _host.ptr(bwd_ws), 0)
+    need = int(L.gsr_binning_workspace_bytes(N, K, W, H))
+    bws = bufs.get("binning_ws")
+    if bws is None:
+        bws = _host.workspace("bin", need, dev, stream)
+    elif bws.numel() < need:
+        raise ValueError(f"capacity_buffers: binning_ws needs {need} bytes")
+    _lib.check(L.gsr_forward_capacity(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws), gws.numel(),
+                                      _host.ptr(bws), bws.numel(), hint, stream))
+    count = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
+    if N > 0:
+        count.copy_(point_offsets[N - 1:N], non_blocking=True)
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(dev))
+    point_list._gsr_capacity = (K, hint, count, done)
+    return point_list, block_masks, block_order, bwd_ws
+
+
+def rendered_count(buf):
+    """(D, overflowed) of a capacity-mode frame: waits for that frame's count copy only (its event), not for the stream.  `buf`:
+    the dict render_gaussians returned, or its point_list.  overflowed = D > K: nothing computed from that frame is trusted."""
+    pl = buf["point_list"] if isinstance(buf, dict) else buf
+    tag = getattr(pl, "_gsr_capacity", None)
+    if tag is None:
+        raise ValueError("not a capacity-mode frame: its D is point_list.shape[0]")
+    K, _, count, done = tag
+    done.synchronize()
+    D = int(count[0])
+    return D, bool(D < 0 or D > K)

@@ -79,7 +79,7 @@ def score_views(P, cams, targets, bg):
     return rows, images
 
 
-def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev):
+def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=()):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -89,6 +89,8 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev):
                "points_start": density_log[0]["points"], "points_final": model.num_points, "density_control_calls": len(density_log) - 1,
                "parameters_finite": finite, "train_views": rows, "train_l1_mean": float(np.mean([r["l1"] for r in rows])),
                "train_psnr_mean": float(np.mean([r["psnr"] for r in rows]))}
+    if args.capacity:
+        summary["capacity_retries"] = len(capacity_log)
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
@@ -106,6 +108,8 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev):
             f.write(json.dumps({"record": "arguments", **{k: v for k, v in vars(args).items()}}) + "\n")
             for d in density_log:
                 f.write(json.dumps({"record": "density_control", **d}) + "\n")
+            for d in capacity_log:
+                f.write(json.dumps({"record": "capacity_retry", **d}) + "\n")
             for i in range(0, len(curve), 100):               # every iteration's loss, 100 per line
                 f.write(json.dumps({"record": "loss", "from_iteration": i, "l1": [round(float(x), 6) for x in curve[i:i + 100]]}) + "\n")
             f.write(json.dumps({"record": "summary", **summary}) + "\n")
@@ -152,7 +156,14 @@ def main():
     ap.add_argument("--eval-views", type=int, default=1, help="how many of the training views --eval-dir renders to PNG")
     ap.add_argument("--holdout", default=None, help="NeRF-synthetic split to score after training without training on it, e.g. "
                     "'test:8' = the first 8 frames of transforms_test.json (needs --dataset)")
+    ap.add_argument("--capacity", action="store_true", help="capacity-mode forward (include/gsr_capacity.h): no host wait for the pair "
+                    "count D.  The first iteration and any iteration after the point count changes render with the sized path to learn "
+                    "D; the others with K = ceil(1.25 x the largest D seen).  The count is checked after backward() is enqueued, before "
+                    "Adam; an overflowed view grows K and is run again with the sized path (a capacity_retry record in --log)")
+    ap.add_argument("--capacity-initial", type=int, default=None, help="with --capacity: start with this K instead of a sized first iteration")
     args = ap.parse_args()
+    if args.capacity_initial is not None and not (args.capacity and 0 <= args.capacity_initial <= (1 << 30)):
+        raise SystemExit("--capacity-initial needs --capacity and a value in [0, 2^30]")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and world != args.gpus:
@@ -203,6 +214,10 @@ def main():
     sum_scale = float(cams[0]["height"] * cams[0]["width"] * 3)             # an L1 sum -> mean (all views of a dataset share one size)
     streams_few, streams_many = gsr.dist.ViewStreams(1, dev), gsr.dist.ViewStreams(min(per_rank_views, args.view_streams or 3), dev)
     density_log = [{"iteration": -1, "points": model.num_points}]
+    # --capacity: K (None = render sized), the point count K was last confirmed for, the largest D seen, and each view's last D (its
+    # shape hint: the backward's block shape then follows the view's own count, as on the sized path)
+    cap = {"K": args.capacity_initial, "n": model.num_points if args.capacity_initial is not None else None, "max_D": 0, "D_of": {}}
+    capacity_log, sized_D = [], []
     import time
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
@@ -215,12 +230,17 @@ def main():
         # ranks exchange that (11 + 3 floats per Gaussian instead of 59, dist.py) and the Adam kernel forms basis x payload
         # inside the SH update (optimizer.adam_update(sh_views=...)) -- also with one rank.  --dense-sh keeps the 48-float path.
         factored = not args.dense_sh
-        def one_view(v):
+        def one_view(v, capacity=None):
             c = cams[v]
             kw = dict(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
                       viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"], tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"],
                       image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"])
-            img, _, buf = gsr.render_gaussians(**kw)
+            if capacity is None:
+                img, _, buf = gsr.render_gaussians(**kw)
+                if args.capacity:
+                    sized_D.append(int(buf["point_list"].shape[0]))        # (the sized path's D: what --capacity learns K from)
+            else:
+                img, _, buf = gsr.render_gaussians(**kw, capacity=capacity, capacity_hint=cap["D_of"].get(v, cap["max_D"]))
             # (one view per rank and step: the L1 sum goes straight into this iteration's slot of the loss curve)
             loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None)
             g = gsr.backward(background=bg, means3D=P["positions"], dL_dpixels=dpix, opacity=P["opacities"], shs=P["shs"], scales=P["scales"],
@@ -230,12 +250,39 @@ def main():
                              cov3Ds=buf["cov3Ds"], clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
                              img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
                              sh_gradient="factored" if factored else "dense")
+            if capacity is not None:
+                return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"], buf
             return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"]
+
+        def capacity_views():
+            """--capacity: every view enqueued without a wait for D; then, with the backward enqueued and before Adam, each view's count
+            is read (the GPU is long past the scan) and an overflowed view is run again with the sized path."""
+            sized = cap["K"] is None or cap["n"] != n
+            out = []
+            for v in mine:
+                if sized:                                                   # learn D (first iteration, or the point count changed)
+                    out.append(one_view(v, None))
+                    cap["D_of"][v] = sized_D[-1]
+                    cap["max_D"] = max(cap["max_D"], sized_D[-1])
+                    cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
+                    continue
+                l_v, a_v, p_v, buf = one_view(v, cap["K"])
+                D, overflowed = gsr.forward.rendered_count(buf)
+                cap["D_of"][v] = D
+                cap["max_D"] = max(cap["max_D"], D)
+                if overflowed:                                              # nothing computed from that frame is trusted
+                    capacity_log.append({"iteration": it, "view": v, "capacity": cap["K"], "D": D})
+                    cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
+                    l_v, a_v, p_v = one_view(v)
+                out.append((l_v, a_v, p_v))
+            if sized:
+                cap["n"] = n
+            return out
 
         # a rank with several views renders them on separate streams (one view's sort chain under another's blend kernels) and
         # then sums them in view order, exactly as the serial loop does
         view_streams = streams_many if (args.view_streams > 1 or (args.view_streams == 0 and n >= (1 << 17))) else streams_few
-        for l_v, a_v, p_v in view_streams.map(one_view, mine):
+        for l_v, a_v, p_v in (capacity_views() if args.capacity else view_streams.map(one_view, mine)):
             if len(mine) > 1:
                 loss_acc += l_v
             arena = a_v if arena is None else arena.add_(a_v)
@@ -293,7 +340,7 @@ def main():
     if per_rank_views == 1:
         loss_hist /= sum_scale                                              # slots hold sums of |difference|: one division for the whole curve
     if rank == 0:
-        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev)
+        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log)
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Host time of one render_gaussians() + backward() pair: a scene so small (64 Gaussians, 32 x 32 pixels) that the GPU is never
-the limit, so the wall clock per step is what the Python / ctypes / launch path costs; then cProfile's top entries."""
+the limit, so the wall clock per step is what the Python / ctypes / launch path costs; then cProfile's top entries.
+`--capacity K`: the same with the capacity-mode forward (include/gsr_capacity.h), which does not wait for D."""
 import cProfile, importlib, os, pstats, sys, time
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -17,12 +18,13 @@ dpix = t(np.random.default_rng(9).normal(0.0, 1.0, (H, W, 3)))
 kw = dict(background=bg, **P, viewmatrix=cam["world_to_camera"], projmatrix=cam["full_proj_matrix"], tan_fovx=cam["tan_fovx"], tan_fovy=cam["tan_fovy"],
           image_height=H, image_width=W, sh=shs, degree=3, campos=cam["camera_center"])
 tf = tb = 0.0
+CAP = {"capacity": int(sys.argv[sys.argv.index("--capacity") + 1])} if "--capacity" in sys.argv else {}
 
 
 def step():
     global tf, tb
     t0 = time.perf_counter()
-    img, depth, buf = gsr.render_gaussians(**kw)
+    img, depth, buf = gsr.render_gaussians(**kw, **CAP)
     t1 = time.perf_counter()
     gsr.backward(background=bg, dL_dpixels=dpix, shs=shs, **P, viewmatrix=kw["viewmatrix"], projmatrix=kw["projmatrix"], tan_fovx=kw["tan_fovx"],
                  tan_fovy=kw["tan_fovy"], image_height=H, image_width=W, campos=kw["campos"], radii=buf["radii"], means2D=buf["points_xy_image"],
@@ -42,7 +44,8 @@ for _ in range(n):
     step()
 torch.cuda.synchronize()
 wall = time.perf_counter() - t0
-print(f"wall {wall / n * 1e6:.1f} us per step: render_gaussians {tf / n * 1e6:.1f} us (includes the wait for D), backward {tb / n * 1e6:.1f} us")
+print(f"wall {wall / n * 1e6:.1f} us per step: render_gaussians {tf / n * 1e6:.1f} us "
+      f"({'capacity mode, K = %d: no wait' % CAP['capacity'] if CAP else 'includes the wait for D'}), backward {tb / n * 1e6:.1f} us")
 pr = cProfile.Profile()
 pr.enable()
 for _ in range(500):
