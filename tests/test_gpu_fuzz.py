@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 from conftest import lego_camera
-from test_gpu_parity import _fwd_bwd
+from test_gpu_parity import _fwd_bwd, _pixel_grad
 
 pytestmark = pytest.mark.gpu
 CASES = int(os.environ.get("GSR_FUZZ_CASES", "32"))
@@ -41,6 +41,39 @@ def _case(scenes, cameras, seed):
     return sc, cam, W, H, int(rng.integers(0, 4)), bool(rng.integers(0, 2)), tuple(rng.uniform(0, 1, 3).round(2))
 
 
+# The re-judging gate.  Seed 15099 of round 4's 20 000-case sweep, the one case the fallback exists for: scales 0.93 : 0.019,
+# radius 325 px, conic determinant 2e-5, i.e. a blurred Sigma2D with condition number about 2.7e3.  A case is re-judged only
+# if EVERY element outside the tight band of the failing array belongs to a Gaussian at least that ill-conditioned, within a
+# factor of about 3 in the condition number and 2 in the radius; a well-conditioned Gaussian out of band is a regression.
+REJUDGE_KAPPA, REJUDGE_RADIUS = 1000.0, 150
+
+
+def conic_condition(conic_opacity):
+    """Condition number of the 2x2 conic [[A, B], [B, C]] (the same as of the blurred Sigma2D it inverts)."""
+    c = np.asarray(conic_opacity, np.float64).reshape(-1, 4)
+    a, b, d = c[:, 0], c[:, 1], c[:, 2]
+    mid, rad = 0.5 * (a + d), np.sqrt(0.25 * (a - d) ** 2 + b * b)
+    lo = mid - rad
+    return np.where(lo > 0, (mid + rad) / np.where(lo > 0, lo, 1.0), np.inf)
+
+
+def rejudge_allowed(got, ref, conic_opacity, radii, kappa_min=REJUDGE_KAPPA, radius_min=REJUDGE_RADIUS):
+    """True when `got` misses the standard gradient contract against `ref` only on ill-conditioned Gaussians: every element
+    outside the tight band (parity.GRAD_ABS * max|g| + parity.GRAD_REL * |g|) is in the row of a Gaussian whose conic has
+    condition number >= kappa_min and whose radius is >= radius_min.  False when nothing is out of band (nothing to re-judge)."""
+    import parity
+    radii = np.asarray(radii).reshape(-1)
+    n = radii.shape[0]
+    got = parity.to_np(got).astype(np.float64).reshape(n, -1)
+    ref = parity.to_np(ref).astype(np.float64).reshape(n, -1)
+    m = np.abs(ref).max() if ref.size else 0.0
+    out = (np.abs(got - ref) > parity.GRAD_ABS * m + parity.GRAD_REL * np.abs(ref)).any(axis=1)
+    if not out.any():
+        return False
+    ill = (conic_condition(conic_opacity) >= kappa_min) & (radii >= radius_min)
+    return bool(ill[out].all())
+
+
 def _needle_criterion(gsr, oracle, parity, bkw, arrays):
     """The criterion of test_needle_splats_against_both_checkers (frozen in round 3), as a function: the kernel against the
     exactly accumulated answer, with the reference-order float32 sum's own error and the kernel's run-to-run spread as yardsticks."""
@@ -69,17 +102,30 @@ def test_random_configuration(oracle, cameras, scenes, seed):
         # dL_dmean3D inside where 99.9 % are asked for -- and so has the reference-order float32 sum against the exactly
         # accumulated one, and the kernel against itself on a second run (tools/seed_probe.py 15099).  Such a case is re-judged
         # by the needle test's frozen criterion: a per-Gaussian gradient array only, this family only, the forward never.
+        # Only where every out-of-band element belongs to a measurably ill-conditioned Gaussian (rejudge_allowed), in both
+        # backward inputs _fwd_bwd checks; otherwise the failure stands.
         if seed % 6 != 3 or not any(k in str(err) for k in ("dL_dmean3D", "dL_dscale", "dL_drot")):
             raise
         import parity
         from conftest import backward_kwargs, pkg, render_kwargs
         kw = render_kwargs(sc, cam, width=W, height=H, degree=degree, train_convention=train_convention, bg=bg)
         ref = oracle.render_gaussians(**kw)
-        parity.compare_forward(pkg().render_gaussians(**kw), ref)
+        got = pkg().render_gaussians(**kw)
+        parity.compare_forward(got, ref)
         dpix = (np.random.default_rng(seed).normal(0.0, 1.0, (H, W, 3)) / (H * W * 3)).astype(np.float32)
+        dpix_fwd = _pixel_grad(H, W)                                      # the pixel gradient _fwd_bwd failed with
+        g_ref = oracle.backward(**backward_kwargs(sc, cam, kw, ref[2], dpix_fwd))
+        for bufs in (ref[2], got[2]):
+            g = pkg().backward(**backward_kwargs(sc, cam, kw, bufs, dpix_fwd))
+            for k in ("dL_dmean3D", "dL_dscale", "dL_drot"):
+                try:
+                    parity.assert_grad(k, g[k], g_ref[k])
+                except AssertionError:
+                    if not rejudge_allowed(g[k], g_ref[k], ref[2]["conic_opacity"], ref[2]["radii"]):
+                        raise
         _needle_criterion(pkg(), oracle, parity, backward_kwargs(sc, cam, kw, ref[2], dpix),
                           ("dL_dcolor", "dL_dopacity", "dL_dmean2D", "dL_dconic", "dL_dmean3D", "dL_dscale", "dL_drot", "dL_dshs"))
-        print(f"\nfuzz seed {seed}: ill-conditioned 50:1 splat, judged by the needle criterion ({str(err).splitlines()[0][:120]})")
+        print(f"\nfuzz seed {seed}: RE-JUDGED, ill-conditioned 50:1 splat, judged by the needle criterion ({str(err).splitlines()[0][:120]})")
 
 
 # ---- beyond 50:1: needle-like splats, where float32 accumulation order is the limit, for the oracle as for the kernel ----
