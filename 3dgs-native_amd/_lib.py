@@ -105,6 +105,13 @@ CAPACITY_EXPORTS = {
                                        C.POINTER(GsrImage), vp, C.c_size_t, vp, C.c_size_t, C.c_int64, vp]),
 }
 
+# include/gsr_loss.h: the L1 + D-SSIM training loss with its pixel gradient (its own header, so its own table)
+LOSS_EXPORTS = {
+    "gsr_dssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_l1_dssim_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, vp]),
+}
+SSIM_WINDOWS = {"reference": 0, "gaussian": 1}   # GSR_SSIM_WINDOW_REFERENCE / GSR_SSIM_WINDOW_GAUSSIAN
+
 STAGES = ["preprocess", "scan", "depth_sort", "host_gap", "depth_scan", "expand", "tile_sort", "ranges", "blend_fwd",
           "bwd_prep", "blend_bwd", "geom_bwd"]
 
@@ -119,7 +126,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(hipcc --offload-arch=gfx950).  There is no fallback path.")
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()):
+        for name, (res, args) in list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items()):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -1,8 +1,10 @@
 """
 Loss step between forward and backward: the reference's `l1_loss` and
 `compute_image_gradients` (reference loss.py:148-176, :217-244) on the GPU, in one pass over the image.
-As in the reference, `lambda_dssim` only scales the L1 gradient; the SSIM gradient is a TODO there
-(loss.py:243) and is not invented here.
+As in the reference, `lambda_dssim` only scales the L1 gradient there; the SSIM gradient is a TODO in the
+reference (loss.py:243), and those two functions keep the reference's behaviour.
+The standard 3DGS loss (1 - lambda) L1 + lambda (1 - SSIM) with its full pixel gradient is
+`l1_dssim_loss_and_gradients` (include/gsr_loss.h).
 """
 import torch
 
@@ -42,9 +44,57 @@ def compute_image_gradients(rendered, target, lambda_dssim=0.2):
     return l1_loss_and_gradients(rendered, target, lambda_dssim)[1]
 
 
-def ssim(rendered, target):
+_DSSIM_WS = {}   # (device, stream, W, H) -> workspace of gsr_l1_dssim_loss_grad (one per stream: views in flight on several streams)
+
+
+def _slot(t, name):
+    if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
+        raise ValueError(f"l1_dssim_loss_and_gradients: {name} must be a 1-element float32 device tensor")
+    return t
+
+
+def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaussian", want_grad=True, loss_out=None, ssim_out=None):
+    """L = (1 - lambda) L1 + lambda (1 - SSIM) in one call (include/gsr_loss.h), with no host sync.
+    Returns (l1_sum, ssim_sum, pixel_grad): device tensors [1] with l1_sum = sum |rendered - target| (mean L1 = l1_sum / (3HW))
+    and ssim_sum = sum over pixels of the channel-mean SSIM (SSIM = ssim_sum / (HW)), and pixel_grad = dL/drendered (H, W, 3),
+    or None without want_grad.  window: "gaussian" (centred sigma = 1.5, standard 3DGS) or "reference" (gsr_ssim's weights),
+    both clipped to the image and renormalised at the border.  `loss_out` / `ssim_out`: 1-element float32 device tensors (e.g.
+    slots of a trainer's curves) that receive the sums instead of fresh ones."""
+    if window not in _lib.SSIM_WINDOWS:
+        raise ValueError(f"window must be one of {sorted(_lib.SSIM_WINDOWS)}, not {window!r}")
+    lam = float(lambda_dssim)
+    if not 0.0 <= lam <= 1.0:
+        raise ValueError(f"lambda_dssim must be in [0, 1], not {lambda_dssim}")
+    _slot(loss_out, "loss_out")
+    _slot(ssim_out, "ssim_out")
+    L = _lib.lib()
+    dev = _host.device_of(rendered, target)
+    r = _host.to_dev(rendered, torch.float32, dev)
+    H, W = int(r.shape[0]), int(r.shape[1])
+    r = r.reshape(H, W, 3)
+    t = _host.to_dev(target, torch.float32, dev, (H, W, 3))
+    grad = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_grad else None
+    l1_sum = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
+    ssim_sum = torch.empty(1, dtype=torch.float32, device=dev) if ssim_out is None else ssim_out
+    with _host.on_device(dev):
+        stream = _host.stream_ptr(dev)
+        key = (dev, stream, W, H)
+        ws = _DSSIM_WS.get(key)
+        if ws is None:
+            ws = _DSSIM_WS[key] = torch.empty(max(16, int(L.gsr_dssim_workspace_bytes(W, H))), dtype=torch.uint8, device=dev)
+        _lib.check(L.gsr_l1_dssim_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(grad), _host.ptr(l1_sum), _host.ptr(ssim_sum), W, H,
+                                            lam, _lib.SSIM_WINDOWS[window], _host.ptr(ws), ws.numel(), stream))
+    return l1_sum, ssim_sum, grad
+
+
+def ssim(rendered, target, window="reference"):
     """Mean SSIM as a Python float (reference loss.py:178-215: 11x11 window, sigma 1.5, weights indexed by distance as the
-    reference does -- see gsr.h).  An evaluation helper: the reference's training loop has its SSIM term commented out."""
+    reference does -- see gsr.h).  An evaluation helper: the reference's training loop has its SSIM term commented out.
+    window="gaussian": the centred sigma = 1.5 window standard 3DGS trains with (gsr_loss.h), through l1_dssim_loss_and_gradients."""
+    if window != "reference":
+        r = rendered
+        _, s, _ = l1_dssim_loss_and_gradients(rendered, target, 0.0, window=window, want_grad=False)
+        return float(s.item()) / (int(r.shape[0]) * int(r.shape[1]))
     L = _lib.lib()
     dev = _host.device_of(rendered, target)
     r = _host.to_dev(rendered, torch.float32, dev)

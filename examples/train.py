@@ -68,18 +68,20 @@ def render_view(P, c, bg):
 
 
 def score_views(P, cams, targets, bg):
-    """Per-view mean L1 and PSNR (10 log10(1 / MSE), colours in [0, 1]) of the current model; the images come back too."""
+    """Per-view mean L1, PSNR (10 log10(1 / MSE), colours in [0, 1]) and SSIM (gaussian window, gsr_loss.h) of the current model;
+    the images come back too."""
     rows, images = [], []
     for c, t in zip(cams, targets):
         img = render_view(P, c, bg).reshape(t.shape)
         d = img - t
         mse = float((d * d).mean().item())
-        rows.append({"l1": float(d.abs().mean().item()), "psnr": (10.0 * np.log10(1.0 / mse)) if mse > 0 else float("inf")})
+        rows.append({"l1": float(d.abs().mean().item()), "psnr": (10.0 * np.log10(1.0 / mse)) if mse > 0 else float("inf"),
+                     "ssim": gsr.loss.ssim(img, t, window="gaussian")})
         images.append(img)
     return rows, images
 
 
-def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=()):
+def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -88,7 +90,7 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
     summary = {"iterations": args.iterations, "wall_s": round(wall, 3), "iterations_per_s": round(args.iterations / wall, 1) if wall > 0 else None,
                "points_start": density_log[0]["points"], "points_final": model.num_points, "density_control_calls": len(density_log) - 1,
                "parameters_finite": finite, "train_views": rows, "train_l1_mean": float(np.mean([r["l1"] for r in rows])),
-               "train_psnr_mean": float(np.mean([r["psnr"] for r in rows]))}
+               "train_psnr_mean": float(np.mean([r["psnr"] for r in rows])), "train_ssim_mean": float(np.mean([r["ssim"] for r in rows]))}
     if args.capacity:
         summary["capacity_retries"] = len(capacity_log)
     if args.holdout and args.dataset:
@@ -96,7 +98,8 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
         hrows, _ = score_views(P, hc, [torch.as_tensor(t).to(dev) for t in ht], bg)
         summary.update({"holdout": args.holdout, "holdout_views": hrows, "holdout_l1_mean": float(np.mean([r["l1"] for r in hrows])),
-                        "holdout_psnr_mean": float(np.mean([r["psnr"] for r in hrows]))})
+                        "holdout_psnr_mean": float(np.mean([r["psnr"] for r in hrows])),
+                        "holdout_ssim_mean": float(np.mean([r["ssim"] for r in hrows]))})
     print(f"trained {args.iterations} iterations in {wall:.2f} s ({summary['iterations_per_s']} it/s); {summary['points_start']} -> "
           f"{model.num_points} points; train L1 {summary['train_l1_mean']:.5f} PSNR {summary['train_psnr_mean']:.2f} dB"
           + (f"; holdout PSNR {summary['holdout_psnr_mean']:.2f} dB" if "holdout_psnr_mean" in summary else "")
@@ -104,6 +107,7 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
     if args.log:
         os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
         curve = loss_hist[:args.iterations].cpu().numpy()
+        scurve = ssim_hist[:args.iterations].cpu().numpy() if ssim_hist is not None else None
         with open(args.log, "w") as f:
             f.write(json.dumps({"record": "arguments", **{k: v for k, v in vars(args).items()}}) + "\n")
             for d in density_log:
@@ -111,7 +115,10 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
             for d in capacity_log:
                 f.write(json.dumps({"record": "capacity_retry", **d}) + "\n")
             for i in range(0, len(curve), 100):               # every iteration's loss, 100 per line
-                f.write(json.dumps({"record": "loss", "from_iteration": i, "l1": [round(float(x), 6) for x in curve[i:i + 100]]}) + "\n")
+                rec = {"record": "loss", "from_iteration": i, "l1": [round(float(x), 6) for x in curve[i:i + 100]]}
+                if scurve is not None:                        # --lambda-dssim > 0: the mean SSIM of the same iterations
+                    rec["ssim"] = [round(float(x), 6) for x in scurve[i:i + 100]]
+                f.write(json.dumps(rec) + "\n")
             f.write(json.dumps({"record": "summary", **summary}) + "\n")
     if args.eval_dir:
         os.makedirs(args.eval_dir, exist_ok=True)
@@ -161,7 +168,13 @@ def main():
                     "D; the others with K = ceil(1.25 x the largest D seen).  The count is checked after backward() is enqueued, before "
                     "Adam; an overflowed view grows K and is run again with the sized path (a capacity_retry record in --log)")
     ap.add_argument("--capacity-initial", type=int, default=None, help="with --capacity: start with this K instead of a sized first iteration")
+    ap.add_argument("--lambda-dssim", type=float, default=0.0, help="train on (1 - lambda) L1 + lambda (1 - SSIM) (include/gsr_loss.h; "
+                    "standard 3DGS uses 0.2).  0 = L1 alone, the reference trainer's loss")
+    ap.add_argument("--ssim-window", default="gaussian", choices=["gaussian", "reference"], help="SSIM window of the D-SSIM term: the "
+                    "centred sigma = 1.5 Gaussian of standard 3DGS, or the reference's distance-indexed weights (gsr_ssim)")
     args = ap.parse_args()
+    if not 0.0 <= args.lambda_dssim <= 1.0:
+        raise SystemExit(f"--lambda-dssim must be in [0, 1], not {args.lambda_dssim}")
     if args.capacity_initial is not None and not (args.capacity and 0 <= args.capacity_initial <= (1 << 30)):
         raise SystemExit("--capacity-initial needs --capacity and a value in [0, 2^30]")
 
@@ -210,6 +223,9 @@ def main():
     sched = {k: gsr.scheduler.LRScheduler(lr) for k, lr in gsr.optimizer.DEFAULT_LR.items()}
     rng = np.random.default_rng(0)                                          # same stream on every rank -> same view batch
     loss_hist = torch.zeros(max(1, args.iterations), device=dev)            # the loss curve stays on the device until the end
+    dssim = args.lambda_dssim > 0.0
+    ssim_hist = torch.zeros(max(1, args.iterations), device=dev) if dssim else None   # --lambda-dssim: the SSIM curve beside it
+    ssim_of = {}                                                            # (several views per rank: each view's mean SSIM)
     per_rank_views = -(-args.views_per_step // world)
     sum_scale = float(cams[0]["height"] * cams[0]["width"] * 3)             # an L1 sum -> mean (all views of a dataset share one size)
     streams_few, streams_many = gsr.dist.ViewStreams(1, dev), gsr.dist.ViewStreams(min(per_rank_views, args.view_streams or 3), dev)
@@ -242,7 +258,13 @@ def main():
             else:
                 img, _, buf = gsr.render_gaussians(**kw, capacity=capacity, capacity_hint=cap["D_of"].get(v, cap["max_D"]))
             # (one view per rank and step: the L1 sum goes straight into this iteration's slot of the loss curve)
-            loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None)
+            if dssim:                                                       # ... and the SSIM sum into the SSIM curve's
+                loss_sum, ssim_sum, dpix = gsr.loss.l1_dssim_loss_and_gradients(
+                    img, targets[v], args.lambda_dssim, args.ssim_window, loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None,
+                    ssim_out=ssim_hist[it:it + 1] if len(mine) == 1 else None)
+                ssim_of[v] = ssim_sum / (c["height"] * c["width"])          # (a re-run of an overflowed view replaces its entry)
+            else:
+                loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None)
             g = gsr.backward(background=bg, means3D=P["positions"], dL_dpixels=dpix, opacity=P["opacities"], shs=P["shs"], scales=P["scales"],
                              rotations=P["rotations"], viewmatrix=kw["viewmatrix"], projmatrix=kw["projmatrix"], tan_fovx=kw["tan_fovx"],
                              tan_fovy=kw["tan_fovy"], image_height=c["height"], image_width=c["width"], campos=kw["campos"],
@@ -320,6 +342,8 @@ def main():
         gsr.optimizer.adam_update(P, model.grads, M, V, lrs, iteration=it, sh_views=sh_views, sh_degree=3, sh_scale=sh_scale)
         if len(mine) > 1:
             loss_hist[it] = loss_acc[0] / len(mine)
+            if dssim:
+                ssim_hist[it] = sum(ssim_of[v] for v in mine)[0] / len(mine)
         elif len(mine) == 1:
             pass                                                            # written by the loss kernel as a SUM: scaled once, at the end
         log = model.densification_and_pruning(it)                           # train.py:1060
@@ -333,14 +357,21 @@ def main():
         if rank == 0 and args.output and (it % args.save_interval == 0 or it == args.iterations - 1):
             gsr.point_cloud.save_ply(model.params, os.path.join(args.output, "point_cloud", f"iteration_{it}", "point_cloud.ply"), model.num_points)
         if rank == 0 and (it % args.print_interval == 0 or it == args.iterations - 1):
-            shown = float(loss_hist[it].item()) / (sum_scale if len(mine) == 1 else 1.0)
+            if dssim:                                                       # the combined loss (one read of both slots)
+                l1_v, ssim_v = torch.stack([loss_hist[it], ssim_hist[it]]).tolist()
+                l1_v, ssim_v = (l1_v / sum_scale, ssim_v * 3.0 / sum_scale) if len(mine) == 1 else (l1_v, ssim_v)
+                shown = (1.0 - args.lambda_dssim) * l1_v + args.lambda_dssim * (1.0 - ssim_v)
+            else:
+                shown = float(loss_hist[it].item()) / (sum_scale if len(mine) == 1 else 1.0)
             print(f"iter {it:5d}  loss {shown:.6f}", flush=True)
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t_start
     if per_rank_views == 1:
         loss_hist /= sum_scale                                              # slots hold sums of |difference|: one division for the whole curve
+        if dssim:
+            ssim_hist /= sum_scale / 3.0                                    # ... and sums of per-pixel SSIM
     if rank == 0:
-        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log)
+        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist)
 
 
 if __name__ == "__main__":
