@@ -35,26 +35,10 @@ struct Carver {
     }
 };
 
-int tile_bits(int tiles)
-{
-    int b = 1;
-    while ((1LL << b) < tiles) ++b;
-    return b;
-}
-
-struct BinWs {
-    int32_t *hist;       // [nb][256]
-    int32_t *acc[2];     // [gsr_radix_acc_ints(D)] each: see GeomWs::acc
-    int32_t *edge;       // [3 * 256 * nb] first tile / last tile / position of every (digit, block) run of the last pass
-    uint64_t *tile_a;    // [D]
-    uint64_t *tile_b;    // [D]
-    size_t bytes;
-};
-BinWs carve_bin(void *base, int64_t N, int64_t D)
+BinWs carve_bin(void *base, int64_t D)
 {
     Carver c(base);
     BinWs w;
-    (void)N;
     w.hist = c.take<int32_t>(256 * ((size_t)gsr_radix_blocks(D) + 1));
     w.acc[0] = c.take<int32_t>(gsr_radix_acc_ints(D));
     w.acc[1] = c.take<int32_t>(gsr_radix_acc_ints(D));
@@ -129,6 +113,28 @@ bool geom_ok(const GsrGeom *g)
     const bool arrays = g && ((g->xy && g->rgb && g->conic_opacity) || g->blend_records);
     return arrays && g->radii && g->tiles_touched && g->point_offsets && g->depths && g->cov3D &&
            g->clamped_state;
+}
+
+// ---- the argument checks gsr_forward_render and gsr_forward_capacity share (every one before anything is enqueued) ----
+int check_frame(const GsrScene *sc, const GsrCamera *cam, const GsrBinning *b, const GsrImage *img)
+{
+    if (int rc = check_scene_cam(sc, cam)) return rc;
+    if (!b || !img || !img->image || !img->inv_depth || !img->final_T || !img->n_contrib || !b->ranges) return GSR_E_NULL;
+    if (b->D < 0 || b->D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
+    return GSR_OK;
+}
+bool frame_aligned(const GsrGeom *g, const void *geom_ws, const void *bin_ws, const GsrBinning *b, const GsrImage *img)
+{
+    return (!g || geom_aligned(g)) && gsr_aligned16(geom_ws) && gsr_aligned16(bin_ws) && gsr_aligned16(b->point_list) && gsr_aligned16(b->ranges) &&
+           gsr_aligned16(b->block_order) && gsr_aligned16(b->backward_ws) && gsr_aligned16(img->image) && gsr_aligned16(img->inv_depth) &&
+           gsr_aligned16(img->final_T) && gsr_aligned16(img->n_contrib);
+}
+// both workspaces, sized for N Gaussians and D pairs (the capacity K in capacity mode)
+int check_workspaces(int64_t N, int64_t D, const void *geom_ws, size_t geom_ws_bytes, const void *bin_ws, size_t bin_ws_bytes, const GsrCamera *cam)
+{
+    if (N > 0 && (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N))) return GSR_E_WORKSPACE;
+    if (N > 0 && (!bin_ws || bin_ws_bytes < gsr_binning_workspace_bytes(N, D, cam->W, cam->H))) return GSR_E_WORKSPACE;
+    return GSR_OK;
 }
 
 // ---- stage timing (profiling aid) ----
@@ -283,6 +289,23 @@ void read_tuning()
     });
 }
 
+// The front half of the forward, shared by gsr_forward_count and gsr_forward_capacity: preprocess, the id-order scan and the
+// depth sort's last `depth_passes` passes.  With a readback slot the scan's last wave stores D, and its control workgroups the
+// depth extremes, straight into the pinned words, and rb->ev marks the scan's end: work that does not need D goes out before the
+// host waits for it.  Without one D stays in point_offsets[N-1].
+int enqueue_depth_stage(const GsrScene *scene, const CamK &cam, const GsrGeom *geom, const GeomWs &ws, Readback *rb, int depth_passes, hipStream_t s,
+                        int st)
+{
+    mark(st, 0, s);
+    HIP_TRY(gsr_launch_preprocess(*scene, cam, *geom, ws, s, fwd_order_wanted(cam.grid_x * cam.grid_y)));
+    mark(st, 1, s);
+    HIP_TRY(gsr_launch_id_scan(geom->tiles_touched, geom->point_offsets, ws, scene->N, rb ? rb->pinned : nullptr, s));
+    mark(st, 2, s);
+    if (rb) HIP_TRY(hipEventRecord(rb->ev, s));
+    HIP_TRY(gsr_launch_depth_sort(ws, scene->N, cam.grid_x, cam.grid_y, depth_passes, s));
+    return GSR_OK;
+}
+
 } // namespace
 
 GeomWs gsr_carve_geom(void *base, int64_t N)
@@ -339,7 +362,7 @@ const char *gsr_strerror(int code)
 }
 
 size_t gsr_geom_workspace_bytes(int64_t N) { return gsr_carve_geom(nullptr, N < 0 ? 0 : N).bytes; }
-size_t gsr_binning_workspace_bytes(int64_t N, int64_t D, int32_t, int32_t) { return carve_bin(nullptr, N < 0 ? 0 : N, D < 0 ? 0 : D).bytes; }
+size_t gsr_binning_workspace_bytes(int64_t, int64_t D, int32_t, int32_t) { return carve_bin(nullptr, D < 0 ? 0 : D).bytes; }
 size_t gsr_backward_workspace_bytes(int64_t N, int64_t, int32_t, int32_t) { return carve_bwd(nullptr, N < 0 ? 0 : N).bytes; }
 size_t gsr_backward_accumulators_offset(int64_t N) { return gsr_align((size_t)(N < 0 ? 0 : N) * sizeof(BlendRec)); } // carve_bwd: the records come first
 size_t gsr_block_order_ints(int32_t W, int32_t H)
@@ -365,44 +388,19 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     hipStream_t s = (hipStream_t)stream;
     const CamK cam = make_cam(camera);
     const GeomWs ws = gsr_carve_geom(geom_ws, N);
-    const int st = t_fwd_record = timer_open(true);
-    mark(st, 0, s);
-    HIP_TRY(gsr_launch_preprocess(*scene, cam, *geom, ws, s, fwd_order_wanted(cam.grid_x * cam.grid_y)));
-    mark(st, 1, s);
     ReadbackLease lease;
     Readback *rb = lease.r;
     if (!rb) return GSR_E_HIP;
-    // the scan's last wave stores D = point_offsets[N-1] straight into the pinned host word
-    // (preprocess left one partial sum per 256 Gaussians in scan_tmp: one launch)
-    // (its first wave also turns the per-block depth extremes preprocess left into the depth sort's pass plan, on the device)
-    // (words 2 .. : the visible depth extremes, one pair per control workgroup of the scan's launch -- the host derives from them
-    // how many depth passes this frame needed, its launch guess for the next)
-    if (gsr_small_depth_path(N)) HIP_TRY(gsr_launch_scan(geom->tiles_touched, nullptr, geom->point_offsets, ws.scan_tmp, N, 0, rb->pinned, true, s, ws.blk_minmax, ws.depth_ctl));
-    else HIP_TRY(gsr_launch_scan_ctl_hist(geom->tiles_touched, geom->point_offsets, ws, N, rb->pinned, s)); // + the first active depth pass's histogram
-    mark(st, 2, s);
-    HIP_TRY(hipEventRecord(rb->ev, s));
-    // Work that does not need D goes out before the host waits: Gaussians by depth bits (stable from id order, four 8-bit
-    // passes over the high word, ending back in depth_item; the last one also carries each Gaussian's tile rectangle and
-    // tile count to its sorted position).
-    // How many of the four 8-bit passes this frame needs is decided on the device (DepthCtl); the host launches as many as the
-    // previous frame in this workspace needed (its guess; four the first time).  If the guess turns out too low the launched
+    const int st = t_fwd_record = timer_open(true);
+    // How many of the depth sort's four passes this frame needs is decided on the device (DepthCtl); the host launches as many as
+    // the previous frame in this workspace needed (its guess; four the first time).  If the guess turns out too low the launched
     // passes leave the data alone and all four are launched once the readback has said so.
     const int guess = (gsr_debug_flags & 256) ? 4 : depth_pass_guess(geom_ws);
-    // (packed depth items, scan_sort.hip: the tile grid at 6 bits per coordinate, the ids in 24)
-    const int pack_ok = (!(gsr_debug_flags & 2048) && cam.grid_x <= 63 && cam.grid_y <= 63 && N <= (1 << 24)) ? 1 : 0;
-    HIP_TRY(gsr_launch_depth_sort(ws, N, s, guess, pack_ok));
+    if (int rc = enqueue_depth_stage(scene, cam, geom, ws, rb, guess, s, st)) return rc;
     HIP_TRY(hipEventSynchronize(rb->ev)); // D (and the pass count) are on the host; the GPU keeps sorting
     const int32_t last = *rb->pinned;
-    int needed = 4;
-    if (!gsr_small_depth_path(N)) {
-        uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-        for (int k = 0, K = gsr_depth_ctl_wgs(N); k < K; ++k) {
-            lo = std::min(lo, (uint32_t)rb->pinned[2 + 2 * k]);
-            hi = std::max(hi, (uint32_t)rb->pinned[3 + 2 * k]);
-        }
-        needed = gsr_depth_plan(lo, hi, (gsr_debug_flags & 256) ? 4 : 0).npass;
-    }
-    if (needed > guess && !gsr_small_depth_path(N)) HIP_TRY(gsr_launch_depth_sort(ws, N, s, 4, pack_ok));
+    const int needed = gsr_depth_passes_needed(rb->pinned, N);
+    if (needed > guess && !gsr_small_depth_path(N)) HIP_TRY(gsr_launch_depth_sort(ws, N, cam.grid_x, cam.grid_y, 4, s));
     mark(st, 3, s);
     // (the depth-order offsets -- the exclusive scan of those counts -- are made by gsr_forward_render, next to their one reader,
     // the expansion)
@@ -417,7 +415,7 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
 namespace {
 
 // what gsr_forward_render enqueues for a frame without pairs: zeros, not background (quirk Q10), and the promised clear of the
-// backward workspace's accumulators
+// backward workspace's accumulators (its alignment was checked by the caller)
 int empty_frame(const GsrBinning *binning, const GsrImage *image, int64_t N, int tiles, size_t P, hipStream_t s)
 {
     HIP_TRY(hipMemsetAsync(binning->ranges, 0, sizeof(int32_t) * 2 * tiles, s));
@@ -426,10 +424,7 @@ int empty_frame(const GsrBinning *binning, const GsrImage *image, int64_t N, int
     HIP_TRY(hipMemsetAsync(image->final_T, 0, P * sizeof(float), s));
     HIP_TRY(hipMemsetAsync(image->n_contrib, 0, P * sizeof(int32_t), s));
     // the accumulator clear of GsrBinning.backward_ws is promised whenever the workspace is handed over, blend or no blend
-    if (binning->backward_ws && N > 0) {
-        if (!gsr_aligned16(binning->backward_ws)) return GSR_E_ALIGN;
-        HIP_TRY(hipMemsetAsync(carve_bwd(binning->backward_ws, N).acc, 0, sizeof(GradRec) * (size_t)N, s));
-    }
+    if (binning->backward_ws && N > 0) HIP_TRY(hipMemsetAsync(carve_bwd(binning->backward_ws, N).acc, 0, sizeof(GradRec) * (size_t)N, s));
     return GSR_OK;
 }
 
@@ -444,17 +439,9 @@ int enqueue_render(const GsrScene *scene, const CamK &cam, const GsrGeom *geom, 
     const int tiles = cam.grid_x * cam.grid_y;
     if (!d_count) shape_D = D;
     mark(st, 4, s); // (stage 3 -> 4: the host between the two calls -- the wait for D, the caller's allocations)
-    // 3. expansion of the depth-sorted Gaussians (gsr_forward_count) to (tile << id_shift | id) items.  When the tile
-    //    bits and the id bits fit one 32-bit word (800x800 with 1M Gaussians: 12 + 20) the items are uint32, which
-    //    halves the traffic of the expansion, both partition passes and the range scan.
-    const int tb = tile_bits(tiles);
-    int id_bits = 1;
-    while ((1LL << id_bits) < N) ++id_bits;
-    const bool narrow = tb + id_bits <= 32 && !(gsr_debug_flags & 32); // GSR_DEBUG bit 5: 64-bit tile items at any size (tests)
-    const int id_shift = narrow ? id_bits : 32, item_bytes = narrow ? 4 : 8;
-    // the stable partition by tile id below: ceil(tb/8) passes over the tile-id bits, split as evenly as possible (12 bits -> 6+6, 13 -> 7+6)
-    const int npass = (tb + 7) / 8;
-    auto pass_bits = [&](int pass, int shift) { return std::max(4, (tb - shift + (npass - pass) - 1) / (npass - pass)); };
+    // 3. expansion of the depth-sorted Gaussians (gsr_forward_count) to tile items, 4. their stable partition by tile id, whose
+    //    last pass writes point_list and the tile ranges (scan_sort.hip)
+    const TilePlan plan = gsr_tile_plan(N, tiles);
     // the block order (forward -> backward scratch): header cleared here; filed by the blend below unless the image is large
     int32_t *order = binning->block_masks ? binning->block_order : nullptr;
     // (and not for a frame whose backward will take 8x8 blocks, which run in band order: the `filed` flag then stays 0)
@@ -467,45 +454,16 @@ int enqueue_render(const GsrScene *scene, const CamK &cam, const GsrGeom *geom, 
     HIP_TRY(gsr_launch_depth_block_offsets(gw, N, binning->ranges, 2 * tiles, bw.acc[0], (int)gsr_radix_acc_ints(D), order, order ? GSR_BO_HEADER : 0,
                                            file_order ? 1 : 0, s));
     mark(st, 5, s);
-    HIP_TRY(gsr_launch_expand_blocks(gw, bw.tile_a, N, cam.grid_x, D, id_shift, item_bytes, pass_bits(0, 0), bw.hist, bw.acc[0], s, d_count));
+    HIP_TRY(gsr_launch_expand_blocks(plan, gw, bw, N, cam.grid_x, D, d_count, s));
     mark(st, 6, s);
-    // 4. stable partition by tile id
-    void *tsrc = bw.tile_a, *tdst = bw.tile_b;
-    // Two passes over 64-bit items whose remaining tile bits + id bits fit a word after the first one (1080p with 5 M Gaussians:
-    // 6 + 23): the first pass writes 32-bit items and the second recovers the first digit from the item's position
-    // (scan_sort.hip ScatterFinal) -- 4 instead of 8 bytes per item through the second histogram and the final scatter.
-    const int bits0 = pass_bits(0, 0);
-    const bool narrowing = !narrow && npass == 2 && (tb - bits0) + id_bits <= 32 && !(gsr_debug_flags & 4096);
-    for (int pass = 0, shift = 0; pass < npass; ++pass) {
-        const int bits = pass_bits(pass, shift);
-        const bool hist_ready = pass == 0;
-        if (pass + 1 < npass) {
-            HIP_TRY(gsr_launch_radix_pass(tsrc, tdst, bw.hist, bw.acc[pass & 1], D, id_shift + shift, bits, item_bytes, bw.acc[(pass + 1) & 1], s, hist_ready,
-                                          narrowing ? id_bits : 0, narrowing ? bw.acc[pass & 1] : nullptr, d_count));
-        } else if (narrowing) {
-            HIP_TRY(gsr_launch_radix_final_pass(tsrc, bw.hist, bw.acc[pass & 1], D, id_bits, bits, 4, id_bits, binning->point_list, binning->ranges, bw.edge, s,
-                                                false, bw.acc[(pass + 1) & 1], bits0, d_count));
-        } else {
-            // 5. the last pass writes point_list and the tile ranges itself (reference forward.py:806-824, :561-586) instead of
-            //    sorted items that a further kernel would re-read
-            HIP_TRY(gsr_launch_radix_final_pass(tsrc, bw.hist, bw.acc[pass & 1], D, id_shift + shift, bits, item_bytes, id_shift, binning->point_list,
-                                                binning->ranges, bw.edge, s, hist_ready, nullptr, 0, d_count));
-        }
-        shift += bits;
-        void *t = tsrc; tsrc = tdst; tdst = t;
-    }
+    HIP_TRY(gsr_launch_tile_partition(plan, bw, binning->point_list, binning->ranges, D, d_count, s));
     mark(st, 7, s);
     mark(st, 8, s); // (stage slot "ranges": nothing left in it)
     // 6. blend
-        // the backward's accumulator records are cleared by the blend kernel's spare workgroups when the caller hands its backward
+    // the backward's accumulator records are cleared by the blend kernel's spare workgroups when the caller hands its backward
     // workspace over (GsrBinning.backward_ws); it then tells gsr_backward so (GsrBinning.backward_ws_cleared)
-    void *clear = nullptr;
-    size_t clear_bytes = 0;
-    if (binning->backward_ws) {
-        if (!gsr_aligned16(binning->backward_ws)) return GSR_E_ALIGN;
-        clear = carve_bwd(binning->backward_ws, N).acc;
-        clear_bytes = sizeof(GradRec) * (size_t)N;
-    }
+    void *clear = binning->backward_ws ? carve_bwd(binning->backward_ws, N).acc : nullptr;
+    const size_t clear_bytes = clear ? sizeof(GradRec) * (size_t)N : 0;
     HIP_TRY(gsr_launch_blend_forward(cam, binning->ranges, binning->point_list, geom->blend_records ? (const BlendRec *)geom->blend_records : gw.rec, *image, binning->block_masks, file_order ? order : nullptr,
                                      clear, clear_bytes, s, use_fwd_order ? gw.fwd_order : nullptr, tiles <= GSR_FO_MAX_TILES ? gw.fwd_cost : nullptr,
                                      d_count, D));
@@ -521,31 +479,23 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
                        const GsrImage *image, void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, void *stream)
 {
     read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (!binning || !image || !image->image || !image->inv_depth || !image->final_T || !image->n_contrib || !binning->ranges)
-        return GSR_E_NULL;
+    if (int rc = check_frame(scene, camera, binning, image)) return rc;
     const int64_t N = scene->N, D = binning->D;
-    if (D < 0 || D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
     hipStream_t s = (hipStream_t)stream;
     const CamK cam = make_cam(camera);
-    const size_t P = (size_t)cam.W * cam.H;
-    const int tiles = cam.grid_x * cam.grid_y;
     if (D == 0 || N == 0) { // reference skips the blend: zeros, not background (forward.py:830, quirk Q10)
+        if (!gsr_aligned16(binning->backward_ws)) return GSR_E_ALIGN;
         t_fwd_record = -1;  // a sampled record that ends here stays incomplete and is dropped by gsr_stage_times
-        return empty_frame(binning, image, N, tiles, P, s);
+        return empty_frame(binning, image, N, cam.grid_x * cam.grid_y, (size_t)cam.W * cam.H, s);
     }
     if (!geom_ok(geom) || !binning->point_list) return GSR_E_NULL;
-    if (!geom_aligned(geom) || !gsr_aligned16(geom_ws) || !gsr_aligned16(bin_ws) || !gsr_aligned16(binning->point_list) ||
-        !gsr_aligned16(binning->ranges) || !gsr_aligned16(binning->block_order) || !gsr_aligned16(image->image) || !gsr_aligned16(image->inv_depth) ||
-        !gsr_aligned16(image->final_T) || !gsr_aligned16(image->n_contrib))
-        return GSR_E_ALIGN;
-    if (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N)) return GSR_E_WORKSPACE;
-    if (!bin_ws || bin_ws_bytes < gsr_binning_workspace_bytes(N, D, cam.W, cam.H)) return GSR_E_WORKSPACE;
+    if (!frame_aligned(geom, geom_ws, bin_ws, binning, image)) return GSR_E_ALIGN;
+    if (int rc = check_workspaces(N, D, geom_ws, geom_ws_bytes, bin_ws, bin_ws_bytes, camera)) return rc;
     // D must be the count gsr_forward_count returned for the items now in geom_ws (see CountNote above)
     if (check_count(geom_ws, N, D) != 1) return GSR_E_CAPACITY;
     const int st = t_fwd_record;
     t_fwd_record = -1;
-    return enqueue_render(scene, cam, geom, binning, image, gsr_carve_geom(geom_ws, N), carve_bin(bin_ws, N, D), nullptr, D, s, st);
+    return enqueue_render(scene, cam, geom, binning, image, gsr_carve_geom(geom_ws, N), carve_bin(bin_ws, D), nullptr, D, s, st);
 }
 
 int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
@@ -553,40 +503,24 @@ int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const G
 {
     read_tuning();
     // every argument is checked before anything is enqueued (include/gsr_capacity.h)
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (!binning || !image || !image->image || !image->inv_depth || !image->final_T || !image->n_contrib || !binning->ranges)
-        return GSR_E_NULL;
+    if (int rc = check_frame(scene, camera, binning, image)) return rc;
     const int64_t N = scene->N, K = binning->D;
-    if (K < 0 || K > GSR_MAX_RENDERED || shape_hint < 0 || shape_hint > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
+    if (shape_hint < 0 || shape_hint > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
     if (K > 0 && !binning->point_list) return GSR_E_NULL;
     if (N > 0 && !geom_ok(geom)) return GSR_E_NULL;
-    if ((geom && !geom_aligned(geom)) || !gsr_aligned16(geom_ws) || !gsr_aligned16(bin_ws) || !gsr_aligned16(binning->point_list) ||
-        !gsr_aligned16(binning->ranges) || !gsr_aligned16(binning->block_masks) || !gsr_aligned16(binning->block_order) ||
-        !gsr_aligned16(binning->backward_ws) || !gsr_aligned16(image->image) || !gsr_aligned16(image->inv_depth) || !gsr_aligned16(image->final_T) ||
-        !gsr_aligned16(image->n_contrib))
-        return GSR_E_ALIGN;
-    const CamK cam = make_cam(camera);
-    if (N > 0 && (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N))) return GSR_E_WORKSPACE;
-    if (N > 0 && (!bin_ws || bin_ws_bytes < gsr_binning_workspace_bytes(N, K, cam.W, cam.H))) return GSR_E_WORKSPACE;
+    if (!frame_aligned(geom, geom_ws, bin_ws, binning, image) || !gsr_aligned16(binning->block_masks)) return GSR_E_ALIGN;
+    if (int rc = check_workspaces(N, K, geom_ws, geom_ws_bytes, bin_ws, bin_ws_bytes, camera)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int tiles = cam.grid_x * cam.grid_y;
-    if (N == 0) return empty_frame(binning, image, N, tiles, (size_t)cam.W * cam.H, s);
+    const CamK cam = make_cam(camera);
+    if (N == 0) return empty_frame(binning, image, N, cam.grid_x * cam.grid_y, (size_t)cam.W * cam.H, s);
     const GeomWs gw = gsr_carve_geom(geom_ws, N);
     const int st = timer_open(true);
-    mark(st, 0, s);
-    HIP_TRY(gsr_launch_preprocess(*scene, cam, *geom, gw, s, fwd_order_wanted(tiles)));
-    mark(st, 1, s);
-    // the same scan as gsr_forward_count, minus the pinned host words: D stays in point_offsets[N-1], where every D-dependent
-    // kernel below reads it
-    if (gsr_small_depth_path(N)) HIP_TRY(gsr_launch_scan(geom->tiles_touched, nullptr, geom->point_offsets, gw.scan_tmp, N, 0, nullptr, true, s, gw.blk_minmax, gw.depth_ctl));
-    else HIP_TRY(gsr_launch_scan_ctl_hist(geom->tiles_touched, geom->point_offsets, gw, N, nullptr, s));
-    mark(st, 2, s);
     // All four depth passes: with no readback there is no guess to check, and the device plan (DepthCtl) makes the passes this
     // frame does not need return at once -- one or two launches of early-exit workgroups, a few microseconds of GPU time.
-    const int pack_ok = (!(gsr_debug_flags & 2048) && cam.grid_x <= 63 && cam.grid_y <= 63 && N <= (1 << 24)) ? 1 : 0;
-    HIP_TRY(gsr_launch_depth_sort(gw, N, s, 4, pack_ok));
+    // D stays in point_offsets[N-1], where every D-dependent kernel below reads it.
+    if (int rc = enqueue_depth_stage(scene, cam, geom, gw, nullptr, 4, s, st)) return rc;
     mark(st, 3, s);
-    return enqueue_render(scene, cam, geom, binning, image, gw, carve_bin(bin_ws, N, K), geom->point_offsets + (N - 1), shape_hint, s, st);
+    return enqueue_render(scene, cam, geom, binning, image, gw, carve_bin(bin_ws, K), geom->point_offsets + (N - 1), shape_hint, s, st);
 }
 
 // first half: accumulator clear, record (re)pack, blend backward, optional view payload

@@ -229,7 +229,7 @@ int gsr_mask_scan(int64_t N, const int32_t *mask, int32_t *prefix, int32_t *coun
     if (!gsr_aligned16(scratch)) return GSR_E_ALIGN;
     if (scratch_bytes < gsr_mask_scan_workspace_bytes(N)) return GSR_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    if (gsr_launch_scan(mask, nullptr, prefix, (int32_t *)scratch, N, 2, nullptr, false, s) != hipSuccess) return GSR_E_HIP;
+    if (gsr_launch_exclusive_scan(mask, prefix, (int32_t *)scratch, N, s) != hipSuccess) return GSR_E_HIP;
     // the reference's count is the LAST ENTRY of the exclusive scan (train.py:433, 497, 581, 641)
     if (hipMemcpyAsync(count_host, prefix + (N - 1), sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess) return GSR_E_HIP;
     return hipStreamSynchronize(s) == hipSuccess ? GSR_OK : GSR_E_HIP;

@@ -61,10 +61,8 @@ GeomWs gsr_carve_geom(void *base, int64_t N);
 
 // ---- launchers (host functions; each enqueues on `s` and returns hipGetLastError()) ----
 hipError_t gsr_launch_preprocess(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GeomWs &ws, hipStream_t s,
-                                 bool make_fwd_order = false /* a spare workgroup turns ws.fwd_cost into ws.fwd_order */);
+                                 bool make_fwd_order /* a spare workgroup turns ws.fwd_cost into ws.fwd_order */);
 
-// Device-wide scan of int32.  mode 0: out[i] = inclusive scan of in[i].
-// mode 2: out[i] = exclusive scan of in[i] (total_out still receives the grand total).
 // The depth sort's pass plan from the frame's visible depth extremes (bit patterns of positive floats).  Shared by the device
 // (every depth kernel derives it from DepthCtlRaw) and the host (its launch guess for the next frame, from the pinned words).
 struct DepthPlan {
@@ -82,17 +80,19 @@ static inline __host__ __device__ DepthPlan gsr_depth_plan(uint32_t lo, uint32_t
     p.first = 4 - p.npass;
     return p;
 }
-#define GSR_DEPTH_CTL_WGS_MAX 16
-// how many workgroups of the scan's launch reduce the per-block extremes (2048 blocks each at most 16: one round of loads per thread)
-static inline int gsr_depth_ctl_wgs(int64_t N) { const int64_t nblk = (N + 255) / 256; const int64_t k = (nblk + 2047) / 2048; return (int)(k < 1 ? 1 : k > GSR_DEPTH_CTL_WGS_MAX ? GSR_DEPTH_CTL_WGS_MAX : k); }
 #define GSR_SCAN_WAVE_ITEMS 1024   // items per wave-sized scan unit; scratch = one int32 per unit
-hipError_t gsr_launch_scan(const int32_t *in, const uint64_t *items, int32_t *out, int32_t *block_tmp,
-                           int64_t n, int mode, int32_t *total_out /* optional: receives the grand total */,
-                           bool sums_per_256_ready /* mode 0: block_tmp already holds a sum per 256 items */, hipStream_t s,
-                           const uint32_t *blk_minmax = nullptr, void *depth_ctl = nullptr /* mode 0: also derive the depth sort's DepthCtl */);
-hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, hipStream_t s, int launch_passes = 4 /* the last `launch_passes` of the four */,
-                                 int pack_ok = 0 /* the sizes allow packed depth items (scan_sort.hip) */);
-hipError_t gsr_launch_scan_ctl_hist(const int32_t *tiles_touched, int32_t *point_offsets, const GeomWs &ws, int64_t n, int32_t *total_out, hipStream_t s);
+// The id-order inclusive scan of tiles_touched into point_offsets over the sums per 256 Gaussians that preprocess left in
+// ws.scan_tmp.  The same launch derives the depth sort's DepthCtl and (not on the small-scene path) the first active depth pass's
+// histogram.  `host_words` (optional, pinned): word 0 receives D = point_offsets[n-1], words 2 .. the depth extremes that
+// gsr_depth_passes_needed reads.
+hipError_t gsr_launch_id_scan(const int32_t *tiles_touched, int32_t *point_offsets, const GeomWs &ws, int64_t n, int32_t *host_words, hipStream_t s);
+// How many depth passes the frame needed, from the host words of gsr_launch_id_scan once it has run (four on the small-scene path).
+int gsr_depth_passes_needed(const int32_t *host_words, int64_t n);
+// out[i] = exclusive scan of in[i]; block_tmp holds one int32 per GSR_SCAN_WAVE_ITEMS items.
+hipError_t gsr_launch_exclusive_scan(const int32_t *in, int32_t *out, int32_t *block_tmp, int64_t n, hipStream_t s);
+// The depth sort, the last `launch_passes` of its four passes (see scan_sort.hip); whether the items may be packed is decided here
+// from the tile grid and n.
+hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, int grid_x, int grid_y, int launch_passes, hipStream_t s);
 #define GSR_SMALL_SORT_N 8192          // up to this many Gaussians one workgroup sorts, carries and scans (scan_sort.hip)
 bool gsr_small_depth_path(int64_t n); // true: gsr_launch_depth_sort sorts in one workgroup
 
@@ -150,24 +150,38 @@ static inline size_t gsr_radix_acc_ints(int64_t n)
     const int nb = (int)gsr_radix_blocks(n), sb = gsr_radix_sb(nb); // GSR_DEBUG bit 6 cuts n into fewer blocks: fewer rows
     return 256 * (size_t)(3 + nb / sb);
 }
-hipError_t gsr_launch_radix_pass(const void *in, void *out, int32_t *hist /*[nb][radix]*/, int32_t *acc /* gsr_radix_acc_ints(n), zero */,
-                                 int64_t n, int shift, int bits, int item_bytes, int32_t *zero_acc /* next pass's, or NULL */, hipStream_t s,
-                                 bool hist_ready = false /* hist and acc were filled by gsr_launch_expand_blocks */,
-                                 int narrow_id_bits = 0 /* 64-bit items only: > 0 = write 32-bit items (tile >> bits) << narrow_id_bits | id ... */,
-                                 int32_t *totals_out = nullptr /* ... and leave the digit totals here for the final pass (scan_sort.hip ScatterFinal) */,
-                                 const int32_t *d_count = nullptr /* capacity mode (below): n is the capacity K */);
-
-// Last pass of the tile partition: writes point_list and ranges instead of the sorted items (scan_sort.hip, ScatterFinal).
-// `edge`: 3 * 256 * (gsr_radix_blocks(n) + 1) int32 of scratch.
-hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
-                                       int id_shift, int32_t *point_list, int32_t *ranges /* pre-zeroed */, int32_t *edge, hipStream_t s,
-                                       bool hist_ready = false, const int32_t *low_totals = nullptr /* narrowed items: the first pass's digit totals */,
-                                       int low_bits = 0 /* ... and digit width */, const int32_t *d_count = nullptr /* capacity mode: n is K */);
-
-// Tile items are (tile << id_shift | gaussian id): uint64 with id_shift = 32, or uint32 when tile bits + id bits <= 32.
-// The expansion (scan_sort.hip): one prefix per 256 depth-sorted Gaussians (into ws.scan_tmp; also clears the
-// ranges, the first partition pass's accumulators and the block-order header), then one workgroup per radix block of the output,
-// which also leaves the first partition pass's histograms (launch that pass with hist_ready).
+// ---- the tile partition: the D (tile, Gaussian) pairs, expanded in depth order, stably partitioned by tile id ----
+// Its plan, from the Gaussian count and the tile count (scan_sort.hip gsr_tile_plan).  Tile items are (tile << id_shift | id):
+// uint32 with id_shift = id_bits when tile bits + id bits fit a word, else uint64 with id_shift = 32.  The partition takes
+// ceil(tile_bits / 8) passes whose digits split the tile bits as evenly as possible (12 -> 6 + 6, 13 -> 7 + 6).
+struct TilePlan {
+    int tile_bits, id_bits;
+    int item_bytes, id_shift;
+    int npass;
+    int bits[4];    // digit width of each pass (4..8), lowest tile bits first
+    bool narrowing; // two passes over 64-bit items whose first pass writes 32-bit ones (scan_sort.hip ScatterFinal)
+};
+TilePlan gsr_tile_plan(int64_t N, int tiles);
+// The binning workspace (gsr_binning_workspace_bytes): carved by api.hip, used by the expansion and the partition.
+struct BinWs {
+    int32_t *hist;       // [nb][256]
+    int32_t *acc[2];     // [gsr_radix_acc_ints(D)] each: see GeomWs::acc
+    int32_t *edge;       // [3 * 256 * nb] first tile / last tile / position of every (digit, block) run of the last pass
+    uint64_t *tile_a;    // [D]
+    uint64_t *tile_b;    // [D]
+    size_t bytes;
+};
+// The expansion (scan_sort.hip): one prefix per 256 depth-sorted Gaussians (into ws.scan_tmp; also clears the ranges, the first
+// partition pass's accumulators bw.acc[0] and the block-order header), then one workgroup per radix block of the D items in
+// bw.tile_a, which also leaves the first partition pass's histograms.
+hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *ranges, int ranges_n, int32_t *zero_acc, int zero_n, int32_t *zero_b,
+                                          int zero_b_n, int bo_flag, hipStream_t s);
+hipError_t gsr_launch_expand_blocks(const TilePlan &plan, const GeomWs &ws, const BinWs &bw, int64_t n, int grid_x, int64_t D, const int32_t *d_count,
+                                    hipStream_t s);
+// The partition passes behind the expansion; the last one writes point_list and ranges (pre-zeroed) instead of sorted items.
+// `D`: the item count, or the capacity K with d_count (capacity mode, above).
+hipError_t gsr_launch_tile_partition(const TilePlan &plan, const BinWs &bw, int32_t *point_list, int32_t *ranges, int64_t D, const int32_t *d_count,
+                                     hipStream_t s);
 // ---- forward tile order (round 4) ----
 // The forward blend's 2 500 workgroups at 800 x 800 run on 2 048 workgroup slots: the 452 that start when the first slots free up
 // decide when the kernel ends (they start at 0.4 of its span and live half of it).  An oracle experiment (tools/residency.py
@@ -180,10 +194,6 @@ hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *a
 // workspace dispatches the tiles by cost class, heaviest first (fwd_order, made by a spare workgroup of preprocess_kernel
 // every frame from whatever fwd_cost holds -- garbage in a fresh workspace gives some permutation, never a wrong one).  Execution
 // order only: every tile computes what it always did.  Not for images of more than GSR_FO_MAX_TILES tiles (many rounds, no tail).
-hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *ranges, int ranges_n, int32_t *zero_acc, int zero_n, int32_t *zero_b,
-                                          int zero_b_n, int bo_flag, hipStream_t s);
-hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t n, int grid_x, int64_t D, int id_shift, int item_bytes, int bits0,
-                                    int32_t *hist, int32_t *acc, hipStream_t s, const int32_t *d_count = nullptr /* capacity mode: D is K */);
 // ---- block order (GsrBinning.block_order): the backward blend's 8x4-pixel blocks, heaviest first ---------------------------
 // The backward's waves live 40-90 us of a 165-us kernel, so what starts last decides when the kernel ends.  How many list
 // entries the backward's compaction will keep for a block (mask hits up to the block's last contributor) is the one cheap

@@ -18,6 +18,8 @@
 // SLOWER on MI355X -- depth sort 0.196 vs 0.093 ms, tile sort 0.187 vs 0.131 ms at C3 -- because every
 // look-back hop is a ~1-3 us memory-side round trip and all chunks run in lockstep; see DESIGN.md.)
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 
 #include "gsr_internal.h"
 
@@ -140,7 +142,7 @@ __device__ __forceinline__ DepthCtl depth_ctl_load(const DepthCtlRaw *__restrict
 // visible one) and its visible count.  Workgroup k of K reduces its share of the blocks (at most 2048 when K < 16: one round of
 // loads per thread -- as ONE workgroup this was ten dependent rounds at 5 M Gaussians, 16 us that the whole launch waited for)
 // and adds it to DepthCtlRaw; its extremes also go to the pinned host words 2 + 2k, 3 + 2k (the host's launch guess for the next
-// frame: api.hip).
+// frame: gsr_depth_passes_needed).
 __device__ __forceinline__ void depth_ctl_from_blocks(const uint32_t *__restrict__ blk_minmax, int nblk, DepthCtlRaw *__restrict__ raw, int k, int K,
                                                       int32_t *host_words)
 {
@@ -1215,29 +1217,14 @@ __global__ __launch_bounds__(1024) void depth_sort_small_kernel(const uint64_t *
 
 } // namespace
 
-hipError_t gsr_launch_scan(const int32_t *in, const uint64_t *items, int32_t *out, int32_t *block_tmp, int64_t n, int mode,
-                           int32_t *total_out, bool sums_per_256_ready, hipStream_t s, const uint32_t *blk_minmax, void *depth_ctl)
-{
-    if (n <= 0) return hipSuccess;
-    const int nw = (int)gsr_div_up(n, GSR_SCAN_WAVE_ITEMS); // wave-sized units; block_tmp holds one sum per unit
-    const int nb = (nw + 3) / 4;
-    (void)items;
-    DepthCtlRaw *ctl = (DepthCtlRaw *)depth_ctl; // only the id-order scan behind preprocess is asked to fill it (one workgroup here)
-    const int nblk = (int)gsr_div_up(n, 256);
-    if (mode == 0 && sums_per_256_ready) { // block_tmp already holds one sum per 256 items (preprocess.hip)
-        hipLaunchKernelGGL((scan_final_kernel<0, 4>), dim3(nb + (ctl ? 1 : 0)), dim3(256), 0, s, in, block_tmp, out, n, total_out, blk_minmax, nblk, ctl);
-    } else if (mode == 0) {
-        hipLaunchKernelGGL(scan_reduce_kernel<0>, dim3(nb), dim3(256), 0, s, in, block_tmp, n);
-        hipLaunchKernelGGL((scan_final_kernel<0, 1>), dim3(nb + (ctl ? 1 : 0)), dim3(256), 0, s, in, block_tmp, out, n, total_out, blk_minmax, nblk, ctl);
-    } else if (mode == 2) {
-        hipLaunchKernelGGL(scan_reduce_kernel<2>, dim3(nb), dim3(256), 0, s, in, block_tmp, n);
-        hipLaunchKernelGGL((scan_final_kernel<2, 1>), dim3(nb), dim3(256), 0, s, in, block_tmp, out, n, total_out, (const uint32_t *)nullptr, 0,
-                           (DepthCtlRaw *)nullptr);
-    } else {
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-}
+// ---------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------
+// how many workgroups of the id-order scan's launch reduce the per-block depth extremes (2048 blocks each, at most 16: one round of
+// loads per thread); workgroup k leaves its extremes in the pinned host words 2 + 2k, 3 + 2k (depth_ctl_from_blocks)
+static int depth_ctl_wgs(int64_t n) { return (int)std::min<int64_t>(16, std::max<int64_t>(1, (gsr_div_up(n, 256) + 2047) / 2048)); }
+
+bool gsr_small_depth_path(int64_t n) { return n <= GSR_SMALL_SORT_N && !(gsr_debug_flags & 1024); } // GSR_DEBUG bit 10: never (tests)
 
 // chunk size and super-block size of a pass over n items (gsr_internal.h: gsr_radix_blocks, gsr_radix_sb)
 struct PassGeom {
@@ -1255,181 +1242,198 @@ static PassGeom pass_geom(int64_t n)
     g.prefixed = g.nb > GSR_RADIX_PREFIX_NB || (gsr_debug_flags & 128); // GSR_DEBUG bit 7: at any block count (tests)
     return g;
 }
-
-template <int BITS, typename ItemT, bool CARRY, bool FINAL, bool DEPTH = false, bool LOWREC = false, bool PACKCAP = false>
-static void radix_pass_launch(const ItemT *in, ItemT *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int32_t *zero_acc, int zero_n,
-                              const ScatterCarry &carry, const ScatterFinal &fin, hipStream_t s, const DepthPass &dp = DepthPass{}, bool hist_ready = false,
-                              const int32_t *d_count = nullptr)
+// the kernel shapes of a tier: items per block, and threads per scatter workgroup (histograms always take 256)
+template <int TIER> struct TierShape {
+    static constexpr int CHUNK = TIER == 0 ? GSR_RADIX_TINY_CHUNK : TIER == 1 ? GSR_RADIX_SMALL_CHUNK : GSR_RADIX_CHUNK;
+    static constexpr int WG = TIER == 0 ? 256 : TIER == 1 ? GSR_RADIX_SMALL_WG : GSR_RADIX_WG;
+};
+// f(std::integral_constant<int, TIER>{}) for a runtime tier
+template <class F> static void with_tier(int tier, F &&f)
 {
+    if (tier == 0) f(std::integral_constant<int, 0>{});
+    else if (tier == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 2>{});
+}
+
+// One stable radix pass: the histogram kernel (unless `hist_ready`: the kernel that produced `in` left this pass's block
+// histograms and super-block sums), the super-block scan of a many-block pass, the scatter and, for the final tile pass, the
+// range fix-up.  `acc`: this pass's accumulators (zero when its first kernel runs); `zero_acc`: the next pass's, which the scatter
+// clears.  With d_count (capacity mode, tile passes only) the same launches are sized from the capacity n = K and take the
+// kernels that read the real count.
+template <int BITS, typename ItemT, bool CARRY, bool FINAL, bool DEPTH, bool LOWREC, bool PACKCAP>
+static void radix_pass_launch(const ItemT *in, ItemT *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int32_t *zero_acc, int zero_n,
+                              const ScatterCarry &carry, const ScatterFinal &fin, const DepthPass &dp, bool hist_ready, const int32_t *d_count,
+                              hipStream_t s)
+{
+    constexpr bool CAN_CAP = !CARRY && !DEPTH && !PACKCAP;
     const PassGeom g = pass_geom(n);
-    if constexpr (!CARRY && !DEPTH && !PACKCAP) {
-        if (d_count) { // capacity mode: the same launches, sized from the capacity n = K; the kernels read the real count
+    with_tier(g.tier, [&](auto tier) {
+        using T = TierShape<decltype(tier)::value>;
+        constexpr int HIST_ITEMS = T::CHUNK / 256, ITEMS = T::CHUNK / T::WG;
+        const dim3 grid(g.nb);
+        if (hist_ready) {
+        } else if (CAN_CAP && d_count) {
+            if constexpr (CAN_CAP) hipLaunchKernelGGL((radix_hist_cap_kernel<HIST_ITEMS, BITS, ItemT>), grid, dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
+        } else {
+            hipLaunchKernelGGL((radix_hist_kernel<HIST_ITEMS, BITS, ItemT, DEPTH>), grid, dim3(256), 0, s, in, hist, acc, n, shift, g.sb, dp);
+        }
+        // (a skipped depth pass leaves its accumulator rows zero, as does a block past the items in capacity mode: the super-block
+        // scan then scans zeros)
+        if (g.prefixed) hipLaunchKernelGGL(radix_superscan_kernel, dim3(4), dim3(1024), 0, s, acc, (g.nb + g.sb - 1) / g.sb, dp);
+        if (CAN_CAP && d_count) {
             DepthPass cdp{};
             cdp.count = d_count;
-            if (hist_ready) {
-            } else if (g.tier == 0) {
-                hipLaunchKernelGGL((radix_hist_cap_kernel<GSR_RADIX_TINY_CHUNK / 256, BITS, ItemT>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
-            } else if (g.tier == 1) {
-                hipLaunchKernelGGL((radix_hist_cap_kernel<GSR_RADIX_SMALL_CHUNK / 256, BITS, ItemT>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
-            } else {
-                hipLaunchKernelGGL((radix_hist_cap_kernel<GSR_RADIX_CHUNK / 256, BITS, ItemT>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, d_count);
-            }
-            // (the super-block scan needs no count: the rows of super-blocks past the items were cleared and nothing added to them)
-            if (g.prefixed) hipLaunchKernelGGL(radix_superscan_kernel, dim3(4), dim3(1024), 0, s, acc, (g.nb + g.sb - 1) / g.sb, dp);
-            if (g.tier == 0) {
-                hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_TINY_CHUNK / 256, BITS, ItemT, false, FINAL, false, 256, LOWREC, false, true>), dim3(g.nb), dim3(256), 0, s, in, out, hist, acc, n,
-                                   shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, ScatterCarry{}, fin, cdp);
-            } else if (g.tier == 1) {
-                hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_SMALL_CHUNK / GSR_RADIX_SMALL_WG, BITS, ItemT, false, FINAL, false, GSR_RADIX_SMALL_WG, LOWREC, false, true>), dim3(g.nb),
-                                   dim3(GSR_RADIX_SMALL_WG), 0, s, in, out, hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, ScatterCarry{}, fin, cdp);
-            } else {
-                hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_CHUNK / GSR_RADIX_WG, BITS, ItemT, false, FINAL, false, GSR_RADIX_WG, LOWREC, false, true>), dim3(g.nb), dim3(GSR_RADIX_WG), 0, s,
-                                   in, out, hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, ScatterCarry{}, fin, cdp);
-            }
-            if constexpr (FINAL) // (empty runs of blocks past the items are marked by those blocks: the fix-up walks all g.nb)
-                hipLaunchKernelGGL(ranges_fixup_kernel, dim3(1 << BITS), dim3(1024), 0, s, fin.edge_first, fin.edge_last, fin.edge_pos, acc, g.nb, 1 << BITS,
-                                   fin.ranges);
-            return;
+            if constexpr (CAN_CAP)
+                hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, BITS, ItemT, false, FINAL, false, T::WG, LOWREC, false, true>), grid, dim3(T::WG), 0, s, in, out,
+                                   hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, carry, fin, cdp);
+        } else {
+            hipLaunchKernelGGL((radix_scatter_kernel<ITEMS, BITS, ItemT, CARRY, FINAL, DEPTH, T::WG, LOWREC, PACKCAP>), grid, dim3(T::WG), 0, s, in, out, hist,
+                               acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, carry, fin, dp);
         }
-    }
-    // (a skipped depth pass leaves its accumulator rows zero: the super-block scan of a many-block pass then scans zeros)
-    // hist_ready: the kernel that produced `in` left this pass's block histograms and super-block sums (expand_blocks_kernel)
-    if (hist_ready) {
-    } else if (g.tier == 0) {
-        hipLaunchKernelGGL((radix_hist_kernel<GSR_RADIX_TINY_CHUNK / 256, BITS, ItemT, DEPTH>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, dp);
-    } else if (g.tier == 1) {
-        hipLaunchKernelGGL((radix_hist_kernel<GSR_RADIX_SMALL_CHUNK / 256, BITS, ItemT, DEPTH>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, dp);
-    } else {
-        hipLaunchKernelGGL((radix_hist_kernel<GSR_RADIX_CHUNK / 256, BITS, ItemT, DEPTH>), dim3(g.nb), dim3(256), 0, s, in, hist, acc, n, shift, g.sb, dp);
-    }
-    if (g.prefixed) hipLaunchKernelGGL(radix_superscan_kernel, dim3(4), dim3(1024), 0, s, acc, (g.nb + g.sb - 1) / g.sb, dp);
-    if (g.tier == 0) {
-        hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_TINY_CHUNK / 256, BITS, ItemT, CARRY, FINAL, DEPTH, 256, LOWREC, PACKCAP>), dim3(g.nb), dim3(256), 0, s, in, out, hist, acc, n, shift,
-                           g.nb, g.sb, g.prefixed, zero_acc, zero_n, carry, fin, dp);
-    } else if (g.tier == 1) {
-        hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_SMALL_CHUNK / GSR_RADIX_SMALL_WG, BITS, ItemT, CARRY, FINAL, DEPTH, GSR_RADIX_SMALL_WG, LOWREC, PACKCAP>), dim3(g.nb), dim3(GSR_RADIX_SMALL_WG),
-                           0, s, in, out, hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, carry, fin, dp);
-    } else {
-        hipLaunchKernelGGL((radix_scatter_kernel<GSR_RADIX_CHUNK / GSR_RADIX_WG, BITS, ItemT, CARRY, FINAL, DEPTH, GSR_RADIX_WG, LOWREC, PACKCAP>), dim3(g.nb), dim3(GSR_RADIX_WG), 0, s, in, out,
-                           hist, acc, n, shift, g.nb, g.sb, g.prefixed, zero_acc, zero_n, carry, fin, dp);
-    }
-    if constexpr (FINAL)
+    });
+    if constexpr (FINAL) // (in capacity mode the blocks past the items mark their runs empty: the fix-up walks all g.nb)
         hipLaunchKernelGGL(ranges_fixup_kernel, dim3(1 << BITS), dim3(1024), 0, s, fin.edge_first, fin.edge_last, fin.edge_pos, acc, g.nb, 1 << BITS,
                            fin.ranges);
 }
 
-template <typename ItemT, bool FINAL>
-static hipError_t radix_pass_any(const ItemT *in, ItemT *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int32_t *zero_acc,
-                                 int zero_n, const ScatterFinal &fin, hipStream_t s, bool hist_ready, const int32_t *d_count)
+// One tile-partition pass on the `bits`-wide digit (4..8) at `shift` over uint32 (item_bytes 4) or uint64 items.  Ranking costs
+// one ballot per digit bit, so passes use the narrowest digits that cover the key.  A final pass over narrowed items
+// (fin.low_bits) also recovers the first pass's digit (ScatterFinal).
+template <bool FINAL>
+static hipError_t tile_pass(int item_bytes, const void *in, void *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int32_t *zero_acc,
+                            const ScatterFinal &fin, const int32_t *d_count, hipStream_t s, bool hist_ready)
 {
-    const ScatterCarry nc{};
-    const DepthPass nd{};
-    if constexpr (FINAL && sizeof(ItemT) == 4) {
-        if (fin.low_bits) { // narrowed items: the kernel that also recovers the first pass's digit (ScatterFinal)
-            switch (bits) {
-            case 4: radix_pass_launch<4, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-            case 5: radix_pass_launch<5, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-            case 6: radix_pass_launch<6, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-            case 7: radix_pass_launch<7, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-            case 8: radix_pass_launch<8, ItemT, false, true, false, true>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-            default: return hipErrorInvalidValue;
+    const int zero_n = zero_acc ? (int)gsr_radix_acc_ints(n) : 0;
+    auto launch = [&](auto item, auto digit) {
+        using ItemT = decltype(item);
+        constexpr int BITS = decltype(digit)::value;
+        const ItemT *src = (const ItemT *)in;
+        if constexpr (FINAL && sizeof(ItemT) == 4) {
+            if (fin.low_bits) {
+                radix_pass_launch<BITS, ItemT, false, true, false, true, false>(src, (ItemT *)out, hist, acc, n, shift, zero_acc, zero_n, ScatterCarry{}, fin,
+                                                                                DepthPass{}, hist_ready, d_count, s);
+                return;
             }
-            return hipGetLastError();
         }
-    }
-    switch (bits) {
-    case 4: radix_pass_launch<4, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-    case 5: radix_pass_launch<5, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-    case 6: radix_pass_launch<6, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-    case 7: radix_pass_launch<7, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-    case 8: radix_pass_launch<8, ItemT, false, FINAL>(in, out, hist, acc, n, shift, zero_acc, zero_n, nc, fin, s, nd, hist_ready, d_count); break;
-    default: return hipErrorInvalidValue;
-    }
+        radix_pass_launch<BITS, ItemT, false, FINAL, false, false, false>(src, (ItemT *)out, hist, acc, n, shift, zero_acc, zero_n, ScatterCarry{}, fin,
+                                                                          DepthPass{}, hist_ready, d_count, s);
+    };
+    auto with_bits = [&](auto item) {
+        switch (bits) {
+        case 4: launch(item, std::integral_constant<int, 4>{}); return true;
+        case 5: launch(item, std::integral_constant<int, 5>{}); return true;
+        case 6: launch(item, std::integral_constant<int, 6>{}); return true;
+        case 7: launch(item, std::integral_constant<int, 7>{}); return true;
+        case 8: launch(item, std::integral_constant<int, 8>{}); return true;
+        default: return false;
+        }
+    };
+    if (!(item_bytes == 4 ? with_bits(uint32_t{}) : with_bits(uint64_t{}))) return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
-// One stable pass on the `bits`-wide digit at `shift` (bits in 4..8).  Ranking costs one ballot per digit bit,
-// so passes use the narrowest digits that cover the key: 6+6 bits for the 12-bit tile ids of an 800x800 image.
-// item_bytes: 8 (uint64 items) or 4 (uint32 items: tile id and Gaussian id share one word when they fit).
-// `acc`: this pass's accumulators (gsr_radix_acc_ints(n) ints, zero when the pass's first kernel runs); `zero_acc`: the
-// accumulators of the NEXT pass over the same n, cleared by this pass's scatter (or NULL).
-hipError_t gsr_launch_radix_pass(const void *in, void *out, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
-                                 int32_t *zero_acc, hipStream_t s, bool hist_ready, int narrow_id_bits, int32_t *totals_out, const int32_t *d_count)
+TilePlan gsr_tile_plan(int64_t N, int tiles)
 {
-    if (n <= 0) return hipSuccess;
-    const int zero_n = zero_acc ? (int)gsr_radix_acc_ints(n) : 0;
-    ScatterFinal opt{};
-    opt.narrow_id_bits = item_bytes == 8 ? narrow_id_bits : 0; // 64-bit items in, 32-bit items out (see ScatterFinal)
-    opt.totals = opt.narrow_id_bits ? totals_out : nullptr;
-    if (item_bytes == 4)
-        return radix_pass_any<uint32_t, false>((const uint32_t *)in, (uint32_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready, d_count);
-    return radix_pass_any<uint64_t, false>((const uint64_t *)in, (uint64_t *)out, hist, acc, n, shift, bits, zero_acc, zero_n, opt, s, hist_ready, d_count);
+    TilePlan p;
+    p.tile_bits = 1;
+    while ((1LL << p.tile_bits) < tiles) ++p.tile_bits;
+    p.id_bits = 1;
+    while ((1LL << p.id_bits) < N) ++p.id_bits;
+    // 32-bit items when tile and id bits fit one word (800x800 with 1M Gaussians: 12 + 20): that halves the traffic of the
+    // expansion and of every partition pass
+    const bool narrow = p.tile_bits + p.id_bits <= 32 && !(gsr_debug_flags & 32); // GSR_DEBUG bit 5: 64-bit tile items at any size (tests)
+    p.id_shift = narrow ? p.id_bits : 32;
+    p.item_bytes = narrow ? 4 : 8;
+    p.npass = (p.tile_bits + 7) / 8;
+    for (int pass = 0, shift = 0; pass < 4; ++pass) {
+        const int left = p.npass - pass;
+        p.bits[pass] = left > 0 ? std::max(4, (p.tile_bits - shift + left - 1) / left) : 0;
+        shift += p.bits[pass];
+    }
+    // Two passes over 64-bit items whose remaining tile bits + id bits fit a word after the first one (1080p with 5 M Gaussians:
+    // 6 + 23): the first pass writes 32-bit items and the second recovers the first digit from the item's position -- 4 instead
+    // of 8 bytes per item through the second histogram and the final scatter.
+    p.narrowing = !narrow && p.npass == 2 && (p.tile_bits - p.bits[0]) + p.id_bits <= 32 && !(gsr_debug_flags & 4096); // GSR_DEBUG bit 12: never (tests)
+    return p;
 }
 
-// The LAST pass of the tile partition: histogram, then a scatter that writes point_list and the in-sight range boundaries
-// directly (ScatterFinal), and the edge fix-up.  `edge` holds 3 * (1 << bits) * nb int32 (gsr_radix_blocks(n) = nb).
-hipError_t gsr_launch_radix_final_pass(const void *in, int32_t *hist, int32_t *acc, int64_t n, int shift, int bits, int item_bytes,
-                                       int id_shift, int32_t *point_list, int32_t *ranges, int32_t *edge, hipStream_t s, bool hist_ready,
-                                       const int32_t *low_totals, int low_bits, const int32_t *d_count)
+// The id-order scan (scan_final_kernel<0, 4> over the sums per 256 Gaussians that preprocess left) with the depth sort's pass plan
+// in one launch: on the small-scene path one extra workgroup derives DepthCtl; otherwise scan_ctl_hist_kernel, whose control
+// workgroups derive it and whose remaining workgroups make the first active depth pass's histogram.
+hipError_t gsr_launch_id_scan(const int32_t *tiles_touched, int32_t *point_offsets, const GeomWs &ws, int64_t n, int32_t *host_words, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    const size_t per = ((size_t)1 << bits) * (size_t)gsr_radix_blocks(n);
-    const ScatterFinal fin{point_list, ranges, edge, edge + per, edge + 2 * per, acc, id_shift, 0, low_totals, low_totals ? low_bits : 0};
-    if (item_bytes == 4)
-        return radix_pass_any<uint32_t, true>((const uint32_t *)in, (uint32_t *)nullptr, hist, acc, n, shift, bits, nullptr, 0, fin, s, hist_ready, d_count);
-    return radix_pass_any<uint64_t, true>((const uint64_t *)in, (uint64_t *)nullptr, hist, acc, n, shift, bits, nullptr, 0, fin, s, hist_ready, d_count);
-}
-
-// The id-order scan of tiles_touched into point_offsets (D to the pinned host word), the depth sort's pass plan and the first
-// active depth pass's histogram, one launch (scan_ctl_hist_kernel).  Not for the small-scene path (gsr_small_depth_path).
-hipError_t gsr_launch_scan_ctl_hist(const int32_t *tiles_touched, int32_t *point_offsets, const GeomWs &ws, int64_t n, int32_t *total_out, hipStream_t s)
-{
-    if (n <= 0) return hipSuccess;
-    const int nb_scan = ((int)gsr_div_up(n, GSR_SCAN_WAVE_ITEMS) + 3) / 4, nblk = (int)gsr_div_up(n, 256), n_ctl = gsr_depth_ctl_wgs(n);
-    const PassGeom g = pass_geom(n);
+    const int nb_scan = ((int)gsr_div_up(n, GSR_SCAN_WAVE_ITEMS) + 3) / 4, nblk = (int)gsr_div_up(n, 256);
     DepthCtlRaw *ctl = (DepthCtlRaw *)ws.depth_ctl;
-#define GSR_SCH(CH)                                                                                                                                    \
-    hipLaunchKernelGGL((scan_ctl_hist_kernel<(CH) / 256>), dim3(nb_scan + n_ctl + g.nb), dim3(256), 0, s, tiles_touched, ws.scan_tmp, point_offsets, n, \
-                       total_out, ws.blk_minmax, nblk, ctl, n_ctl, nb_scan, ws.depth_item, ws.hist, ws.acc_first, g.sb)
-    if (g.tier == 0) GSR_SCH(GSR_RADIX_TINY_CHUNK);
-    else if (g.tier == 1) GSR_SCH(GSR_RADIX_SMALL_CHUNK);
-    else GSR_SCH(GSR_RADIX_CHUNK);
-#undef GSR_SCH
+    if (gsr_small_depth_path(n)) {
+        hipLaunchKernelGGL((scan_final_kernel<0, 4>), dim3(nb_scan + 1), dim3(256), 0, s, tiles_touched, ws.scan_tmp, point_offsets, n, host_words, ws.blk_minmax,
+                           nblk, ctl);
+        return hipGetLastError();
+    }
+    const int n_ctl = depth_ctl_wgs(n);
+    const PassGeom g = pass_geom(n);
+    with_tier(g.tier, [&](auto tier) {
+        hipLaunchKernelGGL((scan_ctl_hist_kernel<TierShape<decltype(tier)::value>::CHUNK / 256>), dim3(nb_scan + n_ctl + g.nb), dim3(256), 0, s, tiles_touched,
+                           ws.scan_tmp, point_offsets, n, host_words, ws.blk_minmax, nblk, ctl, n_ctl, nb_scan, ws.depth_item, ws.hist, ws.acc_first, g.sb);
+    });
+    return hipGetLastError();
+}
+
+int gsr_depth_passes_needed(const int32_t *host_words, int64_t n)
+{
+    if (gsr_small_depth_path(n)) return 4;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    for (int k = 0, K = depth_ctl_wgs(n); k < K; ++k) {
+        lo = std::min(lo, (uint32_t)host_words[2 + 2 * k]);
+        hi = std::max(hi, (uint32_t)host_words[3 + 2 * k]);
+    }
+    return gsr_depth_plan(lo, hi, (gsr_debug_flags & 256) ? 4 : 0).npass;
+}
+
+hipError_t gsr_launch_exclusive_scan(const int32_t *in, int32_t *out, int32_t *block_tmp, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    const int nb = ((int)gsr_div_up(n, GSR_SCAN_WAVE_ITEMS) + 3) / 4; // four wave-sized units per workgroup; block_tmp holds one sum per unit
+    hipLaunchKernelGGL(scan_reduce_kernel<2>, dim3(nb), dim3(256), 0, s, in, block_tmp, n);
+    hipLaunchKernelGGL((scan_final_kernel<2, 1>), dim3(nb), dim3(256), 0, s, in, block_tmp, out, n, (int32_t *)nullptr, (const uint32_t *)nullptr, 0,
+                       (DepthCtlRaw *)nullptr);
     return hipGetLastError();
 }
 
 // The depth sort: Gaussians by depth bits, stable from id order.  Four 8-bit passes over the 64-bit (depth bits << 32 | id) items
-// are launched; how many of them this frame's depth range needs is decided on the device (DepthCtl, filled by the id-order scan),
-// the others return at once.  The last pass writes, instead of the sorted items, what the rest of the pipeline reads: the ids,
-// and each Gaussian's tile rectangle and tile count carried to its sorted position.
-bool gsr_small_depth_path(int64_t n) { return n <= GSR_SMALL_SORT_N && !(gsr_debug_flags & 1024); } // GSR_DEBUG bit 10: never (tests)
-
-hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, hipStream_t s, int launch_passes, int pack_ok)
+// exist; the host launches the last `launch_passes` of them, and how many this frame's depth range needs is decided on the device
+// (DepthCtl, filled by the id-order scan): the others return at once.  The last pass writes, instead of the sorted items, what the
+// rest of the pipeline reads: the ids, and each Gaussian's tile rectangle and tile count carried to its sorted position.
+hipError_t gsr_launch_depth_sort(const GeomWs &ws, int64_t n, int grid_x, int grid_y, int launch_passes, hipStream_t s)
 {
     if (n <= 0) return hipSuccess;
-    launch_passes = std::min(4, std::max(1, launch_passes));
     if (gsr_small_depth_path(n)) { // sorts and carries in one workgroup
         hipLaunchKernelGGL(depth_sort_small_kernel, dim3(1), dim3(1024), 0, s, ws.depth_item, (int)n, ws.rect, ws.id_sorted, ws.rect_sorted,
                            ws.cnt_sorted);
         return hipGetLastError();
     }
+    // packed depth items (above): the tile grid at 6 bits per coordinate, the ids in 24.  GSR_DEBUG bit 11: never (tests)
+    const int pack_ok = (!(gsr_debug_flags & 2048) && grid_x <= 63 && grid_y <= 63 && n <= (1 << 24)) ? 1 : 0;
+    launch_passes = std::min(4, std::max(1, launch_passes));
     const int zero_n = (int)gsr_radix_acc_ints(n);
     const ScatterCarry carry{ws.rect, ws.rect_sorted, ws.cnt_sorted, ws.id_sorted, n};
     for (int pass = 4 - launch_passes; pass < 4; ++pass) {
         const DepthPass dp{{(const DepthCtlRaw *)ws.depth_ctl}, (gsr_debug_flags & 256) ? 4 : 0, pass, {ws.depth_item, ws.sort_tmp}, ws.acc_first, 4 - launch_passes, pack_ok};
         // pass p accumulates into acc[p & 1] (both cleared by preprocess) and clears the other one for pass p + 1 -- except the
-        // first ACTIVE pass, whose histogram and sums were made beside the id-order scan (gsr_launch_scan_ctl_hist) in acc_first.
+        // first ACTIVE pass, whose histogram and sums were made beside the id-order scan (gsr_launch_id_scan) in acc_first.
         // The first LAUNCHED pass is either skipped by the plan or the first active one: its histogram kernel is not launched.
         const bool no_hist = pass == 4 - launch_passes;
+        int32_t *acc = ws.acc[pass & 1], *next = ws.acc[(pass + 1) & 1];
         if (pass < 3 && pack_ok)
-            radix_pass_launch<8, uint64_t, false, false, true, false, true>(ws.depth_item, ws.sort_tmp, ws.hist, ws.acc[pass & 1], n, 0, ws.acc[(pass + 1) & 1], zero_n,
-                                                                            carry /* (its rect array: the pass that packs the items reads it) */, ScatterFinal{}, s, dp, no_hist);
+            radix_pass_launch<8, uint64_t, false, false, true, false, true>(ws.depth_item, ws.sort_tmp, ws.hist, acc, n, 0, next, zero_n,
+                                                                            carry /* (its rect array: the pass that packs the items reads it) */, ScatterFinal{},
+                                                                            dp, no_hist, nullptr, s);
         else if (pass < 3)
-            radix_pass_launch<8, uint64_t, false, false, true>(ws.depth_item, ws.sort_tmp, ws.hist, ws.acc[pass & 1], n, 0, ws.acc[(pass + 1) & 1], zero_n,
-                                                               ScatterCarry{}, ScatterFinal{}, s, dp, no_hist);
+            radix_pass_launch<8, uint64_t, false, false, true, false, false>(ws.depth_item, ws.sort_tmp, ws.hist, acc, n, 0, next, zero_n, ScatterCarry{},
+                                                                             ScatterFinal{}, dp, no_hist, nullptr, s);
         else
-            radix_pass_launch<8, uint64_t, true, false, true>(ws.depth_item, ws.sort_tmp, ws.hist, ws.acc[pass & 1], n, 0, nullptr, 0, carry, ScatterFinal{}, s, dp,
-                                                              no_hist);
+            radix_pass_launch<8, uint64_t, true, false, true, false, false>(ws.depth_item, ws.sort_tmp, ws.hist, acc, n, 0, nullptr, 0, carry, ScatterFinal{},
+                                                                            dp, no_hist, nullptr, s);
     }
     return hipGetLastError();
 }
@@ -1444,28 +1448,63 @@ hipError_t gsr_launch_depth_block_offsets(const GeomWs &ws, int64_t n, int32_t *
                        ranges_n, zero_acc, zero_n, zero_b, zero_b_n, bo_flag);
     return hipGetLastError();
 }
-// `bits0`: the digit width of the first partition pass over the D items (its digit = the low bits0 bits of the tile id); `hist`,
-// `acc`: that pass's block histograms and (zeroed) accumulators, which this kernel fills -- launch the pass with hist_ready.
-hipError_t gsr_launch_expand_blocks(const GeomWs &ws, void *tile_items, int64_t n, int grid_x, int64_t D, int id_shift, int item_bytes, int bits0,
-                                    int32_t *hist, int32_t *acc, hipStream_t s, const int32_t *d_count)
+// The D items go to bw.tile_a; the kernel also fills the first partition pass's block histograms (bw.hist) and its zeroed
+// accumulators (bw.acc[0]) for that pass's digit, the low plan.bits[0] bits of the tile id: the pass then needs no histogram kernel.
+hipError_t gsr_launch_expand_blocks(const TilePlan &plan, const GeomWs &ws, const BinWs &bw, int64_t n, int grid_x, int64_t D, const int32_t *d_count,
+                                    hipStream_t s)
 {
     if (n <= 0 || D <= 0) return hipSuccess;
     const PassGeom g = pass_geom(D);
-    const int chunk = g.chunk, nsum = (int)gsr_div_up(n, 256);
-    if (d_count) { // capacity mode: D is the capacity K (the grid), the kernel reads the real count
-        if (item_bytes == 4)
-            hipLaunchKernelGGL(expand_blocks_cap_kernel<uint32_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted,
-                               (uint32_t *)tile_items, n, grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb, d_count);
+    const int nsum = (int)gsr_div_up(n, 256), digit_mask = (1 << plan.bits[0]) - 1;
+    auto launch = [&](auto *items) {
+        using ItemT = std::remove_pointer_t<decltype(items)>;
+        if (d_count) // capacity mode: D is the capacity K (the grid), the kernel reads the real count
+            hipLaunchKernelGGL(expand_blocks_cap_kernel<ItemT>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted,
+                               items, n, grid_x, D, plan.id_shift, g.chunk, digit_mask, bw.hist, bw.acc[0], g.sb, d_count);
         else
-            hipLaunchKernelGGL(expand_blocks_cap_kernel<uint64_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted,
-                               (uint64_t *)tile_items, n, grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb, d_count);
-        return hipGetLastError();
-    }
-    if (item_bytes == 4)
-        hipLaunchKernelGGL(expand_blocks_kernel<uint32_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted, (uint32_t *)tile_items, n,
-                           grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb);
-    else
-        hipLaunchKernelGGL(expand_blocks_kernel<uint64_t>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted, (uint64_t *)tile_items, n,
-                           grid_x, D, id_shift, chunk, (1 << bits0) - 1, hist, acc, g.sb);
+            hipLaunchKernelGGL(expand_blocks_kernel<ItemT>, dim3(g.nb), dim3(256), 0, s, ws.id_sorted, ws.cnt_sorted, ws.scan_tmp, ws.sum4096, nsum, ws.rect_sorted,
+                               items, n, grid_x, D, plan.id_shift, g.chunk, digit_mask, bw.hist, bw.acc[0], g.sb);
+    };
+    if (plan.item_bytes == 4) launch((uint32_t *)bw.tile_a);
+    else launch(bw.tile_a);
     return hipGetLastError();
+}
+
+// The stable partition of the D items by tile id, plan.npass passes ping-ponging between bw.tile_a and bw.tile_b.  Pass p
+// accumulates into bw.acc[p & 1] and its scatter clears the other for pass p + 1; the first pass's histograms come from the
+// expansion.  The last pass writes point_list and the tile ranges itself (reference forward.py:806-824, :561-586) instead of
+// sorted items that a further kernel would re-read; its edge table is bw.edge.
+hipError_t gsr_launch_tile_partition(const TilePlan &plan, const BinWs &bw, int32_t *point_list, int32_t *ranges, int64_t D, const int32_t *d_count,
+                                     hipStream_t s)
+{
+    if (D <= 0) return hipSuccess;
+    void *src = bw.tile_a, *dst = bw.tile_b;
+    for (int pass = 0, shift = 0; pass < plan.npass; ++pass) {
+        const int bits = plan.bits[pass];
+        int32_t *acc = bw.acc[pass & 1], *next = bw.acc[(pass + 1) & 1];
+        hipError_t e;
+        if (pass + 1 < plan.npass) {
+            ScatterFinal opt{};
+            if (plan.narrowing) { // 64-bit items in, 32-bit items out, and the digit totals left for the final pass (see ScatterFinal)
+                opt.narrow_id_bits = plan.id_bits;
+                opt.totals = acc;
+            }
+            e = tile_pass<false>(plan.item_bytes, src, dst, bw.hist, acc, D, plan.id_shift + shift, bits, next, opt, d_count, s, pass == 0);
+        } else {
+            const size_t per = ((size_t)1 << bits) * (size_t)gsr_radix_blocks(D);
+            ScatterFinal fin{point_list, ranges, bw.edge, bw.edge + per, bw.edge + 2 * per, acc, plan.id_shift, 0, nullptr, 0};
+            if (plan.narrowing) { // the items are (tile >> bits[0]) << id_bits | id, the first pass's digit totals in `next`
+                fin.id_shift = plan.id_bits;
+                fin.low_totals = next;
+                fin.low_bits = plan.bits[0];
+                e = tile_pass<true>(4, src, nullptr, bw.hist, acc, D, plan.id_bits, bits, nullptr, fin, d_count, s, false);
+            } else {
+                e = tile_pass<true>(plan.item_bytes, src, nullptr, bw.hist, acc, D, plan.id_shift + shift, bits, nullptr, fin, d_count, s, pass == 0);
+            }
+        }
+        if (e != hipSuccess) return e;
+        shift += bits;
+        std::swap(src, dst);
+    }
+    return hipSuccess;
 }

@@ -251,6 +251,10 @@ def test_alignment_and_capacity_are_checked_before_any_hip_call(libpath):
     binning, img = _lib.GsrBinning(100, A, A, None), _lib.GsrImage(A, A, A, A)
     rc = L.gsr_forward_render(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), A, 1 << 30, A, 1 << 30, None)
     assert rc == _lib.GSR_E_CAPACITY and "count" in _lib.strerror(rc)
+    for pairs in (0, 100):      # an unaligned backward_ws is refused before anything is enqueued, with and without pairs
+        bad = _lib.GsrBinning(pairs, A, A, None, None, A + 4, 0)
+        rc = L.gsr_forward_render(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(bad), C.byref(img), A, 1 << 30, A, 1 << 30, None)
+        assert rc == _lib.GSR_E_ALIGN, (pairs, rc)
     grads = _lib.GsrGrads(A, A, A + 4, A, A, A, A, A, None)
     rc = L.gsr_backward_geom(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), A, 1 << 30, None)
     assert rc == _lib.GSR_E_ALIGN
