@@ -112,6 +112,23 @@ LOSS_EXPORTS = {
 }
 SSIM_WINDOWS = {"reference": 0, "gaussian": 1}   # GSR_SSIM_WINDOW_REFERENCE / GSR_SSIM_WINDOW_GAUSSIAN
 
+
+class GsrPixelGrads(C.Structure):
+    _fields_ = [("dL_dpixels", vp), ("dL_dinv_depth", vp), ("dL_dalpha", vp)]
+
+
+# include/gsr_aux_grads.h: the backward through the inverse-depth and alpha images, and their losses (its own header, so its own table)
+AUX_EXPORTS = {
+    "gsr_backward_aux": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                   C.POINTER(GsrImage), C.POINTER(GsrPixelGrads), C.POINTER(GsrGrads), vp, vp, C.c_size_t, vp]),
+    "gsr_backward_blend_aux": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                         C.POINTER(GsrImage), C.POINTER(GsrPixelGrads), vp, vp, C.c_size_t, vp]),
+    "gsr_backward_geom_aux": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrGrads), vp, vp,
+                                        C.c_size_t, vp]),
+    "gsr_depth_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp]),
+    "gsr_alpha_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp]),
+}
+
 STAGES = ["preprocess", "scan", "depth_sort", "host_gap", "depth_scan", "expand", "tile_sort", "ranges", "blend_fwd",
           "bwd_prep", "blend_bwd", "geom_bwd"]
 
@@ -126,7 +143,7 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(hipcc --offload-arch=gfx950).  There is no fallback path.")
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items()):
+        for name, (res, args) in list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items()) + list(AUX_EXPORTS.items()):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

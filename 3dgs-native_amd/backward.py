@@ -12,6 +12,11 @@ payload (`_view_payload`: N rows, then the camera position); `_arena` is then th
 and `dL_dshs` is None until `dist.sh_gradients_from_views` rebuilds it from all views' payloads ("both" returns the dense
 arena and the payload of the same call).  `on_payload(payload)` is called as soon as the payload is complete -- after the
 blend half, before the per-Gaussian half -- so an exchange can start early (dist.FactoredExchange).
+
+Two more keywords (include/gsr_aux_grads.h): `dL_ddepth_image` and `dL_dalpha_image`, (H, W) gradients with respect to the
+forward's inverse-depth image (img_buffer "depth_image") and its alpha image 1 - final_Ts.  With either, the call runs the
+auxiliary backward (dL_dpixels may then be None), and the result has one more key, `dL_dinv_depths`: dL/d(1/depth) per
+Gaussian, an (N,) strided view of the accumulator records.  With neither, the call is exactly the one above.
 """
 import ctypes as C
 
@@ -46,9 +51,13 @@ def _get(buf, key):
 def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=None, rotations=None, scale_modifier=1.0,
              viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256, campos=None,
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
-             binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None):
+             binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
+             dL_ddepth_image=None, dL_dalpha_image=None):
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
+    aux = dL_ddepth_image is not None or dL_dalpha_image is not None
+    if dL_dpixels is None and not aux:
+        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image")
     factored = sh_gradient == "factored"
     from . import forward as _forward
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
@@ -58,7 +67,9 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     f32, i32 = torch.float32, torch.int32
     means = _host.to_dev(means3D, f32, dev, (-1, 3))
     N = means.shape[0]
-    dpix = _host.to_dev(dL_dpixels, f32, dev, (H, W, 3))
+    dpix = _host.to_dev(dL_dpixels, f32, dev, (H, W, 3)) if dL_dpixels is not None else None
+    g_depth = _host.to_dev(dL_ddepth_image, f32, dev, (H, W)) if dL_ddepth_image is not None else None
+    g_alpha = _host.to_dev(dL_dalpha_image, f32, dev, (H, W)) if dL_dalpha_image is not None else None
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
     rot = _host.to_dev(rotations, f32, dev, (-1, 4))
@@ -141,7 +152,12 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
 
     scene = _lib.GsrScene(N, _host.ptr(means), _host.ptr(sc), _host.ptr(rot), _host.ptr(op), _host.ptr(sh), int(degree),
                           float(scale_modifier), 1)
-    geom = _lib.GsrGeom(_host.ptr(radii), None, None, _host.ptr(m2d), None, _host.ptr(c3), _host.ptr(col), _host.ptr(con),
+    depths = None
+    if g_depth is not None and records is None:
+        # the re-packed records carry 1/depth only from the forward's depths (gsr_aux_grads.h: without them, GSR_E_NULL)
+        depths = geom_buffer.get("depths") if geom_buffer is not None else None
+        depths = _host.to_dev(depths, f32, dev, (-1,)) if depths is not None else None
+    geom = _lib.GsrGeom(_host.ptr(radii), None, None, _host.ptr(m2d), _host.ptr(depths), _host.ptr(c3), _host.ptr(col), _host.ptr(con),
                         _host.ptr(cl), _host.ptr(records), _host.ptr(sh_dir))
     if masks is not None and not (isinstance(masks, torch.Tensor) and masks.dtype == torch.uint8 and masks.device == dev
                                   and masks.numel() == D and masks.is_contiguous()):
@@ -193,7 +209,19 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         binning = _lib.GsrBinning(D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(masks), _host.ptr(order),
                                   _host.ptr(ws) if cleared else None, 1 if cleared else 0)
         backward.last_call_skipped_the_clear = cleared     # for tests and debugging
-        if on_payload is not None and payload is not None:
+        if aux:
+            pg = _lib.GsrPixelGrads(_host.ptr(dpix), _host.ptr(g_depth), _host.ptr(g_alpha))
+            if on_payload is not None and payload is not None:
+                _lib.check(L.gsr_backward_blend_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
+                                                    _host.ptr(payload), _host.ptr(ws), ws.numel(), stream))
+                on_payload(payload)
+                grads.dL_drgb = None
+                _lib.check(L.gsr_backward_geom_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), None, _host.ptr(ws),
+                                                   ws.numel(), stream))
+            else:
+                _lib.check(L.gsr_backward_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
+                                              C.byref(grads), None, _host.ptr(ws), ws.numel(), stream))
+        elif on_payload is not None and payload is not None:
             # two halves: the view payload is complete after the blend half, so the caller's hook can start its exchange
             # (an asynchronous all-gather) while the per-Gaussian half still runs
             _lib.check(L.gsr_backward_blend(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(dpix),
@@ -204,10 +232,13 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         else:
             _lib.check(L.gsr_backward(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(dpix),
                                       C.byref(grads), _host.ptr(ws), ws.numel(), stream))
-    return {
+    out = {
         "dL_dmean3D": dL_dmean3D, "dL_dcolor": dL_dcolor, "dL_dshs": dL_dsh, "dL_dopacity": dL_dopacity,
         "dL_dscale": dL_dscale, "dL_drot": dL_drot, "dL_dmean2D": dL_dmean2D, "dL_dconic": dL_dconic,
         "dL_dcov3D": _zeros_cov3d(N, dev),
         "_arena": arena,
         "_view_payload": payload,
     }
+    if aux:
+        out["dL_dinv_depths"] = acc[:, 11]      # GradRec slot 11 (gsr_gradrec_slot(9)): dL/d(1/depth) per Gaussian
+    return out

@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "gsr_aux_grads.h"
 #include "gsr_capacity.h"
 #include "gsr_internal.h"
 
@@ -523,17 +524,22 @@ int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const G
     return enqueue_render(scene, cam, geom, binning, image, gw, carve_bin(bin_ws, K), geom->point_offsets + (N - 1), shape_hint, s, st);
 }
 
-// first half: accumulator clear, record (re)pack, blend backward, optional view payload
+// first half: accumulator clear, record (re)pack, blend backward, optional view payload.  `aux` (include/gsr_aux_grads.h): the
+// AUX blend kernels with the inverse-depth and alpha gradients dL_dinvd / dL_dA; dL_dpixels may then be NULL, and the records
+// must carry 1/depth when dL_dinvd is given.
 static int backward_blend_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
-                               const GsrImage *image, const float *dL_dpixels, float *payload, void *ws, size_t ws_bytes, hipStream_t s, int st)
+                               const GsrImage *image, const float *dL_dpixels, float *payload, void *ws, size_t ws_bytes, hipStream_t s, int st,
+                               bool aux = false, const float *dL_dinvd = nullptr, const float *dL_dA = nullptr)
 {
     const int64_t N = scene->N;
     if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // (cov3D may be NULL: gsr.h GsrGeom)
     if (!geom->blend_records && (!geom->xy || !geom->rgb || !geom->conic_opacity)) return GSR_E_NULL; // the records, or what they are rebuilt from
-    if (!binning || !image || !dL_dpixels) return GSR_E_NULL;
+    if (!binning || !image || (!dL_dpixels && !(aux && (dL_dinvd || dL_dA)))) return GSR_E_NULL;
+    if (dL_dinvd && !geom->blend_records && !geom->depths) return GSR_E_NULL; // a re-pack without depths would carry invd = 0
     if (!geom_aligned(geom) || !gsr_aligned16(ws) || !gsr_aligned16(binning->point_list) || !gsr_aligned16(binning->ranges) ||
         !gsr_aligned16(binning->block_masks) || !gsr_aligned16(binning->block_order) ||
-        !gsr_aligned16(image->final_T) || !gsr_aligned16(image->n_contrib) || !gsr_aligned16(dL_dpixels) || !gsr_aligned16(payload))
+        !gsr_aligned16(image->final_T) || !gsr_aligned16(image->n_contrib) || !gsr_aligned16(dL_dpixels) || !gsr_aligned16(payload) ||
+        !gsr_aligned16(dL_dinvd) || !gsr_aligned16(dL_dA))
         return GSR_E_ALIGN;
     const int64_t D = binning->D;
     if (D < 0 || D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
@@ -551,7 +557,8 @@ static int backward_blend_impl(const GsrScene *scene, const GsrCamera *camera, c
     }
     mark(st, 11, s);
     if (D > 0) HIP_TRY(gsr_launch_blend_backward_splat(cam, binning->ranges, binning->point_list, records, *image, dL_dpixels, binning->block_masks,
-                                                       binning->block_masks ? binning->block_order : nullptr, bw.acc, N, D, s));
+                                                       binning->block_masks ? binning->block_order : nullptr, bw.acc, N, D, s, aux,
+                                                       dL_dinvd, dL_dA));
     mark(st, 12, s);
     if (payload) HIP_TRY(gsr_launch_view_payload(*scene, cam, *geom, bw.acc, payload, s));
     return GSR_OK;
@@ -559,18 +566,21 @@ static int backward_blend_impl(const GsrScene *scene, const GsrCamera *camera, c
 
 // second half: the four per-Gaussian kernels of backward_preprocess, fused
 static int backward_geom_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, void *ws,
-                              size_t ws_bytes, hipStream_t s, int st)
+                              size_t ws_bytes, hipStream_t s, int st, bool aux = false, float *dL_dinv_depths = nullptr)
 {
     const int64_t N = scene->N;
     // dL_dshs and dL_drgb may both be NULL here: the payload was taken from the blend half and the SH gradient is rebuilt later
     // (dL_dcolor / dL_dmean2D / dL_dconic may each be NULL: they are columns of the accumulator records in `ws`, gsr.h GsrGrads)
     if (!grads || !grads->dL_dmean3D || !grads->dL_dscale || !grads->dL_drot || !grads->dL_dopacity) return GSR_E_NULL;
     if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // cov3D NULL: recomputed from scales / rotations (gsr.h GsrGeom)
-    if (!geom_aligned(geom) || !grads_aligned(grads) || !gsr_aligned16(ws)) return GSR_E_ALIGN;
+    if (!geom_aligned(geom) || !grads_aligned(grads) || !gsr_aligned16(ws) || !gsr_aligned16(dL_dinv_depths)) return GSR_E_ALIGN;
     if (!ws || ws_bytes < gsr_backward_workspace_bytes(N, 0, camera->W, camera->H)) return GSR_E_WORKSPACE;
     const CamK cam = make_cam(camera);
     const BwdWs bw = carve_bwd(ws, N);
-    HIP_TRY(gsr_launch_geom_backward(*scene, cam, *geom, bw.acc, *grads, s));
+    HIP_TRY(gsr_launch_geom_backward(*scene, cam, *geom, bw.acc, *grads, s, aux));
+    if (dL_dinv_depths) // column 11 of the accumulator records (gsr_gradrec_slot(9)), packed
+        HIP_TRY(hipMemcpy2DAsync(dL_dinv_depths, sizeof(float), &bw.acc[0].f[gsr_gradrec_slot(9)], sizeof(GradRec), sizeof(float), (size_t)N,
+                                 hipMemcpyDeviceToDevice, s));
     mark(st, 13, s);
     return GSR_OK;
 }
@@ -610,6 +620,53 @@ int gsr_backward_geom(const GsrScene *scene, const GsrCamera *camera, const GsrG
     const int st = t_bwd_record;
     t_bwd_record = -1;
     return backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, (hipStream_t)stream, st);
+}
+
+// ---- include/gsr_aux_grads.h: the backward through the inverse-depth and alpha images ----
+// Every argument of both halves is checked before the blend half enqueues anything.  With neither auxiliary gradient (and no
+// dL_dinv_depths) the call is gsr_backward's own: the same kernels, bit for bit.
+int gsr_backward_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                     const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, void *stream)
+{
+    read_tuning();
+    if (int rc = check_scene_cam(scene, camera)) return rc;
+    if (scene->N == 0) return GSR_OK;
+    if (!pixel_grads) return GSR_E_NULL;
+    if (!grads || !grads->dL_dmean3D || !grads->dL_dscale || !grads->dL_drot || !grads->dL_dopacity || (!grads->dL_dshs && !grads->dL_drgb))
+        return GSR_E_NULL;
+    if (!grads_aligned(grads) || !gsr_aligned16(dL_dinv_depths)) return GSR_E_ALIGN; // (the geom half's one check the blend half lacks)
+    const bool aux = pixel_grads->dL_dinv_depth || pixel_grads->dL_dalpha;
+    hipStream_t s = (hipStream_t)stream;
+    const int st = timer_open(false);
+    if (int rc = backward_blend_impl(scene, camera, geom, binning, image, pixel_grads->dL_dpixels, nullptr, ws, ws_bytes, s, st, aux,
+                                     pixel_grads->dL_dinv_depth, pixel_grads->dL_dalpha))
+        return rc;
+    if (int rc = backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, s, st, aux || dL_dinv_depths, dL_dinv_depths)) return rc;
+    return GSR_OK;
+}
+
+int gsr_backward_blend_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                           const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, void *stream)
+{
+    read_tuning();
+    if (int rc = check_scene_cam(scene, camera)) return rc;
+    if (scene->N == 0) return GSR_OK;
+    if (!pixel_grads) return GSR_E_NULL;
+    t_bwd_record = timer_open(false);
+    return backward_blend_impl(scene, camera, geom, binning, image, pixel_grads->dL_dpixels, payload, ws, ws_bytes, (hipStream_t)stream,
+                               t_bwd_record, pixel_grads->dL_dinv_depth || pixel_grads->dL_dalpha, pixel_grads->dL_dinv_depth,
+                               pixel_grads->dL_dalpha);
+}
+
+int gsr_backward_geom_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, float *dL_dinv_depths,
+                          void *ws, size_t ws_bytes, void *stream)
+{
+    read_tuning();
+    if (int rc = check_scene_cam(scene, camera)) return rc;
+    if (scene->N == 0) return GSR_OK;
+    const int st = t_bwd_record;
+    t_bwd_record = -1;
+    return backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, (hipStream_t)stream, st, true, dL_dinv_depths);
 }
 
 int gsr_stage_timing(int enable, int max_steps)

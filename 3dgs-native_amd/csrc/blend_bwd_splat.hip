@@ -222,7 +222,13 @@ constexpr int QCAP = 128;                 // ring of compacted entries (power of
 
 // USE_MASKS: the per-block hit masks the forward wrote (GsrBinning.block_masks) replace the compaction's own test.  They are
 // per 8x4 block; an 8x8 block ORs the bits of its two halves.
-template <int BW, int BH, bool USE_MASKS>
+// AUX (include/gsr_aux_grads.h): the pixel gradient also has an inverse-depth part gD and an alpha part gA (either pointer may
+// be NULL, and so may dL_dpixels).  The inverse depth composites like a fourth colour channel with background 0, and A = 1 - T_final
+// enters where the background does:
+//     cd_k = c_k . dpix + gD invd_k        Q seed = T_final (bg . dpix - gA)        dL/dinvd_k = sum over pixels of alpha_k T_k gD
+// (invd_k = the record's 1/depth, f[9]); the tenth accumulated value goes to GradRec slot 11 (gsr_gradrec_slot(9)).  The AUX =
+// false kernels get nullptr for the two pointers and are the product's machine code unchanged (tools/kernel_disasm_diff.py).
+template <int BW, int BH, bool USE_MASKS, bool AUX = false>
 __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, int grid_x, float bg0, float bg1, float bg2,
                                                                   const int32_t *__restrict__ ranges,
                                                                   const int32_t *__restrict__ point_list,
@@ -231,7 +237,8 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
                                                                   const int32_t *__restrict__ n_contrib,
                                                                   const float *__restrict__ dL_dpixels,
                                                                   const uint8_t *__restrict__ block_masks, GradRec *__restrict__ acc, int dbg, int n_blocks,
-                                                                  const int32_t *__restrict__ block_order, int bo_cap)
+                                                                  const int32_t *__restrict__ block_order, int bo_cap,
+                                                                  const float *__restrict__ dL_dinvd, const float *__restrict__ dL_dA)
 {
     constexpr int NPIX = BW * BH;            // pixels of the block this wave owns
     constexpr int PER_TILE = 256 / NPIX;     // blocks per 16x16 tile
@@ -241,7 +248,9 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
     __shared__ float4 s_pq[NPIX];
     __shared__ float4 s_pb[NPIX];   // dpix r,g,b, kept (as int bits)
     __shared__ int2 s_ring[QCAP];   // compacted survivors: (Gaussian id, list index); records are re-gathered (L2 hits)
-    __shared__ float s_g[64][9];    // per-entry gradients for the transposed flush (odd stride: no bank conflicts)
+    __shared__ float s_pd[NPIX];    // AUX: gD of each pixel (unreferenced, hence not allocated, otherwise)
+    constexpr int NG = AUX ? 10 : 9; // accumulated values per entry
+    __shared__ float s_g[64][AUX ? 11 : 9]; // per-entry gradients for the transposed flush (odd stride: no bank conflicts)
     __shared__ int s_id[64];
 
     const int lane = threadIdx.x;
@@ -310,11 +319,21 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             const size_t px = (size_t)my_y * W + my_x;
             Tfin = final_T[px];
             kept = min(end, start + n_contrib[px]);
-            d0 = dL_dpixels[3 * px]; d1 = dL_dpixels[3 * px + 1]; d2 = dL_dpixels[3 * px + 2];
+            if (!AUX || dL_dpixels) { d0 = dL_dpixels[3 * px]; d1 = dL_dpixels[3 * px + 1]; d2 = dL_dpixels[3 * px + 2]; }
         }
         float bgdot = bg0 * d0;
         bgdot += bg1 * d1;
         bgdot += bg2 * d2;
+        if constexpr (AUX) {
+            float gd = 0.0f, ga = 0.0f;
+            if (my_x < W && my_y < H) {
+                const size_t px = (size_t)my_y * W + my_x;
+                if (dL_dinvd) gd = dL_dinvd[px];
+                if (dL_dA) ga = dL_dA[px];
+            }
+            bgdot -= ga;
+            s_pd[lane] = gd;
+        }
         s_pq[lane] = make_float4((float)my_x, (float)my_y, Tfin, Tfin * bgdot);
         s_pb[lane] = make_float4(d0, d1, d2, __int_as_float(kept));
     }
@@ -393,7 +412,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         const bool valid = elane < n;
         const int slot = (head + elane) & (QCAP - 1);
         float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        float colb = 0.0f;
+        float colb = 0.0f, invd = 0.0f;
         int idx = 0x7FFFFFFF, id = 0;
         if (valid) {
             const int2 e = s_ring[slot];
@@ -402,7 +421,13 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             const float4 *rp = reinterpret_cast<const float4 *>(rec + id);
             a = rp[0]; // xy.x xy.y con.a con.b
             b = rp[1]; // con.c opacity r g
-            colb = rp[2].x;
+            if constexpr (AUX) {
+                const float2 bz = *reinterpret_cast<const float2 *>(rp + 2); // b, 1/depth
+                colb = bz.x;
+                invd = bz.y;
+            } else {
+                colb = rp[2].x;
+            }
         }
 #ifdef GSR_TIMELINE
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -418,6 +443,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         //   h = dL/dG * G            S1 = sum h dx      S2 = sum h dy
         //   Sxx = sum h dx^2         Sxy = sum h dx dy  Syy = sum h dy^2      Sop = sum G dL/dalpha
         float g_c0 = 0.f, g_c1 = 0.f, g_c2 = 0.f, S1 = 0.f, S2 = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f, Sop = 0.f;
+        float Sdep = 0.f; // AUX: sum alpha T gD
         bool touched = false;
         const float ca2 = -0.5f * a.z, cb2 = -a.w, cc2 = -0.5f * b.x; // exact
 
@@ -433,7 +459,9 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         const float m = live ? inv : 1.0f;                                                                                    \
         const float Pi = SCAN_MUL(m);                                                                                         \
         const float T = pq.z * Pi; /* transmittance in front of this entry = T_final / prod(1-alpha) over it and all deeper */ \
-        const float cd = b.z * pb.x + b.w * pb.y + colb * pb.z;                                                               \
+        float cd = b.z * pb.x + b.w * pb.y + colb * pb.z;                                                                     \
+        float pd = 0.0f;                                                                                                      \
+        if constexpr (AUX) { pd = s_pd[Q]; cd += invd * pd; }                                                                 \
         const float w = alpha * T;                                                                                            \
         const float qv = live ? w * cd : 0.0f;                                                                                \
         const float Qi = SCAN_ADD(qv);                                                                                        \
@@ -443,6 +471,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             const float Qe = pq.w + (Qi - qv); /* background term + deeper entries only */                                    \
             const float dL_dalpha = T * cd - Qe * inv;                                                                        \
             g_c0 += w * pb.x; g_c1 += w * pb.y; g_c2 += w * pb.z;                                                             \
+            if constexpr (AUX) Sdep += w * pd;                                                                                \
             const float gd = G * dL_dalpha;                                                                                   \
             Sop += gd;                                                                                                        \
             const float h = b.y * gd; /* dL/dG * G = o * dL/dalpha * G */                                                     \
@@ -468,6 +497,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             // an entry's sums are split over its four lanes (one per row): add them up (rows 1-3 then hold copies and stay out of the flush)
 #define GSR_SUM4(v) v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
             GSR_SUM4(g_c0) GSR_SUM4(g_c1) GSR_SUM4(g_c2) GSR_SUM4(S1) GSR_SUM4(S2) GSR_SUM4(Sxx) GSR_SUM4(Sxy) GSR_SUM4(Syy) GSR_SUM4(Sop)
+            if constexpr (AUX) { GSR_SUM4(Sdep) }
 #undef GSR_SUM4
             int t4 = (int)touched;
             t4 |= __shfl_xor(t4, 16, 64);
@@ -502,6 +532,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             S1 += __shfl_xor(S1, 32, 64); S2 += __shfl_xor(S2, 32, 64);
             Sxx += __shfl_xor(Sxx, 32, 64); Sxy += __shfl_xor(Sxy, 32, 64); Syy += __shfl_xor(Syy, 32, 64);
             Sop += __shfl_xor(Sop, 32, 64);
+            if constexpr (AUX) Sdep += __shfl_xor(Sdep, 32, 64);
             const int partner_touched = __shfl_xor((int)touched, 32, 64); // unconditionally: a cross-lane read must not sit behind ||
             touched = (touched || partner_touched != 0) && lane < 32;
         }
@@ -516,6 +547,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         s_id[lane] = touched ? id : -1;
         s_g[lane][0] = g_c0; s_g[lane][1] = g_c1; s_g[lane][2] = g_c2; s_g[lane][3] = g_mx; s_g[lane][4] = g_my;
         s_g[lane][5] = g_ca; s_g[lane][6] = g_cb; s_g[lane][7] = g_cc; s_g[lane][8] = g_op;
+        if constexpr (AUX) s_g[lane][9] = Sdep;
         __syncthreads();
         const int c = lane & 15, fslot = gsr_gradrec_slot(c); // the record's layout leaves the API arrays' zero columns free
         const int flush_rows = (n + 3) >> 2; // four entries per wave instruction; entries beyond n have nothing
@@ -523,7 +555,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         for (int r = 0; r < flush_rows; ++r) {
             const int e = r * 4 + (lane >> 4);
             const int eid = s_id[e];
-            if (c < 9 && eid >= 0 && !GSR_ABL(dbg, 1)) unsafeAtomicAdd(&acc[eid].f[fslot], s_g[e][c]);
+            if (c < NG && eid >= 0 && !GSR_ABL(dbg, 1)) unsafeAtomicAdd(&acc[eid].f[fslot], s_g[e][c]);
         }
         __syncthreads();
         TL(4) // flush
@@ -588,7 +620,8 @@ int gsr_debug_flags = 0; // see gsr_internal.h
 
 hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *ranges, const int32_t *point_list, const BlendRec *rec,
                                            const GsrImage &img, const float *dL_dpixels, const uint8_t *block_masks,
-                                           const int32_t *block_order, GradRec *acc, int64_t N, int64_t D, hipStream_t s)
+                                           const int32_t *block_order, GradRec *acc, int64_t N, int64_t D, hipStream_t s, bool aux,
+                                           const float *dL_dinvd, const float *dL_dA)
 {
     const int tiles = cam.grid_x * cam.grid_y;
     if (tiles <= 0) return hipSuccess;
@@ -597,9 +630,15 @@ hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *range
         const int nblk = tiles * (256 / ((BW) * (BH)));                                                                       \
         const int32_t *bo = ((M) && (BH) == 4) ? block_order : nullptr; /* 8x4 blocks only */                                 \
         const int grid = bo ? 8 * 8 * gsr_bo_tiles_per_band(tiles) : 8 * ((nblk + 7) / 8);                                   \
-        hipLaunchKernelGGL((blend_backward_splat_kernel<BW, BH, M>), dim3(grid), dim3(64), 0, s, cam.W, cam.H, cam.grid_x,    \
-                           cam.bg[0], cam.bg[1], cam.bg[2], ranges, point_list, rec, img.final_T, img.n_contrib, dL_dpixels,  \
-                           block_masks, acc, gsr_debug_flags, nblk, bo, gsr_bo_cap(tiles));                                   \
+        if (aux)                                                                                                              \
+            hipLaunchKernelGGL((blend_backward_splat_kernel<BW, BH, M, true>), dim3(grid), dim3(64), 0, s, cam.W, cam.H,     \
+                               cam.grid_x, cam.bg[0], cam.bg[1], cam.bg[2], ranges, point_list, rec, img.final_T,             \
+                               img.n_contrib, dL_dpixels, block_masks, acc, gsr_debug_flags, nblk, bo, gsr_bo_cap(tiles),     \
+                               dL_dinvd, dL_dA);                                                                              \
+        else                                                                                                                  \
+            hipLaunchKernelGGL((blend_backward_splat_kernel<BW, BH, M>), dim3(grid), dim3(64), 0, s, cam.W, cam.H, cam.grid_x, \
+                               cam.bg[0], cam.bg[1], cam.bg[2], ranges, point_list, rec, img.final_T, img.n_contrib,          \
+                               dL_dpixels, block_masks, acc, gsr_debug_flags, nblk, bo, gsr_bo_cap(tiles), nullptr, nullptr); \
     } while (0)
     // Pixels per wave.  The block masks discard an entry for a whole block, so small splats (few tile pairs per Gaussian) want the
     // finer 8x4 blocks; splats that cover their tiles anyway want 8x8, which stages every entry in half as many waves.  Measured

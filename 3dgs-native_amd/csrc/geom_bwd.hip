@@ -59,7 +59,11 @@ __device__ __forceinline__ float dot3(const float a[3], const float b[3])
 // forms from the 48 coefficients (GsrGeom.sh_dir_grad, written by preprocess_kernel with these very expressions).  The kernel
 // then does not read the SH array at all: 36 instead of 192 bytes per Gaussian in, 48 fewer staging registers; the LDS image
 // only transposes the OUTPUT rows.  Without it (a caller that kept no forward state) the coefficients are read as before.
-template <bool DIRGRAD>
+// AUX (include/gsr_aux_grads.h): the blend backward also left dL/dinvd in GradRec slot 11 (invd = 1 / z, z = the view depth
+// preprocess stores in `depths`, t[2] below).  Its true derivative, -dL/dinvd / z^2 * dz/dmean with dz/dmean_k = view[4k + 2], is
+// added to dL_dmean3D beside the reference's dt transform (so without quirk Q3's view[j][3] term).  The AUX = false kernels are
+// the product's machine code unchanged (tools/kernel_disasm_diff.py).
+template <bool DIRGRAD, bool AUX = false>
 __global__ __launch_bounds__(256) void geom_backward_kernel(
     int64_t N, const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ rots,
     const float *__restrict__ shs, int degree, CamK cam, float h_x, float h_y, const int32_t *__restrict__ radii,
@@ -207,6 +211,11 @@ __global__ __launch_bounds__(256) void geom_backward_kernel(
                 r += cam.view[j * 4 + 2] * dt[2];
                 r += cam.view[j * 4 + 3] * dt[3];
                 o_mean[j] += r;
+            }
+            if constexpr (AUX) {
+                const float g_z = -inv_tz2 * a2.w; // dL/dz = dL/dinvd * d(1/z)/dz
+#pragma unroll
+                for (int j = 0; j < 3; ++j) o_mean[j] += cam.view[4 * j + 2] * g_z;
             }
         }
         // ---------------- projection backward (backward.py:709-768) ----------------
@@ -412,18 +421,24 @@ __global__ __launch_bounds__(256) void sh_grad_from_views_kernel(int64_t N, cons
 } // namespace
 
 hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, const GsrGrads &gr,
-                                    hipStream_t s)
+                                    hipStream_t s, bool aux)
 {
     if (sc.N <= 0) return hipSuccess;
     // focal lengths come from the host, formed in float64 and rounded once (reference backward.py:1044-1045, quirk Q8)
     const float h_x = cam.focal_x, h_y = cam.focal_y;
-#define GEOM_BWD(DG)                                                                                                          \
-    hipLaunchKernelGGL(geom_backward_kernel<DG>, dim3((unsigned)gsr_div_up(sc.N, 256)), dim3(256), 0, s, sc.N, sc.means, sc.scales, \
-                       sc.rotations, sc.sh, sc.sh_degree, cam, h_x, h_y, g.radii, g.cov3D, g.clamped_state, acc, gr.dL_dmean3D,  \
-                       gr.dL_dscale, gr.dL_drot, gr.dL_dopacity, gr.dL_dshs, gr.dL_dcolor, gr.dL_dmean2D, gr.dL_dconic, gr.dL_drgb, \
-                       g.sh_dir_grad, sc.scale_modifier)
-    if (g.sh_dir_grad) GEOM_BWD(true);
+#define GEOM_ARGS                                                                                                             \
+    dim3((unsigned)gsr_div_up(sc.N, 256)), dim3(256), 0, s, sc.N, sc.means, sc.scales, sc.rotations, sc.sh, sc.sh_degree, cam, h_x, \
+        h_y, g.radii, g.cov3D, g.clamped_state, acc, gr.dL_dmean3D, gr.dL_dscale, gr.dL_drot, gr.dL_dopacity, gr.dL_dshs,    \
+        gr.dL_dcolor, gr.dL_dmean2D, gr.dL_dconic, gr.dL_drgb, g.sh_dir_grad, sc.scale_modifier
+#define GEOM_BWD(DG) hipLaunchKernelGGL(geom_backward_kernel<DG>, GEOM_ARGS)
+#define GEOM_BWD_AUX(DG) hipLaunchKernelGGL((geom_backward_kernel<DG, true>), GEOM_ARGS)
+    if (aux) {
+        if (g.sh_dir_grad) GEOM_BWD_AUX(true);
+        else GEOM_BWD_AUX(false);
+    } else if (g.sh_dir_grad) GEOM_BWD(true);
     else GEOM_BWD(false);
+#undef GEOM_BWD_AUX
+#undef GEOM_ARGS
 #undef GEOM_BWD
     return hipGetLastError();
 }

@@ -256,9 +256,12 @@ hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *range
                                            const BlendRec *rec, const GsrImage &img, const float *dL_dpixels,
                                            const uint8_t *block_masks /* optional: the forward's */,
                                            const int32_t *block_order /* optional: the forward's, with its masks */, GradRec *acc,
-                                           int64_t N, int64_t D /* choose the block size */, hipStream_t s);
+                                           int64_t N, int64_t D /* choose the block size */, hipStream_t s,
+                                           bool aux = false /* the AUX kernels (include/gsr_aux_grads.h), with: */,
+                                           const float *dL_dinv_depth = nullptr, const float *dL_dalpha = nullptr);
+// aux: the AUX instantiation, which also adds the inverse-depth gradient's z term (GradRec slot 11) into dL_dmean3D
 hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc,
-                                    const GsrGrads &gr, hipStream_t s);
+                                    const GsrGrads &gr, hipStream_t s, bool aux = false);
 
 // tuning knobs (read once from the environment by api.hip; defaults are the measured best)
 hipError_t gsr_launch_view_payload(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *payload, hipStream_t s);

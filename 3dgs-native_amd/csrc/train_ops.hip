@@ -2,6 +2,7 @@
 // (SURVEY.md section 8(f) rows f2 and f3): L1 loss + pixel gradient, and the fused Adam update.
 #include <math.h>
 
+#include "gsr_aux_grads.h"
 #include "gsr_internal.h"
 #include "sh_stage.h"
 
@@ -109,6 +110,28 @@ __global__ __launch_bounds__(256) void depth_loss_kernel(const float *__restrict
     float acc = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         acc += fabsf(rendered[i] - target[i]) * mask[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
+    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+}
+
+// ---- include/gsr_aux_grads.h: masked L1 of the inverse-depth image (ALPHA = false) or of the alpha image 1 - final_T (true),
+// with its pixel gradient weight * mask * sign(r - t), sign(0) = +1 as in l1_loss_grad_kernel; mask and grad may be NULL ----
+template <bool ALPHA>
+__global__ __launch_bounds__(256) void aux_l1_loss_grad_kernel(const float *__restrict__ rendered, const float *__restrict__ target,
+                                                               const float *__restrict__ mask, float *__restrict__ grad,
+                                                               float *__restrict__ loss_sum, int64_t n, float weight)
+{
+    __shared__ float s_part[4];
+    float acc = 0.0f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const float r = ALPHA ? 1.0f - rendered[i] : rendered[i];
+        const float d = r - target[i], m = mask ? mask[i] : 1.0f;
+        acc += fabsf(d) * m;
+        if (grad) grad[i] = weight * m * (d < 0.0f ? -1.0f : 1.0f);
+    }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
     if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
@@ -315,6 +338,33 @@ int gsr_depth_loss(const float *rendered_depth, const float *target_depth, const
     hipLaunchKernelGGL(depth_loss_kernel, dim3((unsigned)std::min<int64_t>(1024, gsr_div_up(n, 256))), dim3(256), 0, s, rendered_depth, target_depth,
                        depth_mask, loss_sum, n);
     return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP;
+}
+
+static int aux_l1_loss_grad(bool alpha, const float *r, const float *t, const float *mask, float *grad, float *loss_sum, int32_t W, int32_t H, float weight,
+                            void *stream)
+{
+    if (!r || !t || !loss_sum) return GSR_E_NULL;
+    if (W <= 0 || H <= 0) return GSR_E_DIMS;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = (int64_t)W * H;
+    if (hipMemsetAsync(loss_sum, 0, sizeof(float), s) != hipSuccess) return GSR_E_HIP;
+    // grid stride over at most 512 workgroups: each ends with one atomic on the one loss word (see gsr_l1_loss_grad)
+    const dim3 grid((unsigned)std::min<int64_t>(512, gsr_div_up(n, 256)));
+    if (alpha) hipLaunchKernelGGL(aux_l1_loss_grad_kernel<true>, grid, dim3(256), 0, s, r, t, mask, grad, loss_sum, n, weight);
+    else hipLaunchKernelGGL(aux_l1_loss_grad_kernel<false>, grid, dim3(256), 0, s, r, t, mask, grad, loss_sum, n, weight);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP;
+}
+
+int gsr_depth_loss_grad(const float *rendered, const float *target, const float *mask, float *grad, float *loss_sum, int32_t W, int32_t H,
+                        float weight, void *stream)
+{
+    return aux_l1_loss_grad(false, rendered, target, mask, grad, loss_sum, W, H, weight, stream);
+}
+
+int gsr_alpha_loss_grad(const float *final_T, const float *target_alpha, const float *mask, float *grad, float *loss_sum, int32_t W,
+                        int32_t H, float weight, void *stream)
+{
+    return aux_l1_loss_grad(true, final_T, target_alpha, mask, grad, loss_sum, W, H, weight, stream);
 }
 
 static int adam_impl(const GsrAdam *a, int32_t sh_degree, int32_t V, const float *const *payloads, float scale, void *stream)

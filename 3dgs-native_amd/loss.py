@@ -120,3 +120,35 @@ def depth_loss(rendered_depth, target_depth, depth_mask):
     with _host.on_device(dev):
         _lib.check(L.gsr_depth_loss(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(acc), W, H, _host.stream_ptr(dev)))
     return float(acc.item()) / (W * H)
+
+
+def _aux_l1(entry, rendered, target, mask, weight, want_grad, loss_out):
+    L = _lib.lib()
+    dev = _host.device_of(rendered, target, mask)
+    r = _host.to_dev(rendered, torch.float32, dev)
+    H, W = int(r.shape[0]), int(r.shape[1])
+    r = r.reshape(H, W)
+    t = _host.to_dev(target, torch.float32, dev, (H, W))
+    m = _host.to_dev(mask, torch.float32, dev, (H, W)) if mask is not None else None
+    _slot(loss_out, "loss_out")
+    grad = torch.empty((H, W), dtype=torch.float32, device=dev) if want_grad else None
+    loss_sum = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
+    with _host.on_device(dev):
+        _lib.check(getattr(L, entry)(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(grad), _host.ptr(loss_sum), W, H,
+                                     float(weight) / (W * H), _host.stream_ptr(dev)))
+    return loss_sum, grad
+
+
+def depth_loss_and_gradients(rendered, target, mask, weight=1.0, want_grad=True, loss_out=None):
+    """Masked L1 between inverse-depth images and its gradient, one kernel, no host sync (include/gsr_aux_grads.h).
+    Returns (loss_sum device tensor [1] = sum |rendered - target| * mask, grad (H, W) or None) with
+    grad = weight / (W H) * mask * sign(rendered - target): the gradient of weight * loss_sum / (W H), the reference's depth_loss
+    normalisation (loss.py:271-303).  mask may be None (all ones).  The gradient goes to backward(dL_ddepth_image=...)."""
+    return _aux_l1("gsr_depth_loss_grad", rendered, target, mask, weight, want_grad, loss_out)
+
+
+def alpha_loss_and_gradients(final_Ts, target_alpha, mask=None, weight=1.0, want_grad=True, loss_out=None):
+    """Masked L1 between the alpha image 1 - final_Ts and target_alpha, and its gradient with respect to the alpha image, as
+    depth_loss_and_gradients (normalised by W H).  final_Ts is the forward's img_buffer["final_Ts"]; the gradient goes to
+    backward(dL_dalpha_image=...)."""
+    return _aux_l1("gsr_alpha_loss_grad", final_Ts, target_alpha, mask, weight, want_grad, loss_out)

@@ -12,6 +12,11 @@ train.py:323-334) is used; without it, targets are renders of a hidden seeded sc
 
     python examples/train.py --iterations 200 --gaussians 20000
     python examples/train.py --gpus 8 --views-per-step 8        (launches its own 8 ranks; or under torch.distributed.run)
+
+Depth and alpha supervision (include/gsr_aux_grads.h): --lambda-depth adds lambda_d times the masked L1 of the rendered inverse
+depth (targets: --depth-dir with --dataset, one float32 (H, W) .npy per frame named after its file_path; else the hidden scene's own
+inverse depth; mask = target > 0), --lambda-alpha lambda_a times the L1 of the alpha image 1 - final_T (targets: the PNG alpha,
+or the hidden scene's).  Both terms are normalised by W H, as the reference's depth_loss.
 """
 import argparse
 import importlib
@@ -49,16 +54,25 @@ import torch  # noqa: E402
 gsr = importlib.import_module("3dgs-native_amd")
 
 
-def load_nerf(path, max_views, split="train"):
+def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
+    """(cams, targets), and with alpha=True also the PNGs' alpha channels / 255 as (H, W) float32 (ones for a PNG without one);
+    with depth_dir also the inverse-depth targets, <depth_dir>/<basename of file_path>.npy."""
     from PIL import Image
     with open(os.path.join(path, f"transforms_{split}.json")) as f:
         tf = json.load(f)
-    cams, targets = [], []
+    cams, targets, alphas, depths = [], [], [], []
     for fr in tf["frames"][:max_views]:
         img = np.asarray(Image.open(os.path.join(path, fr["file_path"] + ".png")), dtype=np.float32) / 255.0
         targets.append(img[:, :, :3].copy())
+        alphas.append(img[:, :, 3].copy() if img.ndim == 3 and img.shape[2] == 4 else np.ones(img.shape[:2], np.float32))
+        if depth_dir is not None:
+            d = np.load(os.path.join(depth_dir, os.path.basename(fr["file_path"]) + ".npy")).astype(np.float32)
+            if d.shape != img.shape[:2]:
+                raise ValueError(f"{fr['file_path']}: depth target {d.shape} for a {img.shape[:2]} image")
+            depths.append(d)
         cams.append(gsr.cameras.nerf_camera(fr["transform_matrix"], img.shape[1], img.shape[0], tf["camera_angle_x"]))
-    return cams, targets
+    out = (cams, targets) + ((alphas,) if alpha else ()) + ((depths,) if depth_dir is not None else ())
+    return out
 
 
 def render_view(P, c, bg):
@@ -81,7 +95,25 @@ def score_views(P, cams, targets, bg):
     return rows, images
 
 
-def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None):
+def aux_scores(P, cams, depth_targets, alpha_targets, bg):
+    """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets."""
+    dl, al = [], []
+    for k, c in enumerate(cams):
+        _, dep, buf = gsr.render_gaussians(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
+                                           rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
+                                           tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
+                                           sh=P["shs"], degree=3, campos=c["camera_center"])
+        if depth_targets is not None:
+            t = depth_targets[k]
+            dl.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
+        if alpha_targets is not None:
+            t = alpha_targets[k]
+            al.append(float(gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], t, want_grad=False)[0].item()) / t.numel())
+    return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None)
+
+
+def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
+           alpha_targets=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -93,6 +125,11 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
                "train_psnr_mean": float(np.mean([r["psnr"] for r in rows])), "train_ssim_mean": float(np.mean([r["ssim"] for r in rows]))}
     if args.capacity:
         summary["capacity_retries"] = len(capacity_log)
+    d_l1, a_l1 = aux_scores(P, cams, depth_targets, alpha_targets, bg)
+    if d_l1 is not None:
+        summary["train_depth_l1_mean"] = d_l1
+    if a_l1 is not None:
+        summary["train_alpha_l1_mean"] = a_l1
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
@@ -172,7 +209,16 @@ def main():
                     "standard 3DGS uses 0.2).  0 = L1 alone, the reference trainer's loss")
     ap.add_argument("--ssim-window", default="gaussian", choices=["gaussian", "reference"], help="SSIM window of the D-SSIM term: the "
                     "centred sigma = 1.5 Gaussian of standard 3DGS, or the reference's distance-indexed weights (gsr_ssim)")
+    ap.add_argument("--lambda-depth", type=float, default=0.0, help="weight of the masked inverse-depth L1 (include/gsr_aux_grads.h)")
+    ap.add_argument("--depth-dir", default=None, help="with --dataset: one float32 (H, W) inverse-depth .npy per frame, named after its "
+                    "file_path (without --dataset the hidden scene's own inverse depth is the target)")
+    ap.add_argument("--lambda-alpha", type=float, default=0.0, help="weight of the L1 of the alpha image 1 - final_T against the PNG "
+                    "alpha (or the hidden scene's)")
     args = ap.parse_args()
+    if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
+        raise SystemExit("--lambda-depth and --lambda-alpha must be >= 0")
+    if args.lambda_depth > 0.0 and args.dataset and not args.depth_dir:
+        raise SystemExit("--lambda-depth with --dataset needs --depth-dir (inverse-depth targets)")
     if not 0.0 <= args.lambda_dssim <= 1.0:
         raise SystemExit(f"--lambda-dssim must be in [0, 1], not {args.lambda_dssim}")
     if args.capacity_initial is not None and not (args.capacity and 0 <= args.capacity_initial <= (1 << 30)):
@@ -192,20 +238,27 @@ def main():
         rank, world = gsr.dist.init_from_env(backend=args.backend, device=dev)
 
     bg = np.zeros(3, np.float32)
+    depth_targets = alpha_targets = None
     if args.dataset:
-        cams, targets = load_nerf(args.dataset, args.views)
+        cams, targets, alpha_targets, *dt = load_nerf(args.dataset, args.views, alpha=True, depth_dir=args.depth_dir)
         targets = [torch.as_tensor(t).to(dev) for t in targets]
+        alpha_targets = [torch.as_tensor(t).to(dev) for t in alpha_targets]
+        depth_targets = [torch.as_tensor(t).to(dev) for t in dt[0]] if dt else None
     else:
         cams = [gsr.cameras.nerf_camera(gsr.scenes.orbit_pose(k, args.views), args.size, args.size, gsr.scenes.LEGO_CAMERA_ANGLE_X)
                 for k in range(args.views)]
         hidden = gsr.scenes.synthetic_scene(args.gaussians, 0.05, 0.5, seed=7)
-        targets = []
+        targets, depth_targets, alpha_targets = [], [], []
         for c in cams:
-            img, _, _ = gsr.render_gaussians(background=bg, means3D=hidden["means"], opacity=hidden["opacities"], scales=hidden["scales"],
+            img, dep, hb = gsr.render_gaussians(background=bg, means3D=hidden["means"], opacity=hidden["opacities"], scales=hidden["scales"],
                                              rotations=hidden["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
                                              tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
                                              sh=hidden["shs"], degree=3, campos=c["camera_center"])
             targets.append(img)
+            depth_targets.append(dep.reshape(c["height"], c["width"]).clone())
+            alpha_targets.append((1.0 - hb["final_Ts"].reshape(c["height"], c["width"])).contiguous())
+    depth_masks = [(t > 0).float() for t in depth_targets] if depth_targets is not None else None
+    aux = args.lambda_depth > 0.0 or args.lambda_alpha > 0.0
 
     n = args.gaussians
     if args.init == "reference":
@@ -252,11 +305,11 @@ def main():
                       viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"], tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"],
                       image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"])
             if capacity is None:
-                img, _, buf = gsr.render_gaussians(**kw)
+                img, dep, buf = gsr.render_gaussians(**kw)
                 if args.capacity:
                     sized_D.append(int(buf["point_list"].shape[0]))        # (the sized path's D: what --capacity learns K from)
             else:
-                img, _, buf = gsr.render_gaussians(**kw, capacity=capacity, capacity_hint=cap["D_of"].get(v, cap["max_D"]))
+                img, dep, buf = gsr.render_gaussians(**kw, capacity=capacity, capacity_hint=cap["D_of"].get(v, cap["max_D"]))
             # (one view per rank and step: the L1 sum goes straight into this iteration's slot of the loss curve)
             if dssim:                                                       # ... and the SSIM sum into the SSIM curve's
                 loss_sum, ssim_sum, dpix = gsr.loss.l1_dssim_loss_and_gradients(
@@ -265,13 +318,20 @@ def main():
                 ssim_of[v] = ssim_sum / (c["height"] * c["width"])          # (a re-run of an overflowed view replaces its entry)
             else:
                 loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None)
+            aux_kw = {}
+            if args.lambda_depth > 0.0:                                     # (the curve keeps the colour loss: the terms are in the summary)
+                aux_kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
+            if args.lambda_alpha > 0.0:
+                aux_kw["dL_dalpha_image"] = gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], alpha_targets[v], None, args.lambda_alpha)[1]
+            if aux:                                                         # the forward's depths: records re-packed with 1/depth
+                aux_kw["geom_buffer"] = {"depths": buf["depths"]}
             g = gsr.backward(background=bg, means3D=P["positions"], dL_dpixels=dpix, opacity=P["opacities"], shs=P["shs"], scales=P["scales"],
                              rotations=P["rotations"], viewmatrix=kw["viewmatrix"], projmatrix=kw["projmatrix"], tan_fovx=kw["tan_fovx"],
                              tan_fovy=kw["tan_fovy"], image_height=c["height"], image_width=c["width"], campos=kw["campos"],
                              radii=buf["radii"], means2D=buf["points_xy_image"], conic_opacity=buf["conic_opacity"], rgb=buf["colors"],
                              cov3Ds=buf["cov3Ds"], clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
                              img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
-                             sh_gradient="factored" if factored else "dense")
+                             sh_gradient="factored" if factored else "dense", **aux_kw)
             if capacity is not None:
                 return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"], buf
             return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"]
@@ -371,7 +431,7 @@ def main():
         if dssim:
             ssim_hist /= sum_scale / 3.0                                    # ... and sums of per-pixel SSIM
     if rank == 0:
-        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist)
+        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets)
 
 
 if __name__ == "__main__":

@@ -2,8 +2,9 @@
 """Compare the gfx950 machine code of every kernel symbol in two builds of libgsr_hip.so, symbol by symbol:
     python tools/kernel_disasm_diff.py OLD/libgsr_hip.so NEW/libgsr_hip.so [SYMBOL ...]   (SYMBOL: print that kernel's diff)
 llvm-objdump disassembles each offload bundle; branch targets, comments and inter-function padding are normalised away.
-radix_scatter_kernel gained a trailing template flag CAP (capacity mode, default false): an old instantiation is compared with
-its CAP = false namesake.  Prints the counts and the symbols that differ, were removed or were added (JSON)."""
+radix_scatter_kernel gained a trailing template flag CAP (capacity mode, default false), blend_backward_splat_kernel and
+geom_backward_kernel one named AUX (include/gsr_aux_grads.h, default false; the blend kernel also two trailing pointer
+arguments): an old instantiation is compared with its flag = false namesake.  Prints the counts and the symbols that differ, were removed or were added (JSON)."""
 import glob, os, re, shutil, subprocess, sys, tempfile, json
 OBJ = "/opt/rocm/llvm/bin/llvm-objdump"
 def kernels(so):
@@ -27,16 +28,20 @@ def kernels(so):
     shutil.rmtree(d)
     return {k: "\n".join(v) for k, v in out.items()}
 a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
-# radix_scatter_kernel gained a trailing template flag CAP (default false): map each old instantiation to its CAP=false name
+# kernels that gained a trailing template flag (default false): map each old instantiation to its flag=false name
+FLAGGED = ("radix_scatter_kernelI", "blend_backward_splat_kernelI", "geom_backward_kernelI")
 renamed = {}
 for k in list(a):
-    if k not in b and "radix_scatter_kernelI" in k:
+    if k not in b and any(f in k for f in FLAGGED):
         i = k.index("EEEv")
         nk = k[:i] + "ELb0" + k[i:]
+        if nk not in b:   # the flag may come with trailing arguments (blend_backward_splat_kernel: the AUX pointers)
+            cand = [c for c in b if c not in a and c.startswith(k[:i] + "ELb0EEEv") and c.startswith(nk)]
+            nk = cand[0] if len(cand) == 1 else nk
         if nk in b:
             renamed[k] = nk
             b[k] = b.pop(nk)
-print("renamed (old -> old + CAP=false):", len(renamed))
+print("renamed (old -> old + trailing flag = false):", len(renamed))
 same = [k for k in a if k in b and a[k] == b[k]]
 diff = [k for k in a if k in b and a[k] != b[k]]
 gone = [k for k in a if k not in b]
