@@ -129,6 +129,14 @@ AUX_EXPORTS = {
     "gsr_alpha_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp]),
 }
 
+# include/gsr_camera_grads.h: dL/d(view, proj, campos) after a backward (its own header, so its own table)
+CAMERA_EXPORTS = {
+    "gsr_backward_camera_scratch_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_backward_camera": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), vp, vp, C.c_size_t, vp, C.c_size_t,
+                                      vp]),
+}
+CAMERA_GRAD_FLOATS = 36     # GSR_CAMERA_GRAD_FLOATS: view 0-15 | proj 16-31 | campos 32-34 | 0
+
 STAGES = ["preprocess", "scan", "depth_sort", "host_gap", "depth_scan", "expand", "tile_sort", "ranges", "blend_fwd",
           "bwd_prep", "blend_bwd", "geom_bwd"]
 
@@ -143,7 +151,8 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(hipcc --offload-arch=gfx950).  There is no fallback path.")
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items()) + list(AUX_EXPORTS.items()):
+        for name, (res, args) in (list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items())
+                                  + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

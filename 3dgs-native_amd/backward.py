@@ -17,6 +17,13 @@ Two more keywords (include/gsr_aux_grads.h): `dL_ddepth_image` and `dL_dalpha_im
 forward's inverse-depth image (img_buffer "depth_image") and its alpha image 1 - final_Ts.  With either, the call runs the
 auxiliary backward (dL_dpixels may then be None), and the result has one more key, `dL_dinv_depths`: dL/d(1/depth) per
 Gaussian, an (N,) strided view of the accumulator records.  With neither, the call is exactly the one above.
+
+`camera_grad=True` (include/gsr_camera_grads.h) adds three keys: `dL_dviewmatrix` (4, 4), `dL_dprojmatrix` (4, 4) and
+`dL_dcampos` (3,), float32 device tensors, the true derivative of the forward with respect to `viewmatrix`, `projmatrix` and
+`campos`, each taken as independent, in the row-vector convention p_view = [p, 1] @ viewmatrix.  They are summed by one more
+kernel pair after the backward above, which reads its accumulators and writes nothing else, so every other key is what the
+call with camera_grad=False returns.  The sum is bitwise reproducible for given accumulators.  pose.pose_gradient turns the
+three into the gradient of a per-view pose correction.
 """
 import ctypes as C
 
@@ -52,7 +59,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256, campos=None,
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
-             dL_ddepth_image=None, dL_dalpha_image=None):
+             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False):
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
     aux = dL_ddepth_image is not None or dL_dalpha_image is not None
@@ -232,6 +239,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         else:
             _lib.check(L.gsr_backward(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(dpix),
                                       C.byref(grads), _host.ptr(ws), ws.numel(), stream))
+        if camera_grad:     # after the backward, on the same stream and workspace: reads its accumulators, writes only its own output
+            dcam = torch.empty(_lib.CAMERA_GRAD_FLOATS, dtype=f32, device=dev)
+            scratch = torch.empty(int(L.gsr_backward_camera_scratch_bytes(N)), dtype=torch.uint8, device=dev)
+            _lib.check(L.gsr_backward_camera(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(dcam), _host.ptr(ws), ws.numel(),
+                                             _host.ptr(scratch), scratch.numel(), stream))
     out = {
         "dL_dmean3D": dL_dmean3D, "dL_dcolor": dL_dcolor, "dL_dshs": dL_dsh, "dL_dopacity": dL_dopacity,
         "dL_dscale": dL_dscale, "dL_drot": dL_drot, "dL_dmean2D": dL_dmean2D, "dL_dconic": dL_dconic,
@@ -239,6 +251,8 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         "_arena": arena,
         "_view_payload": payload,
     }
+    if camera_grad:
+        out["dL_dviewmatrix"], out["dL_dprojmatrix"], out["dL_dcampos"] = dcam[0:16].view(4, 4), dcam[16:32].view(4, 4), dcam[32:35]
     if aux:
         out["dL_dinv_depths"] = acc[:, 11]      # GradRec slot 11 (gsr_gradrec_slot(9)): dL/d(1/depth) per Gaussian
     return out

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "gsr_aux_grads.h"
+#include "gsr_camera_grads.h"
 #include "gsr_capacity.h"
 #include "gsr_internal.h"
 
@@ -667,6 +668,30 @@ int gsr_backward_geom_aux(const GsrScene *scene, const GsrCamera *camera, const 
     const int st = t_bwd_record;
     t_bwd_record = -1;
     return backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, (hipStream_t)stream, st, true, dL_dinv_depths);
+}
+
+// ---- include/gsr_camera_grads.h: dL/d(view, proj, campos) from the accumulators a backward left in `ws` ----
+size_t gsr_backward_camera_scratch_bytes(int64_t N) { return gsr_camera_scratch_bytes(N); }
+
+int gsr_backward_camera(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, float *dL_dcamera, const void *ws, size_t ws_bytes,
+                        void *scratch, size_t scratch_bytes, void *stream)
+{
+    read_tuning();
+    if (int rc = check_scene_cam(scene, camera)) return rc;
+    if (!dL_dcamera) return GSR_E_NULL;
+    if (!gsr_aligned16(dL_dcamera) || !gsr_aligned16(ws) || !gsr_aligned16(scratch)) return GSR_E_ALIGN;
+    const int64_t N = scene->N;
+    hipStream_t s = (hipStream_t)stream;
+    if (N > 0) {
+        if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // (cov3D and sh_dir_grad are optional)
+        if (!geom_aligned(geom)) return GSR_E_ALIGN;
+        if (!ws || ws_bytes < gsr_backward_workspace_bytes(N, 0, camera->W, camera->H)) return GSR_E_WORKSPACE;
+        if (!scratch || scratch_bytes < gsr_camera_scratch_bytes(N)) return GSR_E_WORKSPACE;
+    }
+    const CamK cam = make_cam(camera);
+    const GradRec *acc = N > 0 ? carve_bwd(const_cast<void *>(ws), N).acc : nullptr;
+    HIP_TRY(gsr_launch_camera_backward(*scene, cam, N > 0 ? *geom : GsrGeom{}, acc, dL_dcamera, scratch, s));
+    return GSR_OK;
 }
 
 int gsr_stage_timing(int enable, int max_steps)

@@ -265,6 +265,13 @@ hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const G
 
 // tuning knobs (read once from the environment by api.hip; defaults are the measured best)
 hipError_t gsr_launch_view_payload(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *payload, hipStream_t s);
+// camera_bwd.hip (include/gsr_camera_grads.h): dL/d(view, proj, campos) from the accumulators, summed through per-workgroup
+// partial rows in `scratch` (a fixed grid of gsr_camera_blocks(N) workgroups); N = 0 writes zeros
+#define GSR_CAMERA_MAX_BLOCKS 1024
+int gsr_camera_blocks(int64_t N);
+size_t gsr_camera_scratch_bytes(int64_t N);
+hipError_t gsr_launch_camera_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *dL_dcamera, void *scratch,
+                                      hipStream_t s);
 // GSR_DEBUG (environment, read once by api.hip): every bit forces at any size a path that some frame size takes anyway, so the
 // oracle comparison covers it -- same results by other code paths (tests/test_gpu_alt_paths.py):
 //   bit  5 (32)    64-bit tile items (tile bits + id bits > 32)

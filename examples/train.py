@@ -17,6 +17,12 @@ Depth and alpha supervision (include/gsr_aux_grads.h): --lambda-depth adds lambd
 depth (targets: --depth-dir with --dataset, one float32 (H, W) .npy per frame named after its file_path; else the hidden scene's own
 inverse depth; mask = target > 0), --lambda-alpha lambda_a times the L1 of the alpha image 1 - final_T (targets: the PNG alpha,
 or the hidden scene's).  Both terms are normalised by W H, as the reference's depth_loss.
+
+Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
+trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
+35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
+perturb the dataset poses first, for experiments; the --log summary then records the per-view pose error against the dataset
+poses (degrees, scene units) at the start and the end.  One GPU only.
 """
 import argparse
 import importlib
@@ -35,7 +41,11 @@ def _self_launch():
     """`python examples/train.py --gpus N` (no WORLD_SIZE): start the N ranks before anything here touches the GPU."""
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--gpus", type=int, default=1)
-    gpus = ap.parse_known_args()[0].gpus
+    ap.add_argument("--optimize-poses", action="store_true")
+    known = ap.parse_known_args()[0]
+    gpus = known.gpus
+    if known.optimize_poses and gpus > 1:
+        raise SystemExit("--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus")
     if gpus > 1 and "WORLD_SIZE" not in os.environ:
         from importlib import util as _ilu
         spec = _ilu.spec_from_file_location("gsr_launch", os.path.join(ROOT, "3dgs-native_amd", "launch.py"))
@@ -113,7 +123,7 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg):
 
 
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
-           alpha_targets=None):
+           alpha_targets=None, poses=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -125,6 +135,8 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
                "train_psnr_mean": float(np.mean([r["psnr"] for r in rows])), "train_ssim_mean": float(np.mean([r["ssim"] for r in rows]))}
     if args.capacity:
         summary["capacity_retries"] = len(capacity_log)
+    if poses is not None:                                                   # --pose-noise-* / --optimize-poses: error vs the dataset poses
+        summary.update(poses)
     d_l1, a_l1 = aux_scores(P, cams, depth_targets, alpha_targets, bg)
     if d_l1 is not None:
         summary["train_depth_l1_mean"] = d_l1
@@ -214,7 +226,16 @@ def main():
                     "file_path (without --dataset the hidden scene's own inverse depth is the target)")
     ap.add_argument("--lambda-alpha", type=float, default=0.0, help="weight of the L1 of the alpha image 1 - final_T against the PNG "
                     "alpha (or the hidden scene's)")
+    ap.add_argument("--optimize-poses", action="store_true", help="refine each view's pose with Adam on the camera gradients "
+                    "(include/gsr_camera_grads.h; one GPU; reads 35 floats back per view and iteration)")
+    ap.add_argument("--pose-lr", type=float, default=1e-3, help="Adam learning rate of the pose corrections xi = (translation, "
+                    "axis-angle rotation in radians), camera frame (pose.py)")
+    ap.add_argument("--pose-noise-deg", type=float, default=0.0, help="perturb every dataset pose by this rotation (degrees, random axis)")
+    ap.add_argument("--pose-noise-trans", type=float, default=0.0, help="... and this translation (scene units, random direction)")
+    ap.add_argument("--pose-seed", type=int, default=0, help="seed of the pose perturbation")
     args = ap.parse_args()
+    if not args.pose_lr >= 0.0 or not args.pose_noise_deg >= 0.0 or not args.pose_noise_trans >= 0.0:
+        raise SystemExit("--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0")
     if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
         raise SystemExit("--lambda-depth and --lambda-alpha must be >= 0")
     if args.lambda_depth > 0.0 and args.dataset and not args.depth_dir:
@@ -225,6 +246,8 @@ def main():
         raise SystemExit("--capacity-initial needs --capacity and a value in [0, 2^30]")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.optimize_poses and (args.gpus > 1 or world > 1):
+        raise SystemExit("--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus")
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not 1 <= args.views_per_step <= args.views:
@@ -257,6 +280,15 @@ def main():
             targets.append(img)
             depth_targets.append(dep.reshape(c["height"], c["width"]).clone())
             alpha_targets.append((1.0 - hb["final_Ts"].reshape(c["height"], c["width"])).contiguous())
+    # --pose-noise-*: the poses the trainer starts from; the dataset's stay in true_cams for the pose error (the targets are the
+    # dataset's images, or renders of the hidden scene from the dataset poses)
+    true_cams = cams
+    if args.pose_noise_deg > 0.0 or args.pose_noise_trans > 0.0:
+        prng = np.random.default_rng(args.pose_seed)
+        cams = [gsr.pose.apply_pose_delta(c, gsr.pose.random_pose_delta(prng, args.pose_noise_deg, args.pose_noise_trans)) for c in cams]
+    start_cams = cams
+    pose_xi = [np.zeros(6) for _ in cams]                                    # --optimize-poses: each view's correction, its Adam state
+    pose_m, pose_v, pose_t = [np.zeros(6) for _ in cams], [np.zeros(6) for _ in cams], [0] * len(cams)
     depth_masks = [(t > 0).float() for t in depth_targets] if depth_targets is not None else None
     aux = args.lambda_depth > 0.0 or args.lambda_alpha > 0.0
 
@@ -287,6 +319,17 @@ def main():
     # shape hint: the backward's block shape then follows the view's own count, as on the sized path)
     cap = {"K": args.capacity_initial, "n": model.num_points if args.capacity_initial is not None else None, "max_D": 0, "D_of": {}}
     capacity_log, sized_D = [], []
+    def pose_step(v, grad):
+        """One Adam step (beta 0.9 / 0.999, eps 1e-15) on view v's xi; its camera dict is rebuilt for the next render."""
+        pose_t[v] += 1
+        pose_m[v] = 0.9 * pose_m[v] + 0.1 * grad
+        pose_v[v] = 0.999 * pose_v[v] + 0.001 * grad * grad
+        mh, vh = pose_m[v] / (1.0 - 0.9 ** pose_t[v]), pose_v[v] / (1.0 - 0.999 ** pose_t[v])
+        pose_xi[v] = pose_xi[v] - args.pose_lr * mh / (np.sqrt(vh) + 1e-15)
+        cams[v] = gsr.pose.apply_pose_delta(start_cams[v], pose_xi[v])
+
+    if args.optimize_poses:
+        cams = list(cams)
     import time
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
@@ -331,7 +374,10 @@ def main():
                              radii=buf["radii"], means2D=buf["points_xy_image"], conic_opacity=buf["conic_opacity"], rgb=buf["colors"],
                              cov3Ds=buf["cov3Ds"], clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
                              img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
-                             sh_gradient="factored" if factored else "dense", **aux_kw)
+                             sh_gradient="factored" if factored else "dense", camera_grad=args.optimize_poses, **aux_kw)
+            if args.optimize_poses:                                         # 35 floats back: the wait this flag accepts
+                gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
+                pose_step(v, gsr.pose.pose_gradient(start_cams[v], pose_xi[v], gv.view(4, 4), gp.view(4, 4), gc))
             if capacity is not None:
                 return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"], buf
             return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"]
@@ -431,7 +477,16 @@ def main():
         if dssim:
             ssim_hist /= sum_scale / 3.0                                    # ... and sums of per-pixel SSIM
     if rank == 0:
-        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets)
+        poses = None
+        if true_cams is not start_cams or args.optimize_poses:
+            err = lambda cs: [gsr.pose.pose_error(c, t) for c, t in zip(cs, true_cams)]
+            e0, e1 = err(start_cams), err(cams)
+            poses = {"pose_error_start": {"rot_deg": [r for r, _ in e0], "trans": [t for _, t in e0]},
+                     "pose_error_final": {"rot_deg": [r for r, _ in e1], "trans": [t for _, t in e1]},
+                     "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
+                     "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
+        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
+               poses)
 
 
 if __name__ == "__main__":
