@@ -13,6 +13,11 @@ p_hom.xy / (p_hom.w + 1e-7), Sigma2D = J W Sigma3D W^T J^T with the frustum clam
 1/depth, and the colour through the normalised view direction.  Visibility, tile lists and the sort order are inputs (the
 forward's own), as they are piecewise constant.  The blend stage is differentiated tile by tile and its cotangents chained into
 the per-Gaussian geometry, as f64_reference.backward_f64 does.
+
+camera_gradient_from_cotangents is that second stage alone, fed the blend-stage cotangents the kernels left in their
+accumulator records (and the forward's colour-clamp state): it runs at millions of Gaussians, where the tile-by-tile blend
+would not, and it isolates the camera kernels' own arithmetic from the blend backward's.  tests/test_camera_grad_split.py
+checks that the two stages together are camera_gradient_f64.
 """
 import numpy as np
 import torch
@@ -38,6 +43,13 @@ class Cam:
 def geometry(scene, kw, cam, view, proj, campos, degree, scale_modifier):
     """Per-Gaussian blend inputs as functions of the camera: xy (pixels), conic (A, B, C), colour (clamped), 1/depth.  view and
     proj are (4, 4) or per-Gaussian (N, 4, 4), campos (3,) or (N, 3)."""
+    xy, con, raw, invd = _geometry_raw(scene, kw, cam, view, proj, campos, degree, scale_modifier)
+    colour = torch.where(raw < 0, torch.zeros_like(raw), raw)
+    return xy, con, colour, invd
+
+
+def _geometry_raw(scene, kw, cam, view, proj, campos, degree, scale_modifier):
+    """geometry() with the colour before the clamp (SH + 0.5): the clamp is then the caller's, e.g. the forward's own."""
     N = int(np.asarray(scene["means"]).reshape(-1, 3).shape[0])
     means = F._t(scene["means"], (N, 3))
     Ph = F._homog(means)
@@ -66,8 +78,7 @@ def geometry(scene, kw, cam, view, proj, campos, degree, scale_modifier):
     ln = torch.sqrt(torch.where(l2 > 0, l2, torch.ones_like(l2)))
     dirs = torch.where((l2 > 0)[:, None], d / ln[:, None], torch.zeros_like(d))   # direction 0 (and no gradient) at campos
     raw = F.sh_colour(F._t(scene["shs"], (N, 16, 3)), dirs, degree)
-    colour = torch.where(raw < 0, torch.zeros_like(raw), raw)
-    return xy, con, colour, invd
+    return xy, con, raw, invd
 
 
 def blend_cotangents(xy, con, op, col, invd, point_list, ranges, cam, dpix=None, ddep=None, dalpha=None, alpha_cap_grad=True):
@@ -139,6 +150,48 @@ def camera_gradient_f64(scene, kw, radii, point_list, ranges, dpix=None, ddep=No
     gV, gP, gC = [torch.zeros_like(x) if g is None else g for g, x in zip((gV, gP, gC), (Vn, Pn, Cn))]
     terms = torch.cat([gV.reshape(n, 16), gP.reshape(n, 16), gC, torch.zeros(n, 1, dtype=D)], 1)
     return terms.sum(0).numpy(), terms.abs().sum(0).numpy()
+
+
+def camera_gradient_from_cotangents(scene, kw, radii, clamped, g_ndc, g_conic, g_colour, g_invd=None, chunk=262144):
+    """camera_gradient_f64's second stage alone: the per-Gaussian geometry() VJP of given blend-stage cotangents, in the
+    kernel's layout (the accumulator records gsr_backward_camera reads, include/gsr_camera_grads.h):
+        g_ndc    (N, >= 2)  dL/dndc (not pixels: xy = ((ndc + 1) W - 1) / 2)
+        g_conic  (N, 4)     dL/dA, HALF of dL/dB (conic_b_half), unused, dL/dC
+        g_colour (N, 3)     dL/d(clamped colour); `clamped` (N, 3), the forward's clamped_state, says which channels pass
+        g_invd   (N,)       dL/d(1/depth), or None (zero)
+    Same (grad (36,), scale (36,)) as camera_gradient_f64.  The visible Gaussians (radii > 0) go through in chunks of `chunk`
+    (per-Gaussian camera leaves: memory stays bounded at millions of Gaussians); terms and |terms| are summed in float64."""
+    cam = Cam(kw)
+    degree, sm = int(kw["degree"]), float(kw["scale_modifier"])
+    N = int(np.asarray(scene["means"]).reshape(-1, 3).shape[0])
+    idx = np.nonzero(np.asarray(radii).reshape(-1) > 0)[0]
+    rows = lambda a: np.asarray(a).reshape(N, -1)
+    arrays = {k: rows(scene[k]) for k in ("means", "scales", "rotations", "shs")}
+    g_ndc, g_conic, g_colour, clamped = rows(g_ndc)[:, :2], rows(g_conic), rows(g_colour), rows(clamped)
+    g_invd = None if g_invd is None else np.asarray(g_invd).reshape(N)
+    grad, scale = torch.zeros(36, dtype=D), torch.zeros(36, dtype=D)
+    w64 = lambda a: torch.as_tensor(np.asarray(a, np.float64))
+    for s in range(0, idx.size, chunk):
+        ii = idx[s:s + chunk]
+        n = ii.size
+        sub = {k: a[ii] for k, a in arrays.items()}
+        Vn = cam.view.expand(n, 4, 4).clone().requires_grad_(True)
+        Pn = cam.proj.expand(n, 4, 4).clone().requires_grad_(True)
+        Cn = cam.campos.expand(n, 3).clone().requires_grad_(True)
+        xy, con, raw, invd = _geometry_raw(sub, kw, cam, Vn, Pn, Cn, degree, sm)
+        gxy = w64(g_ndc[ii]) * torch.tensor([2.0 / cam.W, 2.0 / cam.H], dtype=D)     # dxy/dndc = (W / 2, H / 2)
+        gc = w64(g_conic[ii])
+        gcon = torch.stack([gc[:, 0], 2.0 * gc[:, 1], gc[:, 3]], 1)
+        gcol = w64(g_colour[ii]) * (w64(clamped[ii]) == 0)                          # clamped channels pass nothing
+        L = (xy * gxy).sum() + (con * gcon).sum() + (raw * gcol).sum()
+        if g_invd is not None:
+            L = L + (invd * w64(g_invd[ii])).sum()
+        gV, gP, gC = torch.autograd.grad(L, (Vn, Pn, Cn), allow_unused=True)
+        gV, gP, gC = [torch.zeros_like(x) if g is None else g for g, x in zip((gV, gP, gC), (Vn, Pn, Cn))]
+        terms = torch.cat([gV.reshape(n, 16), gP.reshape(n, 16), gC, torch.zeros(n, 1, dtype=D)], 1)
+        grad += terms.sum(0)
+        scale += terms.abs().sum(0)
+    return grad.numpy(), scale.numpy()
 
 
 def loss_f64(scene, kw, view, proj, campos, radii, point_list, ranges, dpix=None, ddep=None, dalpha=None):

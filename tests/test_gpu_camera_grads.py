@@ -14,6 +14,21 @@ Camera gradients (include/gsr_camera_grads.h, backward(camera_grad=True)) and po
 3. Empty frames (N = 0, everything culled) give zeros.
 4. Pose recovery with frozen Gaussians: Adam on xi alone brings a perturbed camera back to the one that rendered the target.
 5. The trainer on Lego with perturbed poses: --optimize-poses lowers the final pose error without raising the training L1.
+6. Against the stage-isolated float64 reference (camera_grad_reference.camera_gradient_from_cotangents, fed the kernel's own
+   accumulator records and clamped_state; tests/test_camera_grad_split.py shows it is check 1's reference split in two) on
+   the case matrix and at the sizes where the kernel pair's structure changes: N = 255 (one partial block), 65 536 / 65 537
+   (camera_finish_kernel sums a second row per lane past 256 rows), 262 144 / 262 145 (the grid is capped at 1024 blocks and
+   the stride loop takes a second lap), C2, C3 and C5 (5 M, about 19 Gaussians per lane).  Same error measure as check 1, but
+   what remains is only the kernel's float32 arithmetic per Gaussian and its float32 lane and wave sums, so the tripwire
+   TRIP_ISOLATED is tighter than TRIP.
+7. One Gaussian at a time, at every structural position of the kernel pair (lane, wave and block edges, finish rows 255 /
+   256 / 512 / 768, both ends of every lap of the stride loop, N - 1) on a 262 145-Gaussian frame and a C5 frame: unit-scale
+   random cotangents in the accumulator records and a copy of radii that is zero except at the chosen Gaussians, so the
+   kernel's output is that one Gaussian's term, checked against the reference's term (TRIP_TERM, relative to the largest
+   entry of the term's view / proj / campos block).  A dropped or duplicated term is an error of 1 there.  Then all chosen
+   Gaussians together, and all-zero radii (exact zeros).  The forward's smallest radius is 3 (the 0.3 blur), so a few
+   Gaussians carry radius 1 in the copy: the kernel's visibility test is radius > 0.  The camera call on the full frame is
+   also bitwise reproducible at these sizes (check 2's assertion at C3).
 """
 import ctypes as C
 import json
@@ -37,6 +52,18 @@ pytestmark = pytest.mark.gpu
 # the MI355X (16x16_n1, colour + depth + alpha; every other case below 6.5e-5); TRIP = 10x
 MEASURED = 8.9e-5
 TRIP = 10.0 * MEASURED
+# check 6: max over the entries of |kernel - isolated f64| / sum |f64 term|, worst case over the case matrix, the large cases and
+# every size, both inputs, measured on the MI355X: 3.73e-5 (200x136_n700, colour + depth + alpha, worst of nine runs: its blend
+# cotangents are float-atomic sums that largely cancel, so they and the conditioning of its terms change from run to run,
+# 8.6e-6 to 3.73e-5; every other case below 6.1e-6 and steady, every size from n255 to C5 below 1.0e-6, C5 1.5e-7);
+# TRIP_ISOLATED = 10x, 2.4x tighter than TRIP
+MEASURED_ISOLATED = 3.73e-5
+TRIP_ISOLATED = 10.0 * MEASURED_ISOLATED
+# check 7: one Gaussian's term, max |kernel - f64| over each block (view, proj, campos) / max |f64| over that block, worst case
+# over every chosen index of both frames, measured on the MI355X: 7.3e-7 (C5, Gaussian 63, campos; the 262 145 frame 3.9e-7);
+# TRIP_TERM = 10x.  All chosen Gaussians together: 2.6e-7 of sum |term| (C5), held to TRIP_ISOLATED.
+MEASURED_TERM = 7.3e-7
+TRIP_TERM = 10.0 * MEASURED_TERM
 # check 2 (whole calls), relative to max |camera gradient| of the dense call: two dense calls differ by up to 6.2e-7 at C3 and the
 # other paths by up to 6.7e-7 from the dense one (float-atomic order of the blend accumulators); the floor is 10x that
 SPREAD_FLOOR = 7e-6
@@ -218,6 +245,152 @@ def test_empty_frames_give_zeros():
     dpix = np.ones((48, 64, 3), np.float32)
     g1 = gsr.backward(**_bkw(behind, cam, kw1, b1, dpix), dL_ddepth_image=np.ones((48, 64), np.float32), camera_grad=True)
     assert not np.any(_cam36(g1))
+
+
+# ------------------------------------------------------------------------------- check 6: against the isolated f64 reference
+# name -> (scene config, N): the sizes where the kernel pair's structure changes, on C3's scene statistics unless named
+SIZES = {"n255": ("C3", 255), "n65536": ("C3", 65536), "n65537": ("C3", 65537), "n262144": ("C3", 262144),
+         "n262145": ("C3", 262145), "C2": ("C2", None), "C3": ("C3", None), "C5": ("C5", None)}
+LAP = 1024 * 256     # lanes of the capped grid (GSR_CAMERA_MAX_BLOCKS blocks of 256): one lap of the stride loop
+GROUPS = (slice(0, 16), slice(16, 32), slice(32, 36))   # view, proj, campos (+ the zero entry 35)
+
+
+def _frame(name):
+    gsr = pkg()
+    cfg_name, n = SIZES[name]
+    cfg = gsr.scenes.CONFIGS[cfg_name]
+    W, H = cfg["width"], cfg["height"]
+    sc = gsr.scenes.synthetic_scene(n or cfg["n"], cfg["scale_median"], cfg["scale_sigma"], cfg["seed"])
+    cam = gsr.cameras.nerf_camera(gsr.scenes.LEGO_FRAME0, W, H, gsr.scenes.LEGO_CAMERA_ANGLE_X)
+    return sc, cam
+
+
+def _records(g):
+    """The (N, 16) float32 accumulator records of the workspace that `g` (a backward() result) returned views of."""
+    c = g["dL_dcolor"]
+    assert c.stride() == (16, 1), c.stride()
+    return c.as_strided((c.shape[0], 16), (16, 1))
+
+
+def _isolated_f64(sc, kw, radii, clamped, rec):
+    """The isolated reference on the kernel's own cotangents (GradRec slots 0-2, 3-4, 6-9, 11)."""
+    return CG.camera_gradient_from_cotangents(sc, kw, radii, clamped, rec[:, 3:5], rec[:, 6:10], rec[:, 0:3], rec[:, 11])
+
+
+def _isolated_error(got, ref, scale, what):
+    zero = scale == 0
+    assert not np.any(got[zero]), (what, np.where(zero & (got != 0))[0])
+    assert np.isfinite(got).all(), what
+    err = np.abs(got - ref)[~zero] / scale[~zero]
+    return float(err.max()) if err.size else 0.0
+
+
+@pytest.mark.parametrize("name", R.CASE_NAMES + list(G.LARGE) + list(SIZES))
+def test_camera_gradient_against_isolated_f64(oracle, cameras, name):
+    gsr = pkg()
+    if name in SIZES:
+        sc, cam = _frame(name)
+        kw = render_kwargs(sc, cam, width=cam["width"], height=cam["height"], bg=(0.1, 0.2, 0.3))
+    else:
+        c = G._case(oracle, cameras, name)
+        sc, cam, kw = c["sc"], c["cam"], c["kw"]
+    H, W = kw["image_height"], kw["image_width"]
+    N = int(np.asarray(sc["means"]).reshape(-1, 3).shape[0])
+    dpix, gD, gA = _grads(H, W, 19)
+    _, _, buf = gsr.render_gaussians(**kw)
+    radii, clamped = parity.to_np(buf["radii"]), parity.to_np(buf["clamped_state"])
+    n_vis = int((radii > 0).sum())
+    worst = {}
+    for label, (p, d, a) in {"colour": (dpix, None, None), "all": (dpix, gD, gA)}.items():
+        g = gsr.backward(**_bkw(sc, cam, kw, buf, p), dL_ddepth_image=d, dL_dalpha_image=a, camera_grad=True)
+        got = _cam36(g)
+        rec = _records(g).cpu().numpy()
+        del g
+        ref, scale = _isolated_f64(sc, kw, radii, clamped, rec)
+        worst[label] = _isolated_error(got, ref, scale, label)
+    print(f"\n{name} (N {N}, visible {n_vis}): " + ", ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert n_vis > 0
+    assert max(worst.values()) <= TRIP_ISOLATED, worst
+
+
+# --------------------------------------------------------------------------------------- check 7: one Gaussian at a time
+def _structural_indices(N):
+    """Lane / wave / block edges, the finish kernel's row edges (256 rows per pass), both ends of every lap of the stride
+    loop, and N - 1."""
+    nblk = min(-(-N // 256), 1024)
+    lap = nblk * 256
+    idx = {0, 63, 64, 255, 256, 65535, 65536, 131071, 131072, 196607, 196608, 262143, 262144, 262145, N - 1}
+    for start in range(0, N, lap):
+        idx |= {start, min(start + lap, N) - 1}
+    return sorted(i for i in idx if 0 <= i < N)
+
+
+@pytest.mark.parametrize("name", ["n262145", "C5"])
+def test_camera_gradient_one_gaussian_at_a_time(name):
+    gsr = pkg()
+    sc, cam = _frame(name)
+    N = int(sc["means"].shape[0])
+    assert N > LAP
+    idx = _structural_indices(N)
+    ones = idx[1::4]                                                # these carry radius 1 in the copy
+    rng = np.random.default_rng(41)
+    sc = {k: np.array(v) for k, v in sc.items()}                    # the chosen Gaussians, moved into the middle of the view
+    sc["means"][idx] = rng.uniform(-0.5, 0.5, (len(idx), 3)).astype(np.float32)
+    sc["scales"][idx] = rng.uniform(0.01, 0.05, (len(idx), 3)).astype(np.float32)
+    sc["opacities"][idx] = 0.5
+    W, H = cam["width"], cam["height"]
+    kw = render_kwargs(sc, cam, width=W, height=H, bg=(0.1, 0.2, 0.3))
+    _, _, buf = gsr.render_gaussians(**kw)
+    radii = buf["radii"]
+    r_np, clamped = parity.to_np(radii), parity.to_np(buf["clamped_state"])
+    assert (r_np[idx] > 0).all(), [i for i in idx if r_np[i] <= 0]
+    dpix, _, _ = _grads(H, W, 8)
+    g = gsr.backward(**_bkw(sc, cam, kw, buf, dpix), camera_grad=True)
+    torch.cuda.synchronize()
+    whole = _cam36(g)
+    # check 2 at this size: the same workspace again gives the same bits
+    for _ in range(2):
+        again = _direct_camera_call(sc, kw, buf, g)
+        assert np.array_equal(again, whole), np.abs(again - whole).max()
+    # unit-scale random cotangents in every slot the camera kernel reads
+    rec = _records(g)
+    cols = [0, 1, 2, 3, 4, 6, 7, 9, 11]
+    rec[:, cols] = torch.as_tensor(rng.normal(0.0, 1.0, (N, len(cols))).astype(np.float32)).to(rec.device)
+    torch.cuda.synchronize()
+    rec_np = rec.cpu().numpy()
+
+    def only(chosen):
+        m = torch.zeros_like(radii)
+        if chosen:
+            sel = torch.as_tensor(chosen, device=radii.device)
+            m[sel] = radii[sel]
+            one = [i for i in chosen if i in ones]
+            if one:
+                m[torch.as_tensor(one, device=radii.device)] = 1
+        return m
+
+    worst, where = 0.0, None
+    for i in idx:
+        m = only([i])
+        got = _direct_camera_call(sc, kw, dict(buf, radii=m), g)
+        ref, scale = _isolated_f64(sc, kw, parity.to_np(m), clamped, rec_np)
+        assert not np.any(got[scale == 0]), (i, np.where((scale == 0) & (got != 0))[0])
+        for s in GROUPS:
+            top = np.abs(ref[s]).max()
+            if top == 0:        # campos when every channel is clamped: the exact-zero check above covers it
+                continue
+            e = float(np.abs(got[s] - ref[s]).max() / top)
+            if e > worst:
+                worst, where = e, (i, s.start)
+        assert worst <= TRIP_TERM, (name, i, worst, where, got, ref)
+    m = only(idx)
+    got = _direct_camera_call(sc, kw, dict(buf, radii=m), g)
+    together = _isolated_error(got, *_isolated_f64(sc, kw, parity.to_np(m), clamped, rec_np), "chosen together")
+    zeros = _direct_camera_call(sc, kw, dict(buf, radii=torch.zeros_like(radii)), g)
+    print(f"\n{name} (N {N}): {len(idx)} Gaussians, one at a time worst {worst:.2e} (index, block {where}), together "
+          f"{together:.2e}")
+    assert not np.any(zeros)
+    assert together <= TRIP_ISOLATED, together
 
 
 # --------------------------------------------------------------------------------------------------- check 4: pose recovery
