@@ -137,6 +137,24 @@ CAMERA_EXPORTS = {
 }
 CAMERA_GRAD_FLOATS = 36     # GSR_CAMERA_GRAD_FLOATS: view 0-15 | proj 16-31 | campos 32-34 | 0
 
+
+
+class GsrDensifyStats(C.Structure):
+    _fields_ = [("N", C.c_int64), ("grad_accum", vp), ("vis_count", vp), ("max_radii", vp)]
+
+
+# include/gsr_densify_stats.h: screen-space densification statistics and the absolute-gradient backward (its own header, so its own table)
+DENSIFY_STATS_EXPORTS = {
+    "gsr_backward_flags": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                     C.POINTER(GsrImage), C.POINTER(GsrPixelGrads), C.POINTER(GsrGrads), vp, vp, C.c_size_t, C.c_uint32, vp]),
+    "gsr_backward_blend_flags": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                           C.POINTER(GsrImage), C.POINTER(GsrPixelGrads), vp, vp, C.c_size_t, C.c_uint32, vp]),
+    "gsr_densify_stats_update": (C.c_int, [C.POINTER(GsrDensifyStats), vp, vp, C.c_size_t, C.c_int32, vp]),
+    "gsr_densify_mark_stats": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrDensifyStats), C.c_float, C.c_float, C.c_float, C.c_int, vp, vp]),
+    "gsr_prune_mark_stats": (C.c_int, [C.POINTER(GsrParams), C.POINTER(GsrDensifyStats), C.c_float, C.c_float, C.c_float, vp, vp]),
+}
+BWD_ABSGRAD = 1             # GSR_BWD_ABSGRAD
+
 STAGES = ["preprocess", "scan", "depth_sort", "host_gap", "depth_scan", "expand", "tile_sort", "ranges", "blend_fwd",
           "bwd_prep", "blend_bwd", "geom_bwd"]
 
@@ -152,7 +170,8 @@ def lib():
                                "(hipcc --offload-arch=gfx950).  There is no fallback path.")
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items())
-                                  + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())):
+                                  + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
+                                  + list(DENSIFY_STATS_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -24,6 +24,13 @@ Gaussian, an (N,) strided view of the accumulator records.  With neither, the ca
 kernel pair after the backward above, which reads its accumulators and writes nothing else, so every other key is what the
 call with camera_grad=False returns.  The sum is bitwise reproducible for given accumulators.  pose.pose_gradient turns the
 three into the gradient of a per-view pose correction.
+
+`absgrad=True` (include/gsr_densify_stats.h, GSR_BWD_ABSGRAD) adds one key, `dL_dmean2D_abs`: an (N, 2) strided view of columns
+12-13 of the accumulator records, the sums of the MAGNITUDES of the per-(pixel, entry) terms whose signed sums are
+dL_dmean2D[:, 0:2] (AbsGS).  The call runs the flagged entry point; every other key is what the call without it returns, up to
+float-atomic order.  Without the keyword the two columns are zero and the key is absent.  Either way the returned `dL_dmean2D`
+carries a private tag (`_gsr_backward_ws`: workspace, its version counter, whether the absolute columns were filled) through
+which densify.DensifyStats.update finds the accumulators.
 """
 import ctypes as C
 
@@ -59,7 +66,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256, campos=None,
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
-             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False):
+             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False):
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
     aux = dL_ddepth_image is not None or dL_dalpha_image is not None
@@ -216,7 +223,23 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         binning = _lib.GsrBinning(D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(masks), _host.ptr(order),
                                   _host.ptr(ws) if cleared else None, 1 if cleared else 0)
         backward.last_call_skipped_the_clear = cleared     # for tests and debugging
-        if aux:
+        if absgrad:     # the flagged pair of gsr_densify_stats.h: gsr_backward_aux's arguments and GSR_BWD_ABSGRAD
+            pg = _lib.GsrPixelGrads(_host.ptr(dpix), _host.ptr(g_depth), _host.ptr(g_alpha))
+            if on_payload is not None and payload is not None:
+                _lib.check(L.gsr_backward_blend_flags(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
+                                                      _host.ptr(payload), _host.ptr(ws), ws.numel(), _lib.BWD_ABSGRAD, stream))
+                on_payload(payload)
+                grads.dL_drgb = None
+                if aux:
+                    _lib.check(L.gsr_backward_geom_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), None, _host.ptr(ws),
+                                                       ws.numel(), stream))
+                else:
+                    _lib.check(L.gsr_backward_geom(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), _host.ptr(ws), ws.numel(),
+                                                   stream))
+            else:
+                _lib.check(L.gsr_backward_flags(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
+                                                C.byref(grads), None, _host.ptr(ws), ws.numel(), _lib.BWD_ABSGRAD, stream))
+        elif aux:
             pg = _lib.GsrPixelGrads(_host.ptr(dpix), _host.ptr(g_depth), _host.ptr(g_alpha))
             if on_payload is not None and payload is not None:
                 _lib.check(L.gsr_backward_blend_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
@@ -255,4 +278,8 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         out["dL_dviewmatrix"], out["dL_dprojmatrix"], out["dL_dcampos"] = dcam[0:16].view(4, 4), dcam[16:32].view(4, 4), dcam[32:35]
     if aux:
         out["dL_dinv_depths"] = acc[:, 11]      # GradRec slot 11 (gsr_gradrec_slot(9)): dL/d(1/depth) per Gaussian
+    if absgrad:
+        out["dL_dmean2D_abs"] = acc[:, 12:14]   # GradRec slots 12-13 (gsr_gradrec_slot(10), (11)): sums of |terms of dL_dmean2D|
+    # for densify.DensifyStats.update: the workspace whose accumulators this call filled (it rides on the packed copy too)
+    dL_dmean2D._gsr_backward_ws = (ws, ws._version, bool(absgrad), N)
     return out

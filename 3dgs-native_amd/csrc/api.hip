@@ -12,6 +12,7 @@
 #include "gsr_aux_grads.h"
 #include "gsr_camera_grads.h"
 #include "gsr_capacity.h"
+#include "gsr_densify_stats.h"
 #include "gsr_internal.h"
 
 namespace {
@@ -530,7 +531,7 @@ int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const G
 // must carry 1/depth when dL_dinvd is given.
 static int backward_blend_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
                                const GsrImage *image, const float *dL_dpixels, float *payload, void *ws, size_t ws_bytes, hipStream_t s, int st,
-                               bool aux = false, const float *dL_dinvd = nullptr, const float *dL_dA = nullptr)
+                               bool aux = false, const float *dL_dinvd = nullptr, const float *dL_dA = nullptr, bool absgrad = false)
 {
     const int64_t N = scene->N;
     if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // (cov3D may be NULL: gsr.h GsrGeom)
@@ -559,7 +560,7 @@ static int backward_blend_impl(const GsrScene *scene, const GsrCamera *camera, c
     mark(st, 11, s);
     if (D > 0) HIP_TRY(gsr_launch_blend_backward_splat(cam, binning->ranges, binning->point_list, records, *image, dL_dpixels, binning->block_masks,
                                                        binning->block_masks ? binning->block_order : nullptr, bw.acc, N, D, s, aux,
-                                                       dL_dinvd, dL_dA));
+                                                       dL_dinvd, dL_dA, absgrad));
     mark(st, 12, s);
     if (payload) HIP_TRY(gsr_launch_view_payload(*scene, cam, *geom, bw.acc, payload, s));
     return GSR_OK;
@@ -626,8 +627,10 @@ int gsr_backward_geom(const GsrScene *scene, const GsrCamera *camera, const GsrG
 // ---- include/gsr_aux_grads.h: the backward through the inverse-depth and alpha images ----
 // Every argument of both halves is checked before the blend half enqueues anything.  With neither auxiliary gradient (and no
 // dL_dinv_depths) the call is gsr_backward's own: the same kernels, bit for bit.
-int gsr_backward_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                     const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, void *stream)
+// (`absgrad`: include/gsr_densify_stats.h, GSR_BWD_ABSGRAD -- the ABS blend kernels; everything else is the same call)
+static int backward_aux_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                             const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, bool absgrad,
+                             void *stream)
 {
     read_tuning();
     if (int rc = check_scene_cam(scene, camera)) return rc;
@@ -640,14 +643,21 @@ int gsr_backward_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGe
     hipStream_t s = (hipStream_t)stream;
     const int st = timer_open(false);
     if (int rc = backward_blend_impl(scene, camera, geom, binning, image, pixel_grads->dL_dpixels, nullptr, ws, ws_bytes, s, st, aux,
-                                     pixel_grads->dL_dinv_depth, pixel_grads->dL_dalpha))
+                                     pixel_grads->dL_dinv_depth, pixel_grads->dL_dalpha, absgrad))
         return rc;
     if (int rc = backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, s, st, aux || dL_dinv_depths, dL_dinv_depths)) return rc;
     return GSR_OK;
 }
 
-int gsr_backward_blend_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                           const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, void *stream)
+int gsr_backward_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                     const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, void *stream)
+{
+    return backward_aux_impl(scene, camera, geom, binning, image, pixel_grads, grads, dL_dinv_depths, ws, ws_bytes, false, stream);
+}
+
+static int backward_blend_aux_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
+                                   const GsrImage *image, const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, bool absgrad,
+                                   void *stream)
 {
     read_tuning();
     if (int rc = check_scene_cam(scene, camera)) return rc;
@@ -656,7 +666,30 @@ int gsr_backward_blend_aux(const GsrScene *scene, const GsrCamera *camera, const
     t_bwd_record = timer_open(false);
     return backward_blend_impl(scene, camera, geom, binning, image, pixel_grads->dL_dpixels, payload, ws, ws_bytes, (hipStream_t)stream,
                                t_bwd_record, pixel_grads->dL_dinv_depth || pixel_grads->dL_dalpha, pixel_grads->dL_dinv_depth,
-                               pixel_grads->dL_dalpha);
+                               pixel_grads->dL_dalpha, absgrad);
+}
+
+int gsr_backward_blend_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                           const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, void *stream)
+{
+    return backward_blend_aux_impl(scene, camera, geom, binning, image, pixel_grads, payload, ws, ws_bytes, false, stream);
+}
+
+// ---- include/gsr_densify_stats.h: the same two calls with flags (GSR_BWD_ABSGRAD: the ABS blend kernels) ----
+int gsr_backward_flags(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                       const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, uint32_t flags,
+                       void *stream)
+{
+    if (flags & ~GSR_BWD_ABSGRAD) return GSR_E_DIMS;
+    return backward_aux_impl(scene, camera, geom, binning, image, pixel_grads, grads, dL_dinv_depths, ws, ws_bytes, (flags & GSR_BWD_ABSGRAD) != 0,
+                             stream);
+}
+
+int gsr_backward_blend_flags(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                             const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, uint32_t flags, void *stream)
+{
+    if (flags & ~GSR_BWD_ABSGRAD) return GSR_E_DIMS;
+    return backward_blend_aux_impl(scene, camera, geom, binning, image, pixel_grads, payload, ws, ws_bytes, (flags & GSR_BWD_ABSGRAD) != 0, stream);
 }
 
 int gsr_backward_geom_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, float *dL_dinv_depths,

@@ -228,7 +228,12 @@ constexpr int QCAP = 128;                 // ring of compacted entries (power of
 //     cd_k = c_k . dpix + gD invd_k        Q seed = T_final (bg . dpix - gA)        dL/dinvd_k = sum over pixels of alpha_k T_k gD
 // (invd_k = the record's 1/depth, f[9]); the tenth accumulated value goes to GradRec slot 11 (gsr_gradrec_slot(9)).  The AUX =
 // false kernels get nullptr for the two pointers and are the product's machine code unchanged (tools/kernel_disasm_diff.py).
-template <int BW, int BH, bool USE_MASKS, bool AUX = false>
+// ABS (include/gsr_densify_stats.h, built with AUX only): beside the signed dL/dmean2D, the sums of the MAGNITUDES of its
+// per-(pixel, entry) terms -- an entry's term is h (a dx + b dy) 0.5 W in x, h (c dy + b dx) 0.5 H in y, so
+//     Sax = sum |h (a dx + b dy)|        Say = sum |h (c dy + b dx)|
+// under the same `live` predicate; they travel as accumulated values 10 and 11 to GradRec columns 12 and 13, which the
+// flush's lanes 10 and 11 of each 16-lane group otherwise leave alone.  ABS = false adds nothing to any kernel.
+template <int BW, int BH, bool USE_MASKS, bool AUX = false, bool ABS = false>
 __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, int grid_x, float bg0, float bg1, float bg2,
                                                                   const int32_t *__restrict__ ranges,
                                                                   const int32_t *__restrict__ point_list,
@@ -249,8 +254,9 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
     __shared__ float4 s_pb[NPIX];   // dpix r,g,b, kept (as int bits)
     __shared__ int2 s_ring[QCAP];   // compacted survivors: (Gaussian id, list index); records are re-gathered (L2 hits)
     __shared__ float s_pd[NPIX];    // AUX: gD of each pixel (unreferenced, hence not allocated, otherwise)
-    constexpr int NG = AUX ? 10 : 9; // accumulated values per entry
-    __shared__ float s_g[64][AUX ? 11 : 9]; // per-entry gradients for the transposed flush (odd stride: no bank conflicts)
+    static_assert(AUX || !ABS, "the ABS kernels are built with AUX only");
+    constexpr int NG = ABS ? 12 : AUX ? 10 : 9; // accumulated values per entry
+    __shared__ float s_g[64][ABS ? 13 : AUX ? 11 : 9]; // per-entry gradients for the transposed flush (odd stride: no bank conflicts)
     __shared__ int s_id[64];
 
     const int lane = threadIdx.x;
@@ -444,6 +450,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         //   Sxx = sum h dx^2         Sxy = sum h dx dy  Syy = sum h dy^2      Sop = sum G dL/dalpha
         float g_c0 = 0.f, g_c1 = 0.f, g_c2 = 0.f, S1 = 0.f, S2 = 0.f, Sxx = 0.f, Sxy = 0.f, Syy = 0.f, Sop = 0.f;
         float Sdep = 0.f; // AUX: sum alpha T gD
+        float Sax = 0.f, Say = 0.f; // ABS: sums of |h (a dx + b dy)| and |h (c dy + b dx)|
         bool touched = false;
         const float ca2 = -0.5f * a.z, cb2 = -a.w, cc2 = -0.5f * b.x; // exact
 
@@ -478,6 +485,10 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             const float hx = h * d_x, hy = h * d_y;                                                                           \
             S1 += hx; S2 += hy;                                                                                               \
             Sxx += hx * d_x; Sxy += hx * d_y; Syy += hy * d_y;                                                                \
+            if constexpr (ABS) {                                                                                              \
+                Sax += fabsf(h * (2.0f * ca2 * d_x + cb2 * d_y));                                                             \
+                Say += fabsf(h * (2.0f * cc2 * d_y + cb2 * d_x));                                                             \
+            }                                                                                                                 \
         }                                                                                                                     \
     }
         const int rows_run = GSR_ABL(dbg, 2) ? 1 : BH;
@@ -498,6 +509,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
 #define GSR_SUM4(v) v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64);
             GSR_SUM4(g_c0) GSR_SUM4(g_c1) GSR_SUM4(g_c2) GSR_SUM4(S1) GSR_SUM4(S2) GSR_SUM4(Sxx) GSR_SUM4(Sxy) GSR_SUM4(Syy) GSR_SUM4(Sop)
             if constexpr (AUX) { GSR_SUM4(Sdep) }
+            if constexpr (ABS) { GSR_SUM4(Sax) GSR_SUM4(Say) }
 #undef GSR_SUM4
             int t4 = (int)touched;
             t4 |= __shfl_xor(t4, 16, 64);
@@ -533,6 +545,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
             Sxx += __shfl_xor(Sxx, 32, 64); Sxy += __shfl_xor(Sxy, 32, 64); Syy += __shfl_xor(Syy, 32, 64);
             Sop += __shfl_xor(Sop, 32, 64);
             if constexpr (AUX) Sdep += __shfl_xor(Sdep, 32, 64);
+            if constexpr (ABS) { Sax += __shfl_xor(Sax, 32, 64); Say += __shfl_xor(Say, 32, 64); }
             const int partner_touched = __shfl_xor((int)touched, 32, 64); // unconditionally: a cross-lane read must not sit behind ||
             touched = (touched || partner_touched != 0) && lane < 32;
         }
@@ -548,6 +561,7 @@ __global__ __launch_bounds__(64) void blend_backward_splat_kernel(int W, int H, 
         s_g[lane][0] = g_c0; s_g[lane][1] = g_c1; s_g[lane][2] = g_c2; s_g[lane][3] = g_mx; s_g[lane][4] = g_my;
         s_g[lane][5] = g_ca; s_g[lane][6] = g_cb; s_g[lane][7] = g_cc; s_g[lane][8] = g_op;
         if constexpr (AUX) s_g[lane][9] = Sdep;
+        if constexpr (ABS) { s_g[lane][10] = Sax * fabsf(ddelx_dx); s_g[lane][11] = Say * fabsf(ddely_dy); } // |terms of g_mx|, |terms of g_my|
         __syncthreads();
         const int c = lane & 15, fslot = gsr_gradrec_slot(c); // the record's layout leaves the API arrays' zero columns free
         const int flush_rows = (n + 3) >> 2; // four entries per wave instruction; entries beyond n have nothing
@@ -621,7 +635,7 @@ int gsr_debug_flags = 0; // see gsr_internal.h
 hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *ranges, const int32_t *point_list, const BlendRec *rec,
                                            const GsrImage &img, const float *dL_dpixels, const uint8_t *block_masks,
                                            const int32_t *block_order, GradRec *acc, int64_t N, int64_t D, hipStream_t s, bool aux,
-                                           const float *dL_dinvd, const float *dL_dA)
+                                           const float *dL_dinvd, const float *dL_dA, bool absgrad)
 {
     const int tiles = cam.grid_x * cam.grid_y;
     if (tiles <= 0) return hipSuccess;
@@ -630,7 +644,12 @@ hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *range
         const int nblk = tiles * (256 / ((BW) * (BH)));                                                                       \
         const int32_t *bo = ((M) && (BH) == 4) ? block_order : nullptr; /* 8x4 blocks only */                                 \
         const int grid = bo ? 8 * 8 * gsr_bo_tiles_per_band(tiles) : 8 * ((nblk + 7) / 8);                                   \
-        if (aux)                                                                                                              \
+        if (absgrad) /* the ABS kernels are AUX kernels: NULL aux pointers cost them a uniform branch */                      \
+            hipLaunchKernelGGL((blend_backward_splat_kernel<BW, BH, M, true, true>), dim3(grid), dim3(64), 0, s, cam.W,      \
+                               cam.H, cam.grid_x, cam.bg[0], cam.bg[1], cam.bg[2], ranges, point_list, rec, img.final_T,      \
+                               img.n_contrib, dL_dpixels, block_masks, acc, gsr_debug_flags, nblk, bo, gsr_bo_cap(tiles),     \
+                               dL_dinvd, dL_dA);                                                                              \
+        else if (aux)                                                                                                         \
             hipLaunchKernelGGL((blend_backward_splat_kernel<BW, BH, M, true>), dim3(grid), dim3(64), 0, s, cam.W, cam.H,     \
                                cam.grid_x, cam.bg[0], cam.bg[1], cam.bg[2], ranges, point_list, rec, img.final_T,             \
                                img.n_contrib, dL_dpixels, block_masks, acc, gsr_debug_flags, nblk, bo, gsr_bo_cap(tiles),     \

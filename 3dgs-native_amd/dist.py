@@ -136,6 +136,19 @@ def reduce_gradients(arena, world_size=None, average=True):
     return arena
 
 
+def reduce_densify_stats(stats, world_size=None):
+    """Combine the screen-space densification statistics (densify.DensifyStats, include/gsr_densify_stats.h) of all ranks, in
+    place: SUM over ranks of `grad_accum` and `vis_count`, MAX of `max_radii`.  Called once per density-control call, before
+    densification_and_pruning -- not per iteration -- so replicated ranks, which each saw their own views, mark identical rows.
+    Three small collectives (4 bytes per Gaussian each).  A single process returns at once."""
+    if not dist.is_initialized() or dist.get_world_size() == 1:
+        return stats
+    dist.all_reduce(stats.grad_accum, op=dist.ReduceOp.SUM)
+    dist.all_reduce(stats.vis_count, op=dist.ReduceOp.SUM)
+    dist.all_reduce(stats.max_radii, op=dist.ReduceOp.MAX)
+    return stats
+
+
 def small_arena_views(arena, n):
     """Split the 11-float arena of the factored mode (arena_size(n, small=True) floats; views, no copies)."""
     o = arena_offsets(n, small=True)

@@ -23,6 +23,13 @@ trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
 perturb the dataset poses first, for experiments; the --log summary then records the per-view pose error against the dataset
 poses (degrees, scene units) at the start and the end.  One GPU only.
+
+Density control on screen-space statistics (include/gsr_densify_stats.h): --densify-stat screen accumulates, per Gaussian, the norm
+of dL/dmean2D over every view that saw it since the last density-control call (one small kernel after each view's backward, on that
+view's stream), marks clone / split candidates from the average against --densify-grad-threshold, and prunes also by
+--prune-screen-size (pixels) and --prune-world-size (fraction of the scene extent) once past the first opacity reset.  --absgrad
+accumulates the sums of per-pixel magnitudes instead (AbsGS; thresholds of 2-4x the signed one are usual).  The default,
+--densify-stat reference, is the reference trainer's rule: the 3D position gradient of the last view.
 """
 import argparse
 import importlib
@@ -233,7 +240,21 @@ def main():
     ap.add_argument("--pose-noise-deg", type=float, default=0.0, help="perturb every dataset pose by this rotation (degrees, random axis)")
     ap.add_argument("--pose-noise-trans", type=float, default=0.0, help="... and this translation (scene units, random direction)")
     ap.add_argument("--pose-seed", type=int, default=0, help="seed of the pose perturbation")
+    ap.add_argument("--densify-stat", default="reference", choices=["reference", "screen"], help="what density control tests: the "
+                    "reference's 3D position gradient of the last view, or the screen-space gradient norm averaged over the views that "
+                    "saw each Gaussian since the last call (include/gsr_densify_stats.h)")
+    ap.add_argument("--absgrad", action="store_true", help="with --densify-stat screen: accumulate absolute per-pixel gradients "
+                    "(backward(absgrad=True)); choose --densify-grad-threshold 2-4x the signed one")
+    ap.add_argument("--densify-grad-threshold", type=float, default=0.0002, help="gradient threshold of clone / split (config.py:54)")
+    ap.add_argument("--prune-screen-size", type=float, default=0.0, metavar="PX", help="with --densify-stat screen: prune Gaussians whose "
+                    "largest screen radius exceeded PX pixels (0 = off; applies after the first opacity reset)")
+    ap.add_argument("--prune-world-size", type=float, default=0.0, metavar="FRAC", help="with --densify-stat screen: prune Gaussians whose "
+                    "largest scale exceeds FRAC of the scene extent (0 = off; applies after the first opacity reset)")
     args = ap.parse_args()
+    if not args.densify_grad_threshold >= 0.0 or not args.prune_screen_size >= 0.0 or not args.prune_world_size >= 0.0:
+        raise SystemExit("--densify-grad-threshold, --prune-screen-size and --prune-world-size must be >= 0")
+    if args.densify_stat != "screen" and (args.absgrad or args.prune_screen_size > 0.0 or args.prune_world_size > 0.0):
+        raise SystemExit("--absgrad, --prune-screen-size and --prune-world-size need --densify-stat screen")
     if not args.pose_lr >= 0.0 or not args.pose_noise_deg >= 0.0 or not args.pose_noise_trans >= 0.0:
         raise SystemExit("--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0")
     if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
@@ -304,7 +325,11 @@ def main():
     model = gsr.densify.GaussianModel(
         P, scene_extent=gsr.densify.calculate_scene_extent([c["camera_center"] for c in cams]),
         config={"densify_from_iter": args.densify_from, "densify_until_iter": args.densify_until, "densification_interval": args.densify_interval,
-                "opacity_reset_interval": args.opacity_reset_interval, "max_allowed_prune_ratio": 1.0, "background_color": [0.0, 0.0, 0.0]})
+                "opacity_reset_interval": args.opacity_reset_interval, "max_allowed_prune_ratio": 1.0, "background_color": [0.0, 0.0, 0.0],
+                "densify_statistic": args.densify_stat, "densify_grad_threshold": args.densify_grad_threshold,
+                "prune_screen_size": args.prune_screen_size, "prune_world_size": args.prune_world_size})
+    screen_stats = args.densify_stat == "screen"
+    abs_kw = {"absgrad": True} if args.absgrad else {}
     sched = {k: gsr.scheduler.LRScheduler(lr) for k, lr in gsr.optimizer.DEFAULT_LR.items()}
     rng = np.random.default_rng(0)                                          # same stream on every rank -> same view batch
     loss_hist = torch.zeros(max(1, args.iterations), device=dev)            # the loss curve stays on the device until the end
@@ -374,7 +399,12 @@ def main():
                              radii=buf["radii"], means2D=buf["points_xy_image"], conic_opacity=buf["conic_opacity"], rgb=buf["colors"],
                              cov3Ds=buf["cov3Ds"], clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
                              img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
-                             sh_gradient="factored" if factored else "dense", camera_grad=args.optimize_poses, **aux_kw)
+                             sh_gradient="factored" if factored else "dense", camera_grad=args.optimize_poses, **aux_kw, **abs_kw)
+            if screen_stats:
+                if capacity is None:                                        # this view's statistics, on this view's stream
+                    model.stats.update(buf["radii"], g, use_abs=args.absgrad)
+                else:                                                       # --capacity: only once the overflow check has passed
+                    buf["_backward_out"] = g
             if args.optimize_poses:                                         # 35 floats back: the wait this flag accepts
                 gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
                 pose_step(v, gsr.pose.pose_gradient(start_cams[v], pose_xi[v], gv.view(4, 4), gp.view(4, 4), gc))
@@ -402,6 +432,8 @@ def main():
                     capacity_log.append({"iteration": it, "view": v, "capacity": cap["K"], "D": D})
                     cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
                     l_v, a_v, p_v = one_view(v)
+                elif screen_stats:
+                    model.stats.update(buf["radii"], buf["_backward_out"], use_abs=args.absgrad)
                 out.append((l_v, a_v, p_v))
             if sized:
                 cap["n"] = n
@@ -452,6 +484,8 @@ def main():
                 ssim_hist[it] = sum(ssim_of[v] for v in mine)[0] / len(mine)
         elif len(mine) == 1:
             pass                                                            # written by the loss kernel as a SUM: scaled once, at the end
+        if (screen_stats and world > 1 and it > args.densify_from and it < args.densify_until and it % args.densify_interval == 0):
+            gsr.dist.reduce_densify_stats(model.stats, world)               # once per density-control call: every rank marks the same rows
         log = model.densification_and_pruning(it)                           # train.py:1060
         if log["cloned"] or log["split"] or log["pruned"] or log["opacity_reset"] or log["prune_skipped"]:
             density_log.append({"iteration": it, "cloned": log["cloned"], "split": log["split"], "split_removed": log["split_removed"],

@@ -4,6 +4,7 @@
 llvm-objdump disassembles each offload bundle; branch targets, comments and inter-function padding are normalised away.
 radix_scatter_kernel gained a trailing template flag CAP (capacity mode, default false), blend_backward_splat_kernel and
 geom_backward_kernel one named AUX (include/gsr_aux_grads.h, default false; the blend kernel also two trailing pointer
+arguments), and blend_backward_splat_kernel a second one named ABS behind it (include/gsr_densify_stats.h, default false, no new
 arguments): an old instantiation is compared with its flag = false namesake.  Prints the counts and the symbols that differ, were removed or were added (JSON)."""
 import glob, os, re, shutil, subprocess, sys, tempfile, json
 OBJ = "/opt/rocm/llvm/bin/llvm-objdump"
