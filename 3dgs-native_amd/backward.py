@@ -27,20 +27,21 @@ three into the gradient of a per-view pose correction.
 
 `absgrad=True` (include/gsr_densify_stats.h, GSR_BWD_ABSGRAD) adds one key, `dL_dmean2D_abs`: an (N, 2) strided view of columns
 12-13 of the accumulator records, the sums of the MAGNITUDES of the per-(pixel, entry) terms whose signed sums are
-dL_dmean2D[:, 0:2] (AbsGS).  The call runs the flagged entry point; every other key is what the call without it returns, up to
+dL_dmean2D[:, 0:2] (AbsGS).  The flag rides on the one entry point every call runs (gsr_backward_flags); every other key is what the call without it returns, up to
 float-atomic order.  Without the keyword the two columns are zero and the key is absent.  Either way the returned `dL_dmean2D`
 carries a private tag (`_gsr_backward_ws`: workspace, its version counter, whether the absolute columns were filled) through
 which densify.DensifyStats.update finds the accumulators.
 """
 import ctypes as C
+import os
 
 import torch
 
 from . import _host, _lib
-
+from . import dist as _dist
+from . import forward as _forward
 
 _ZERO = {}
-import os
 _NO_GRAD_VIEWS = bool(int(os.environ.get("GSR_NO_GRAD_VIEWS", "0")))   # A/B switch: packed dL_dcolor / dL_dmean2D / dL_dconic arrays
 
 
@@ -73,7 +74,6 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     if dL_dpixels is None and not aux:
         raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image")
     factored = sh_gradient == "factored"
-    from . import forward as _forward
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
     L = _lib.lib()
     dev = _host.device_of(means3D, dL_dpixels, shs, radii)
@@ -179,7 +179,6 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     backward.last_call_used_forward_masks = masks is not None      # for tests and debugging
     img = _lib.GsrImage(None, None, _host.ptr(final_Ts), _host.ptr(n_contrib))
 
-    from . import dist as _dist
     o = _dist.arena_offsets(N, small=factored)     # every segment starts on a multiple of 4 floats (16-byte vector stores)
     payload = None
     arena = torch.empty(o[-1], dtype=f32, device=dev)
@@ -223,45 +222,24 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         binning = _lib.GsrBinning(D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(masks), _host.ptr(order),
                                   _host.ptr(ws) if cleared else None, 1 if cleared else 0)
         backward.last_call_skipped_the_clear = cleared     # for tests and debugging
-        if absgrad:     # the flagged pair of gsr_densify_stats.h: gsr_backward_aux's arguments and GSR_BWD_ABSGRAD
-            pg = _lib.GsrPixelGrads(_host.ptr(dpix), _host.ptr(g_depth), _host.ptr(g_alpha))
-            if on_payload is not None and payload is not None:
-                _lib.check(L.gsr_backward_blend_flags(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
-                                                      _host.ptr(payload), _host.ptr(ws), ws.numel(), _lib.BWD_ABSGRAD, stream))
-                on_payload(payload)
-                grads.dL_drgb = None
-                if aux:
-                    _lib.check(L.gsr_backward_geom_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), None, _host.ptr(ws),
-                                                       ws.numel(), stream))
-                else:
-                    _lib.check(L.gsr_backward_geom(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), _host.ptr(ws), ws.numel(),
-                                                   stream))
-            else:
-                _lib.check(L.gsr_backward_flags(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
-                                                C.byref(grads), None, _host.ptr(ws), ws.numel(), _lib.BWD_ABSGRAD, stream))
-        elif aux:
-            pg = _lib.GsrPixelGrads(_host.ptr(dpix), _host.ptr(g_depth), _host.ptr(g_alpha))
-            if on_payload is not None and payload is not None:
-                _lib.check(L.gsr_backward_blend_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
-                                                    _host.ptr(payload), _host.ptr(ws), ws.numel(), stream))
-                on_payload(payload)
-                grads.dL_drgb = None
-                _lib.check(L.gsr_backward_geom_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), None, _host.ptr(ws),
-                                                   ws.numel(), stream))
-            else:
-                _lib.check(L.gsr_backward_aux(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), C.byref(pg),
-                                              C.byref(grads), None, _host.ptr(ws), ws.numel(), stream))
-        elif on_payload is not None and payload is not None:
+        # One request, whatever the options (gsr_densify_stats.h): with no auxiliary gradient and no flag it runs gsr_backward's kernels.
+        pg = _lib.GsrPixelGrads(_host.ptr(dpix), _host.ptr(g_depth), _host.ptr(g_alpha))
+        flags = _lib.BWD_ABSGRAD if absgrad else 0
+        head = (C.byref(scene), C.byref(cam), C.byref(geom))
+        if on_payload is not None and payload is not None:
             # two halves: the view payload is complete after the blend half, so the caller's hook can start its exchange
             # (an asynchronous all-gather) while the per-Gaussian half still runs
-            _lib.check(L.gsr_backward_blend(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(dpix),
-                                            _host.ptr(payload), _host.ptr(ws), ws.numel(), stream))
+            _lib.check(L.gsr_backward_blend_flags(*head, C.byref(binning), C.byref(img), C.byref(pg), _host.ptr(payload), _host.ptr(ws),
+                                                  ws.numel(), flags, stream))
             on_payload(payload)
             grads.dL_drgb = None
-            _lib.check(L.gsr_backward_geom(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), _host.ptr(ws), ws.numel(), stream))
+            if aux:
+                _lib.check(L.gsr_backward_geom_aux(*head, C.byref(grads), None, _host.ptr(ws), ws.numel(), stream))
+            else:
+                _lib.check(L.gsr_backward_geom(*head, C.byref(grads), _host.ptr(ws), ws.numel(), stream))
         else:
-            _lib.check(L.gsr_backward(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(dpix),
-                                      C.byref(grads), _host.ptr(ws), ws.numel(), stream))
+            _lib.check(L.gsr_backward_flags(*head, C.byref(binning), C.byref(img), C.byref(pg), C.byref(grads), None, _host.ptr(ws), ws.numel(),
+                                            flags, stream))
         if camera_grad:     # after the backward, on the same stream and workspace: reads its accumulators, writes only its own output
             dcam = torch.empty(_lib.CAMERA_GRAD_FLOATS, dtype=f32, device=dev)
             scratch = torch.empty(int(L.gsr_backward_camera_scratch_bytes(N)), dtype=torch.uint8, device=dev)

@@ -526,181 +526,181 @@ int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const G
     return enqueue_render(scene, cam, geom, binning, image, gw, carve_bin(bin_ws, K), geom->point_offsets + (N - 1), shape_hint, s, st);
 }
 
-// first half: accumulator clear, record (re)pack, blend backward, optional view payload.  `aux` (include/gsr_aux_grads.h): the
-// AUX blend kernels with the inverse-depth and alpha gradients dL_dinvd / dL_dA; dL_dpixels may then be NULL, and the records
-// must carry 1/depth when dL_dinvd is given.
-static int backward_blend_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
-                               const GsrImage *image, const float *dL_dpixels, float *payload, void *ws, size_t ws_bytes, hipStream_t s, int st,
-                               bool aux = false, const float *dL_dinvd = nullptr, const float *dL_dA = nullptr, bool absgrad = false)
+} // extern "C"
+
+namespace {
+
+// ---- the backward: every exported call below fills one BwdCall.  check_bwd refuses it or passes it, whole, before anything is
+// enqueued; the two enqueue halves take a checked call.  (include/gsr.h, gsr_aux_grads.h, gsr_densify_stats.h) ----
+enum { BWD_BLEND = 1, BWD_GEOM = 2 };
+struct BwdCall {
+    const GsrScene *scene;
+    const GsrCamera *camera;
+    const GsrGeom *geom;
+    // blend half (accumulator clear, record (re)pack, blend backward, optional view payload)
+    const GsrBinning *binning;
+    const GsrImage *image;
+    GsrPixelGrads pix; // at least one; dL_dinv_depth or dL_dalpha selects the AUX blend kernels
+    float *payload;    // optional
+    // geom half (the four per-Gaussian kernels of backward_preprocess, fused)
+    const GsrGrads *grads;
+    float *dL_dinv_depths; // optional: GradRec slot 11, packed
+    void *ws;
+    size_t ws_bytes;
+    uint32_t flags; // GSR_BWD_ABSGRAD: the ABS blend kernels
+    int halves;     // BWD_BLEND | BWD_GEOM
+    bool geom_aux;  // the AUX per-Gaussian kernel whatever the pixel gradients are (gsr_backward_geom_aux)
+    void *stream;
+};
+GsrPixelGrads pix_of(const GsrPixelGrads *pg) { return pg ? *pg : GsrPixelGrads{}; }
+
+// the pieces gsr_backward_camera checks too
+bool geom_core(const GsrGeom *g) { return g && g->radii && g->clamped_state; } // (cov3D may be NULL: recomputed, gsr.h GsrGeom)
+bool bwd_ws_fits(const void *ws, size_t ws_bytes, const GsrScene *sc, const GsrCamera *cam)
 {
-    const int64_t N = scene->N;
-    if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // (cov3D may be NULL: gsr.h GsrGeom)
-    if (!geom->blend_records && (!geom->xy || !geom->rgb || !geom->conic_opacity)) return GSR_E_NULL; // the records, or what they are rebuilt from
-    if (!binning || !image || (!dL_dpixels && !(aux && (dL_dinvd || dL_dA)))) return GSR_E_NULL;
-    if (dL_dinvd && !geom->blend_records && !geom->depths) return GSR_E_NULL; // a re-pack without depths would carry invd = 0
-    if (!geom_aligned(geom) || !gsr_aligned16(ws) || !gsr_aligned16(binning->point_list) || !gsr_aligned16(binning->ranges) ||
-        !gsr_aligned16(binning->block_masks) || !gsr_aligned16(binning->block_order) ||
-        !gsr_aligned16(image->final_T) || !gsr_aligned16(image->n_contrib) || !gsr_aligned16(dL_dpixels) || !gsr_aligned16(payload) ||
-        !gsr_aligned16(dL_dinvd) || !gsr_aligned16(dL_dA))
-        return GSR_E_ALIGN;
-    const int64_t D = binning->D;
-    if (D < 0 || D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
-    if (D > 0 && (!binning->point_list || !binning->ranges || !image->final_T || !image->n_contrib)) return GSR_E_NULL;
-    if (!ws || ws_bytes < gsr_backward_workspace_bytes(N, D, camera->W, camera->H)) return GSR_E_WORKSPACE;
-    const CamK cam = make_cam(camera);
-    const BwdWs bw = carve_bwd(ws, N);
+    return ws && ws_bytes >= gsr_backward_workspace_bytes(sc->N, 0, cam->W, cam->H); // (the size does not depend on D)
+}
+
+// Every argument of the halves the call runs, in the order NULL, ALIGN, OVERFLOW, WORKSPACE; nothing is enqueued.  GSR_OK with
+// N == 0 means there is nothing to do (and nothing else was looked at).
+int check_bwd(const BwdCall &c)
+{
+    if (c.flags & ~GSR_BWD_ABSGRAD) return GSR_E_DIMS;
+    if (int rc = check_scene_cam(c.scene, c.camera)) return rc;
+    if (c.scene->N == 0) return GSR_OK;
+    const GsrGeom *g = c.geom;
+    const GsrGrads *gr = c.grads;
+    const GsrBinning *b = c.binning;
+    const GsrImage *img = c.image;
+    const bool blend = c.halves & BWD_BLEND, per_gaussian = c.halves & BWD_GEOM;
+    // dL_dshs and dL_drgb may both be NULL in a geom half alone: the payload was taken from the blend half and the SH gradient is
+    // rebuilt later (dL_dcolor / dL_dmean2D / dL_dconic may each be NULL: columns of the accumulator records in `ws`, gsr.h GsrGrads)
+    if (per_gaussian && (!gr || !gr->dL_dmean3D || !gr->dL_dscale || !gr->dL_drot || !gr->dL_dopacity || (blend && !gr->dL_dshs && !gr->dL_drgb)))
+        return GSR_E_NULL;
+    if (!geom_core(g)) return GSR_E_NULL;
+    if (blend) {
+        if (!g->blend_records && (!g->xy || !g->rgb || !g->conic_opacity)) return GSR_E_NULL; // the records, or what they are rebuilt from
+        if (!b || !img || (!c.pix.dL_dpixels && !c.pix.dL_dinv_depth && !c.pix.dL_dalpha)) return GSR_E_NULL;
+        if (c.pix.dL_dinv_depth && !g->blend_records && !g->depths) return GSR_E_NULL; // a re-pack without depths would carry invd = 0
+    }
+    if (!geom_aligned(g) || !gsr_aligned16(c.ws)) return GSR_E_ALIGN;
+    if (per_gaussian && (!grads_aligned(gr) || !gsr_aligned16(c.dL_dinv_depths))) return GSR_E_ALIGN;
+    if (blend) {
+        if (!gsr_aligned16(b->point_list) || !gsr_aligned16(b->ranges) || !gsr_aligned16(b->block_masks) || !gsr_aligned16(b->block_order) ||
+            !gsr_aligned16(img->final_T) || !gsr_aligned16(img->n_contrib) || !gsr_aligned16(c.pix.dL_dpixels) || !gsr_aligned16(c.payload) ||
+            !gsr_aligned16(c.pix.dL_dinv_depth) || !gsr_aligned16(c.pix.dL_dalpha))
+            return GSR_E_ALIGN;
+        if (b->D < 0 || b->D > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
+        if (b->D > 0 && (!b->point_list || !b->ranges || !img->final_T || !img->n_contrib)) return GSR_E_NULL;
+    }
+    return bwd_ws_fits(c.ws, c.ws_bytes, c.scene, c.camera) ? GSR_OK : GSR_E_WORKSPACE;
+}
+
+int enqueue_bwd_blend(const BwdCall &c, const CamK &cam, const BwdWs &bw, hipStream_t s, int st)
+{
+    const GsrBinning *b = c.binning;
+    const int64_t N = c.scene->N, D = b->D;
     mark(st, 10, s);
     // (unless gsr_forward_render cleared this very workspace's accumulators in its blend kernel and nothing has used it since)
-    if (!(binning->backward_ws_cleared && binning->backward_ws == ws)) HIP_TRY(hipMemsetAsync(bw.acc, 0, sizeof(GradRec) * (size_t)N, s));
-    const BlendRec *records = (const BlendRec *)geom->blend_records;
+    if (!(b->backward_ws_cleared && b->backward_ws == c.ws)) HIP_TRY(hipMemsetAsync(bw.acc, 0, sizeof(GradRec) * (size_t)N, s));
+    const BlendRec *records = (const BlendRec *)c.geom->blend_records;
     if (D > 0 && !records) {
-        HIP_TRY(gsr_launch_pack_records(*geom, bw.rec, N, s));
+        HIP_TRY(gsr_launch_pack_records(*c.geom, bw.rec, N, s));
         records = bw.rec;
     }
     mark(st, 11, s);
-    if (D > 0) HIP_TRY(gsr_launch_blend_backward_splat(cam, binning->ranges, binning->point_list, records, *image, dL_dpixels, binning->block_masks,
-                                                       binning->block_masks ? binning->block_order : nullptr, bw.acc, N, D, s, aux,
-                                                       dL_dinvd, dL_dA, absgrad));
+    if (D > 0) HIP_TRY(gsr_launch_blend_backward_splat(cam, b->ranges, b->point_list, records, *c.image, c.pix.dL_dpixels, b->block_masks,
+                                                       b->block_masks ? b->block_order : nullptr, bw.acc, N, D, s, c.pix.dL_dinv_depth || c.pix.dL_dalpha,
+                                                       c.pix.dL_dinv_depth, c.pix.dL_dalpha, (c.flags & GSR_BWD_ABSGRAD) != 0));
     mark(st, 12, s);
-    if (payload) HIP_TRY(gsr_launch_view_payload(*scene, cam, *geom, bw.acc, payload, s));
+    if (c.payload) HIP_TRY(gsr_launch_view_payload(*c.scene, cam, *c.geom, bw.acc, c.payload, s));
     return GSR_OK;
 }
 
-// second half: the four per-Gaussian kernels of backward_preprocess, fused
-static int backward_geom_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, void *ws,
-                              size_t ws_bytes, hipStream_t s, int st, bool aux = false, float *dL_dinv_depths = nullptr)
+int enqueue_bwd_geom(const BwdCall &c, const CamK &cam, const BwdWs &bw, hipStream_t s, int st)
 {
-    const int64_t N = scene->N;
-    // dL_dshs and dL_drgb may both be NULL here: the payload was taken from the blend half and the SH gradient is rebuilt later
-    // (dL_dcolor / dL_dmean2D / dL_dconic may each be NULL: they are columns of the accumulator records in `ws`, gsr.h GsrGrads)
-    if (!grads || !grads->dL_dmean3D || !grads->dL_dscale || !grads->dL_drot || !grads->dL_dopacity) return GSR_E_NULL;
-    if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // cov3D NULL: recomputed from scales / rotations (gsr.h GsrGeom)
-    if (!geom_aligned(geom) || !grads_aligned(grads) || !gsr_aligned16(ws) || !gsr_aligned16(dL_dinv_depths)) return GSR_E_ALIGN;
-    if (!ws || ws_bytes < gsr_backward_workspace_bytes(N, 0, camera->W, camera->H)) return GSR_E_WORKSPACE;
-    const CamK cam = make_cam(camera);
-    const BwdWs bw = carve_bwd(ws, N);
-    HIP_TRY(gsr_launch_geom_backward(*scene, cam, *geom, bw.acc, *grads, s, aux));
-    if (dL_dinv_depths) // column 11 of the accumulator records (gsr_gradrec_slot(9)), packed
-        HIP_TRY(hipMemcpy2DAsync(dL_dinv_depths, sizeof(float), &bw.acc[0].f[gsr_gradrec_slot(9)], sizeof(GradRec), sizeof(float), (size_t)N,
-                                 hipMemcpyDeviceToDevice, s));
+    const bool aux = c.geom_aux || c.pix.dL_dinv_depth || c.pix.dL_dalpha || c.dL_dinv_depths;
+    HIP_TRY(gsr_launch_geom_backward(*c.scene, cam, *c.geom, bw.acc, *c.grads, s, aux));
+    if (c.dL_dinv_depths) // column 11 of the accumulator records (gsr_gradrec_slot(9)), packed
+        HIP_TRY(hipMemcpy2DAsync(c.dL_dinv_depths, sizeof(float), &bw.acc[0].f[gsr_gradrec_slot(9)], sizeof(GradRec), sizeof(float),
+                                 (size_t)c.scene->N, hipMemcpyDeviceToDevice, s));
     mark(st, 13, s);
     return GSR_OK;
 }
 
-int gsr_backward(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                 const float *dL_dpixels, const GsrGrads *grads, void *ws, size_t ws_bytes, void *stream)
+int run_bwd(const BwdCall &c)
 {
     read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (scene->N == 0) return GSR_OK;
-    if (!grads || !grads->dL_dmean3D || !grads->dL_dscale || !grads->dL_drot || !grads->dL_dopacity || (!grads->dL_dshs && !grads->dL_drgb))
-        return GSR_E_NULL;
-    hipStream_t s = (hipStream_t)stream;
-    const int st = timer_open(false);
-    if (int rc = backward_blend_impl(scene, camera, geom, binning, image, dL_dpixels, nullptr, ws, ws_bytes, s, st)) return rc;
-    if (int rc = backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, s, st)) return rc;
-    return GSR_OK;
+    if (int rc = check_bwd(c)) return rc;
+    if (c.scene->N == 0) return GSR_OK;
+    // stage events: a whole call opens its own record; the two halves of a split one share a record, opened by the blend half
+    // and closed by the geom half
+    const int st = (c.halves & BWD_BLEND) ? timer_open(false) : t_bwd_record;
+    if (c.halves != (BWD_BLEND | BWD_GEOM)) t_bwd_record = (c.halves & BWD_BLEND) ? st : -1;
+    hipStream_t s = (hipStream_t)c.stream;
+    const CamK cam = make_cam(c.camera);
+    const BwdWs bw = carve_bwd(c.ws, c.scene->N);
+    if (int rc = (c.halves & BWD_BLEND) ? enqueue_bwd_blend(c, cam, bw, s, st) : GSR_OK) return rc;
+    return (c.halves & BWD_GEOM) ? enqueue_bwd_geom(c, cam, bw, s, st) : GSR_OK;
 }
 
-int gsr_backward_blend(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                       const float *dL_dpixels, float *payload, void *ws, size_t ws_bytes, void *stream)
-{
-    read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (scene->N == 0) return GSR_OK;
-    // stage events: the two halves of one backward share a record; it is opened here and closed by gsr_backward_geom
-    t_bwd_record = timer_open(false);
-    return backward_blend_impl(scene, camera, geom, binning, image, dL_dpixels, payload, ws, ws_bytes, (hipStream_t)stream, t_bwd_record);
-}
+} // namespace
 
-int gsr_backward_geom(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, void *ws, size_t ws_bytes,
-                      void *stream)
-{
-    read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (scene->N == 0) return GSR_OK;
-    const int st = t_bwd_record;
-    t_bwd_record = -1;
-    return backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, (hipStream_t)stream, st);
-}
+extern "C" {
 
-// ---- include/gsr_aux_grads.h: the backward through the inverse-depth and alpha images ----
-// Every argument of both halves is checked before the blend half enqueues anything.  With neither auxiliary gradient (and no
-// dL_dinv_depths) the call is gsr_backward's own: the same kernels, bit for bit.
-// (`absgrad`: include/gsr_densify_stats.h, GSR_BWD_ABSGRAD -- the ABS blend kernels; everything else is the same call)
-static int backward_aux_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                             const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, bool absgrad,
-                             void *stream)
-{
-    read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (scene->N == 0) return GSR_OK;
-    if (!pixel_grads) return GSR_E_NULL;
-    if (!grads || !grads->dL_dmean3D || !grads->dL_dscale || !grads->dL_drot || !grads->dL_dopacity || (!grads->dL_dshs && !grads->dL_drgb))
-        return GSR_E_NULL;
-    if (!grads_aligned(grads) || !gsr_aligned16(dL_dinv_depths)) return GSR_E_ALIGN; // (the geom half's one check the blend half lacks)
-    const bool aux = pixel_grads->dL_dinv_depth || pixel_grads->dL_dalpha;
-    hipStream_t s = (hipStream_t)stream;
-    const int st = timer_open(false);
-    if (int rc = backward_blend_impl(scene, camera, geom, binning, image, pixel_grads->dL_dpixels, nullptr, ws, ws_bytes, s, st, aux,
-                                     pixel_grads->dL_dinv_depth, pixel_grads->dL_dalpha, absgrad))
-        return rc;
-    if (int rc = backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, s, st, aux || dL_dinv_depths, dL_dinv_depths)) return rc;
-    return GSR_OK;
-}
-
-int gsr_backward_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                     const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, void *stream)
-{
-    return backward_aux_impl(scene, camera, geom, binning, image, pixel_grads, grads, dL_dinv_depths, ws, ws_bytes, false, stream);
-}
-
-static int backward_blend_aux_impl(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning,
-                                   const GsrImage *image, const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, bool absgrad,
-                                   void *stream)
-{
-    read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (scene->N == 0) return GSR_OK;
-    if (!pixel_grads) return GSR_E_NULL;
-    t_bwd_record = timer_open(false);
-    return backward_blend_impl(scene, camera, geom, binning, image, pixel_grads->dL_dpixels, payload, ws, ws_bytes, (hipStream_t)stream,
-                               t_bwd_record, pixel_grads->dL_dinv_depth || pixel_grads->dL_dalpha, pixel_grads->dL_dinv_depth,
-                               pixel_grads->dL_dalpha, absgrad);
-}
-
-int gsr_backward_blend_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
-                           const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, void *stream)
-{
-    return backward_blend_aux_impl(scene, camera, geom, binning, image, pixel_grads, payload, ws, ws_bytes, false, stream);
-}
-
-// ---- include/gsr_densify_stats.h: the same two calls with flags (GSR_BWD_ABSGRAD: the ABS blend kernels) ----
+// (include/gsr_densify_stats.h) the whole call and its blend half: every other whole or blend call below is one of these two
 int gsr_backward_flags(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
                        const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, uint32_t flags,
                        void *stream)
 {
-    if (flags & ~GSR_BWD_ABSGRAD) return GSR_E_DIMS;
-    return backward_aux_impl(scene, camera, geom, binning, image, pixel_grads, grads, dL_dinv_depths, ws, ws_bytes, (flags & GSR_BWD_ABSGRAD) != 0,
-                             stream);
+    return run_bwd({scene, camera, geom, binning, image, pix_of(pixel_grads), nullptr, grads, dL_dinv_depths, ws, ws_bytes, flags,
+                    BWD_BLEND | BWD_GEOM, false, stream});
 }
 
 int gsr_backward_blend_flags(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
                              const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, uint32_t flags, void *stream)
 {
-    if (flags & ~GSR_BWD_ABSGRAD) return GSR_E_DIMS;
-    return backward_blend_aux_impl(scene, camera, geom, binning, image, pixel_grads, payload, ws, ws_bytes, (flags & GSR_BWD_ABSGRAD) != 0, stream);
+    return run_bwd({scene, camera, geom, binning, image, pix_of(pixel_grads), payload, nullptr, nullptr, ws, ws_bytes, flags, BWD_BLEND, false, stream});
+}
+
+// (include/gsr_aux_grads.h) with neither auxiliary gradient and no dL_dinv_depths the whole call runs gsr_backward's kernels, bit for bit
+int gsr_backward_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                     const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, void *stream)
+{
+    return gsr_backward_flags(scene, camera, geom, binning, image, pixel_grads, grads, dL_dinv_depths, ws, ws_bytes, 0, stream);
+}
+
+int gsr_backward_blend_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                           const GsrPixelGrads *pixel_grads, float *payload, void *ws, size_t ws_bytes, void *stream)
+{
+    return gsr_backward_blend_flags(scene, camera, geom, binning, image, pixel_grads, payload, ws, ws_bytes, 0, stream);
 }
 
 int gsr_backward_geom_aux(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, float *dL_dinv_depths,
                           void *ws, size_t ws_bytes, void *stream)
 {
-    read_tuning();
-    if (int rc = check_scene_cam(scene, camera)) return rc;
-    if (scene->N == 0) return GSR_OK;
-    const int st = t_bwd_record;
-    t_bwd_record = -1;
-    return backward_geom_impl(scene, camera, geom, grads, ws, ws_bytes, (hipStream_t)stream, st, true, dL_dinv_depths);
+    return run_bwd({scene, camera, geom, nullptr, nullptr, {}, nullptr, grads, dL_dinv_depths, ws, ws_bytes, 0, BWD_GEOM, true, stream});
+}
+
+// (include/gsr.h) the same three with the colour image's gradient alone
+int gsr_backward(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                 const float *dL_dpixels, const GsrGrads *grads, void *ws, size_t ws_bytes, void *stream)
+{
+    const GsrPixelGrads pg{dL_dpixels, nullptr, nullptr};
+    return gsr_backward_flags(scene, camera, geom, binning, image, &pg, grads, nullptr, ws, ws_bytes, 0, stream);
+}
+
+int gsr_backward_blend(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                       const float *dL_dpixels, float *payload, void *ws, size_t ws_bytes, void *stream)
+{
+    const GsrPixelGrads pg{dL_dpixels, nullptr, nullptr};
+    return gsr_backward_blend_flags(scene, camera, geom, binning, image, &pg, payload, ws, ws_bytes, 0, stream);
+}
+
+int gsr_backward_geom(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, void *ws, size_t ws_bytes,
+                      void *stream)
+{
+    return run_bwd({scene, camera, geom, nullptr, nullptr, {}, nullptr, grads, nullptr, ws, ws_bytes, 0, BWD_GEOM, false, stream});
 }
 
 // ---- include/gsr_camera_grads.h: dL/d(view, proj, campos) from the accumulators a backward left in `ws` ----
@@ -714,16 +714,15 @@ int gsr_backward_camera(const GsrScene *scene, const GsrCamera *camera, const Gs
     if (!dL_dcamera) return GSR_E_NULL;
     if (!gsr_aligned16(dL_dcamera) || !gsr_aligned16(ws) || !gsr_aligned16(scratch)) return GSR_E_ALIGN;
     const int64_t N = scene->N;
-    hipStream_t s = (hipStream_t)stream;
-    if (N > 0) {
-        if (!geom || !geom->radii || !geom->clamped_state) return GSR_E_NULL; // (cov3D and sh_dir_grad are optional)
+    if (N > 0) { // (the backward's own checks of geom and ws; cov3D and sh_dir_grad are optional)
+        if (!geom_core(geom)) return GSR_E_NULL;
         if (!geom_aligned(geom)) return GSR_E_ALIGN;
-        if (!ws || ws_bytes < gsr_backward_workspace_bytes(N, 0, camera->W, camera->H)) return GSR_E_WORKSPACE;
+        if (!bwd_ws_fits(ws, ws_bytes, scene, camera)) return GSR_E_WORKSPACE;
         if (!scratch || scratch_bytes < gsr_camera_scratch_bytes(N)) return GSR_E_WORKSPACE;
     }
     const CamK cam = make_cam(camera);
     const GradRec *acc = N > 0 ? carve_bwd(const_cast<void *>(ws), N).acc : nullptr;
-    HIP_TRY(gsr_launch_camera_backward(*scene, cam, N > 0 ? *geom : GsrGeom{}, acc, dL_dcamera, scratch, s));
+    HIP_TRY(gsr_launch_camera_backward(*scene, cam, N > 0 ? *geom : GsrGeom{}, acc, dL_dcamera, scratch, (hipStream_t)stream));
     return GSR_OK;
 }
 

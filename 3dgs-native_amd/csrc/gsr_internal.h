@@ -257,12 +257,12 @@ hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *range
                                            const uint8_t *block_masks /* optional: the forward's */,
                                            const int32_t *block_order /* optional: the forward's, with its masks */, GradRec *acc,
                                            int64_t N, int64_t D /* choose the block size */, hipStream_t s,
-                                           bool aux = false /* the AUX kernels (include/gsr_aux_grads.h), with: */,
-                                           const float *dL_dinv_depth = nullptr, const float *dL_dalpha = nullptr,
-                                           bool absgrad = false /* the ABS kernels (include/gsr_densify_stats.h): |dL/dmean2D| terms into columns 12-13 */);
+                                           bool aux /* the AUX kernels (include/gsr_aux_grads.h), with: */,
+                                           const float *dL_dinv_depth, const float *dL_dalpha,
+                                           bool absgrad /* the ABS kernels (include/gsr_densify_stats.h): |dL/dmean2D| terms into columns 12-13 */);
 // aux: the AUX instantiation, which also adds the inverse-depth gradient's z term (GradRec slot 11) into dL_dmean3D
 hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc,
-                                    const GsrGrads &gr, hipStream_t s, bool aux = false);
+                                    const GsrGrads &gr, hipStream_t s, bool aux);
 
 // tuning knobs (read once from the environment by api.hip; defaults are the measured best)
 hipError_t gsr_launch_view_payload(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *payload, hipStream_t s);

@@ -219,7 +219,8 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
 /* backward(): wp_render_backward_kernel + the four per-Gaussian kernels
  * (reference backward.py:890-953, :770-888).  dL_dpixels is [H*W*3].  Reads xy / conic_opacity / rgb /
  * radii / cov3D / clamped_state from *geom and point_list / ranges / final_T / n_contrib from
- * *binning / *image. */
+ * *binning / *image.  Every argument, *grads included, is checked before anything is enqueued: a
+ * refused call leaves nothing on the stream. */
 int gsr_backward(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom,
                  const GsrBinning *binning, const GsrImage *image, const float *dL_dpixels,
                  const GsrGrads *grads, void *ws, size_t ws_bytes, void *stream);

@@ -9,15 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from abi_helpers import libpath  # noqa: F401  (a fixture)
 from conftest import ROOT, PKG_NAME, lego_camera, sub
-
-
-@pytest.fixture(scope="module")
-def libpath():
-    path = os.path.join(ROOT, PKG_NAME, "libgsr_hip.so")
-    if not os.path.exists(path):   # hipcc cross-compiles gfx950 without a GPU
-        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, PKG_NAME, "csrc")])
-    return path
 
 
 def test_every_declared_symbol_is_exported(libpath):
@@ -257,6 +250,11 @@ def test_alignment_and_capacity_are_checked_before_any_hip_call(libpath):
         assert rc == _lib.GSR_E_ALIGN, (pairs, rc)
     grads = _lib.GsrGrads(A, A, A + 4, A, A, A, A, A, None)
     rc = L.gsr_backward_geom(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(grads), A, 1 << 30, None)
+    assert rc == _lib.GSR_E_ALIGN
+    # the whole call checks the per-Gaussian half too before it enqueues the blend half: a refused call leaves nothing on the stream
+    # (every other argument here is acceptable, so a blend half enqueued first would have met the fake pointers)
+    binning = _lib.GsrBinning(100, A, A, None, None, None, 0)
+    rc = L.gsr_backward(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), A, C.byref(grads), A, 1 << 30, None)
     assert rc == _lib.GSR_E_ALIGN
     with pytest.raises(RuntimeError, match="aligned"):
         _lib.check(_lib.GSR_E_ALIGN)

@@ -5,7 +5,6 @@ library exports its entry points, every argument is checked before anything is e
 flags, and dist.reduce_densify_stats sums / maximises over two gloo ranks."""
 import ctypes as C
 import os
-import re
 import socket
 import subprocess
 import sys
@@ -15,6 +14,7 @@ import pytest
 import torch
 import torch.multiprocessing as mp
 
+from abi_helpers import compile_c99_probe, declared_names, fake_call_setup, libpath  # noqa: F401  (libpath: a fixture)
 from conftest import ROOT, PKG_NAME, sub
 import absgrad_reference as AR
 import f64_reference as F
@@ -22,14 +22,6 @@ import test_f64_reference as R
 
 HDR = os.path.join(ROOT, "include", "gsr_densify_stats.h")
 NAMES = {"gsr_backward_flags", "gsr_backward_blend_flags", "gsr_densify_stats_update", "gsr_densify_mark_stats", "gsr_prune_mark_stats"}
-
-
-@pytest.fixture(scope="module")
-def libpath():
-    path = os.path.join(ROOT, PKG_NAME, "libgsr_hip.so")
-    if not os.path.exists(path):   # hipcc cross-compiles gfx950 without a GPU
-        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, PKG_NAME, "csrc")])
-    return path
 
 
 # ---- the yardstick ----
@@ -89,27 +81,22 @@ def test_yardstick_per_pixel_terms_are_autograd_of_the_f64_blend(oracle, cameras
 
 # ---- header, exports ----
 def test_densify_stats_header_is_plain_c99(tmp_path):
-    probe = tmp_path / "probe.c"
-    probe.write_text('#include "gsr_densify_stats.h"\n'
-                     'int main(void) {\n'
-                     '  GsrDensifyStats st = {0, 0, 0, 0};\n'
-                     '  uint32_t f = GSR_BWD_ABSGRAD;\n'
-                     '  int (*a)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
-                     '           const GsrPixelGrads *, const GsrGrads *, float *, void *, size_t, uint32_t, void *) = gsr_backward_flags;\n'
-                     '  int (*b)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
-                     '           const GsrPixelGrads *, float *, void *, size_t, uint32_t, void *) = gsr_backward_blend_flags;\n'
-                     '  int (*u)(const GsrDensifyStats *, const int32_t *, const void *, size_t, int32_t, void *) = gsr_densify_stats_update;\n'
-                     '  int (*m)(const GsrParams *, const GsrDensifyStats *, float, float, float, int, int32_t *, void *) = gsr_densify_mark_stats;\n'
-                     '  int (*p)(const GsrParams *, const GsrDensifyStats *, float, float, float, int32_t *, void *) = gsr_prune_mark_stats;\n'
-                     '  (void)st; (void)f; (void)a; (void)b; (void)u; (void)m; (void)p; return 0; }\n')
-    p = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(probe),
-                        "-o", str(tmp_path / "probe.o")], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
+    compile_c99_probe(tmp_path, '#include "gsr_densify_stats.h"\n'
+                                'int main(void) {\n'
+                                '  GsrDensifyStats st = {0, 0, 0, 0};\n'
+                                '  uint32_t f = GSR_BWD_ABSGRAD;\n'
+                                '  int (*a)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
+                                '           const GsrPixelGrads *, const GsrGrads *, float *, void *, size_t, uint32_t, void *) = gsr_backward_flags;\n'
+                                '  int (*b)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
+                                '           const GsrPixelGrads *, float *, void *, size_t, uint32_t, void *) = gsr_backward_blend_flags;\n'
+                                '  int (*u)(const GsrDensifyStats *, const int32_t *, const void *, size_t, int32_t, void *) = gsr_densify_stats_update;\n'
+                                '  int (*m)(const GsrParams *, const GsrDensifyStats *, float, float, float, int, int32_t *, void *) = gsr_densify_mark_stats;\n'
+                                '  int (*p)(const GsrParams *, const GsrDensifyStats *, float, float, float, int32_t *, void *) = gsr_prune_mark_stats;\n'
+                                '  (void)st; (void)f; (void)a; (void)b; (void)u; (void)m; (void)p; return 0; }\n')
 
 
 def test_densify_stats_entry_points_are_exported_bound_and_documented(libpath):
-    code = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", code))
+    declared = declared_names(HDR)
     assert declared == NAMES
     _lib = sub("_lib")
     assert set(_lib.DENSIFY_STATS_EXPORTS) == declared
@@ -130,13 +117,7 @@ def test_densify_stats_entry_points_are_exported_bound_and_documented(libpath):
 # ---- argument checks ----
 def test_flagged_backward_arguments_are_checked_before_any_hip_call(libpath):
     """Fake 16-byte-aligned pointers: every case below returns before anything is dereferenced or enqueued."""
-    _lib = sub("_lib")
-    L = _lib.lib()
-    A = 0x10000
-    N, W, H = 8, 32, 32
-    scene = _lib.GsrScene(N, A, A, A, A, A, 3, 1.0, 1)
-    cam = _lib.GsrCamera()
-    cam.W, cam.H, cam.tan_fovx, cam.tan_fovy = W, H, 0.5, 0.5
+    _lib, L, A, N, W, H, scene, cam = fake_call_setup()
     ws_bytes = int(L.gsr_backward_workspace_bytes(N, 100, W, H))
     img = _lib.GsrImage(None, None, A, A)
     geom = _lib.GsrGeom(A, None, None, A, None, A, A, A, A, A, None)

@@ -5,7 +5,6 @@ the library exports its entry points, every argument is checked before anything 
 import ctypes as C
 import importlib.util
 import os
-import re
 import subprocess
 import sys
 
@@ -13,43 +12,31 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, PKG_NAME, sub
+from abi_helpers import compile_c99_probe, declared_names, fake_call_setup, libpath  # noqa: F401  (libpath: a fixture)
+from conftest import ROOT, sub
 import f64_reference as F
 
 HDR = os.path.join(ROOT, "include", "gsr_aux_grads.h")
 AUX_NAMES = {"gsr_backward_aux", "gsr_backward_blend_aux", "gsr_backward_geom_aux", "gsr_depth_loss_grad", "gsr_alpha_loss_grad"}
 
 
-@pytest.fixture(scope="module")
-def libpath():
-    path = os.path.join(ROOT, PKG_NAME, "libgsr_hip.so")
-    if not os.path.exists(path):   # hipcc cross-compiles gfx950 without a GPU
-        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, PKG_NAME, "csrc")])
-    return path
-
-
 def test_aux_header_is_plain_c99(tmp_path):
-    probe = tmp_path / "probe.c"
-    probe.write_text('#include "gsr_aux_grads.h"\n'
-                     'int main(void) {\n'
-                     '  GsrPixelGrads pg = {0, 0, 0};\n'
-                     '  int (*a)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
-                     '           const GsrPixelGrads *, const GsrGrads *, float *, void *, size_t, void *) = gsr_backward_aux;\n'
-                     '  int (*b)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
-                     '           const GsrPixelGrads *, float *, void *, size_t, void *) = gsr_backward_blend_aux;\n'
-                     '  int (*g)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrGrads *, float *, void *, size_t, void *)\n'
-                     '      = gsr_backward_geom_aux;\n'
-                     '  int (*d)(const float *, const float *, const float *, float *, float *, int32_t, int32_t, float, void *) = gsr_depth_loss_grad;\n'
-                     '  int (*l)(const float *, const float *, const float *, float *, float *, int32_t, int32_t, float, void *) = gsr_alpha_loss_grad;\n'
-                     '  (void)pg; (void)a; (void)b; (void)g; (void)d; (void)l; return 0; }\n')
-    p = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(probe),
-                        "-o", str(tmp_path / "probe.o")], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
+    compile_c99_probe(tmp_path, '#include "gsr_aux_grads.h"\n'
+                                'int main(void) {\n'
+                                '  GsrPixelGrads pg = {0, 0, 0};\n'
+                                '  int (*a)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
+                                '           const GsrPixelGrads *, const GsrGrads *, float *, void *, size_t, void *) = gsr_backward_aux;\n'
+                                '  int (*b)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
+                                '           const GsrPixelGrads *, float *, void *, size_t, void *) = gsr_backward_blend_aux;\n'
+                                '  int (*g)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrGrads *, float *, void *, size_t, void *)\n'
+                                '      = gsr_backward_geom_aux;\n'
+                                '  int (*d)(const float *, const float *, const float *, float *, float *, int32_t, int32_t, float, void *) = gsr_depth_loss_grad;\n'
+                                '  int (*l)(const float *, const float *, const float *, float *, float *, int32_t, int32_t, float, void *) = gsr_alpha_loss_grad;\n'
+                                '  (void)pg; (void)a; (void)b; (void)g; (void)d; (void)l; return 0; }\n')
 
 
 def test_aux_entry_points_are_exported_bound_and_documented(libpath):
-    code = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", code))
+    declared = declared_names(HDR)
     assert declared == AUX_NAMES
     _lib = sub("_lib")
     assert set(_lib.AUX_EXPORTS) == declared
@@ -64,20 +51,9 @@ def test_aux_entry_points_are_exported_bound_and_documented(libpath):
         assert name not in open(os.path.join(ROOT, "include", "gsr.h")).read()
 
 
-def _fake_call_setup():
-    _lib = sub("_lib")
-    L = _lib.lib()
-    A = 0x10000
-    N, W, H = 8, 32, 32
-    scene = _lib.GsrScene(N, A, A, A, A, A, 3, 1.0, 1)
-    cam = _lib.GsrCamera()
-    cam.W, cam.H, cam.tan_fovx, cam.tan_fovy = W, H, 0.5, 0.5
-    return _lib, L, A, N, W, H, scene, cam
-
-
 def test_aux_backward_arguments_are_checked_before_any_hip_call(libpath):
     """Fake 16-byte-aligned pointers: every case below returns before anything is dereferenced or enqueued."""
-    _lib, L, A, N, W, H, scene, cam = _fake_call_setup()
+    _lib, L, A, N, W, H, scene, cam = fake_call_setup()
     ws_bytes = int(L.gsr_backward_workspace_bytes(N, 100, W, H))
     img = _lib.GsrImage(None, None, A, A)
 
@@ -131,7 +107,7 @@ def test_aux_backward_arguments_are_checked_before_any_hip_call(libpath):
 
 
 def test_aux_loss_arguments_are_checked_before_any_hip_call(libpath):
-    _lib, L, A, N, W, H, scene, cam = _fake_call_setup()
+    _lib, L, A, N, W, H, scene, cam = fake_call_setup()
     for fn in (L.gsr_depth_loss_grad, L.gsr_alpha_loss_grad):
         assert fn(None, A, None, A, A, W, H, 1.0, None) == _lib.GSR_E_NULL
         assert fn(A, None, A, A, A, W, H, 1.0, None) == _lib.GSR_E_NULL

@@ -6,7 +6,6 @@ matrix exponential), apply_pose_delta(cam, 0) is the camera bit for bit, and the
 several GPUs and a negative --pose-lr."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
@@ -14,7 +13,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import ROOT, PKG_NAME, sub
+from abi_helpers import compile_c99_probe, declared_names, fake_call_setup, libpath  # noqa: F401  (libpath: a fixture)
+from conftest import ROOT, sub
 import camera_grad_reference as CG
 import test_f64_reference as R
 
@@ -22,31 +22,18 @@ HDR = os.path.join(ROOT, "include", "gsr_camera_grads.h")
 CAM_NAMES = {"gsr_backward_camera", "gsr_backward_camera_scratch_bytes"}
 
 
-@pytest.fixture(scope="module")
-def libpath():
-    path = os.path.join(ROOT, PKG_NAME, "libgsr_hip.so")
-    if not os.path.exists(path):   # hipcc cross-compiles gfx950 without a GPU
-        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, PKG_NAME, "csrc")])
-    return path
-
-
 def test_camera_header_is_plain_c99(tmp_path):
-    probe = tmp_path / "probe.c"
-    probe.write_text('#include "gsr_camera_grads.h"\n'
-                     'int main(void) {\n'
-                     '  int (*c)(const GsrScene *, const GsrCamera *, const GsrGeom *, float *, const void *, size_t, void *, size_t,\n'
-                     '           void *) = gsr_backward_camera;\n'
-                     '  size_t (*s)(int64_t) = gsr_backward_camera_scratch_bytes;\n'
-                     '  float out[GSR_CAMERA_GRAD_FLOATS];\n'
-                     '  (void)c; (void)s; (void)out; return 0; }\n')
-    p = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(probe),
-                        "-o", str(tmp_path / "probe.o")], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
+    compile_c99_probe(tmp_path, '#include "gsr_camera_grads.h"\n'
+                                'int main(void) {\n'
+                                '  int (*c)(const GsrScene *, const GsrCamera *, const GsrGeom *, float *, const void *, size_t, void *, size_t,\n'
+                                '           void *) = gsr_backward_camera;\n'
+                                '  size_t (*s)(int64_t) = gsr_backward_camera_scratch_bytes;\n'
+                                '  float out[GSR_CAMERA_GRAD_FLOATS];\n'
+                                '  (void)c; (void)s; (void)out; return 0; }\n')
 
 
 def test_camera_entry_points_are_exported_bound_and_documented(libpath):
-    code = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", code))
+    declared = declared_names(HDR)
     assert declared == CAM_NAMES
     _lib = sub("_lib")
     assert set(_lib.CAMERA_EXPORTS) == declared
@@ -68,13 +55,7 @@ def test_camera_entry_points_are_exported_bound_and_documented(libpath):
 
 def test_camera_arguments_are_checked_before_any_hip_call(libpath):
     """Fake 16-byte-aligned pointers: every case below returns before anything is dereferenced or enqueued."""
-    _lib = sub("_lib")
-    L = _lib.lib()
-    A = 0x10000
-    N, W, H = 8, 32, 32
-    scene = _lib.GsrScene(N, A, A, A, A, A, 3, 1.0, 1)
-    cam = _lib.GsrCamera()
-    cam.W, cam.H, cam.tan_fovx, cam.tan_fovy = W, H, 0.5, 0.5
+    _lib, L, A, N, W, H, scene, cam = fake_call_setup()
     ws_bytes = int(L.gsr_backward_workspace_bytes(N, 0, W, H))
     sc_bytes = int(L.gsr_backward_camera_scratch_bytes(N))
 

@@ -3,38 +3,25 @@ point, every argument is checked before anything is enqueued, the Python surface
 GPU, and the trainer takes --capacity / --capacity-initial."""
 import ctypes as C
 import os
-import re
 import subprocess
 import sys
 
 import pytest
 
-from conftest import ROOT, PKG_NAME, sub
+from abi_helpers import compile_c99_probe, declared_names, fake_call_setup, libpath  # noqa: F401  (libpath: a fixture)
+from conftest import ROOT, sub
 
 HDR = os.path.join(ROOT, "include", "gsr_capacity.h")
 
 
-@pytest.fixture(scope="module")
-def libpath():
-    path = os.path.join(ROOT, PKG_NAME, "libgsr_hip.so")
-    if not os.path.exists(path):   # hipcc cross-compiles gfx950 without a GPU
-        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, PKG_NAME, "csrc")])
-    return path
-
-
 def test_capacity_header_is_plain_c99(tmp_path):
-    probe = tmp_path / "probe.c"
-    probe.write_text('#include "gsr_capacity.h"\n'
-                     'int main(void) { int (*f)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
-                     '                          void *, size_t, void *, size_t, int64_t, void *) = gsr_forward_capacity; (void)f; return 0; }\n')
-    p = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(probe),
-                        "-o", str(tmp_path / "probe.o")], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
+    compile_c99_probe(tmp_path, '#include "gsr_capacity.h"\n'
+                                'int main(void) { int (*f)(const GsrScene *, const GsrCamera *, const GsrGeom *, const GsrBinning *, const GsrImage *,\n'
+                                '                          void *, size_t, void *, size_t, int64_t, void *) = gsr_forward_capacity; (void)f; return 0; }\n')
 
 
 def test_capacity_entry_point_is_exported_bound_and_documented(libpath):
-    code = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)        # declarations, not the comments that name gsr.h's sizes
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", code))
+    declared = declared_names(HDR)
     assert declared == {"gsr_forward_capacity"}
     lib = C.CDLL(libpath)
     assert hasattr(lib, "gsr_forward_capacity")
@@ -48,13 +35,7 @@ def test_capacity_entry_point_is_exported_bound_and_documented(libpath):
 
 def test_capacity_arguments_are_checked_before_any_hip_call(libpath):
     """Fake 16-byte-aligned pointers: every case below returns before anything is dereferenced or enqueued."""
-    _lib = sub("_lib")
-    L = _lib.lib()
-    A = 0x10000
-    N, W, H = 8, 32, 32
-    scene = _lib.GsrScene(N, A, A, A, A, A, 3, 1.0, 1)
-    cam = _lib.GsrCamera()
-    cam.W, cam.H, cam.tan_fovx, cam.tan_fovy = W, H, 0.5, 0.5
+    _lib, L, A, N, W, H, scene, cam = fake_call_setup()
     geom = _lib.GsrGeom(A, A, A, A, A, A, A, A, A, None, None)
     img = _lib.GsrImage(A, A, A, A)
     gbytes = int(L.gsr_geom_workspace_bytes(N))

@@ -4,42 +4,29 @@ the Python surface refuses bad arguments before the GPU, and the trainer takes -
 import ctypes as C
 import math
 import os
-import re
 import subprocess
 import sys
 
 import pytest
 
-from conftest import ROOT, PKG_NAME, sub
+from abi_helpers import compile_c99_probe, declared_names, libpath  # noqa: F401  (libpath: a fixture)
+from conftest import ROOT, sub
 
 HDR = os.path.join(ROOT, "include", "gsr_loss.h")
 
 
-@pytest.fixture(scope="module")
-def libpath():
-    path = os.path.join(ROOT, PKG_NAME, "libgsr_hip.so")
-    if not os.path.exists(path):   # hipcc cross-compiles gfx950 without a GPU
-        subprocess.check_call(["make", "-s", "-j8", "-C", os.path.join(ROOT, PKG_NAME, "csrc")])
-    return path
-
-
 def test_loss_header_is_plain_c99(tmp_path):
-    probe = tmp_path / "probe.c"
-    probe.write_text('#include "gsr_loss.h"\n'
-                     'int main(void) {\n'
-                     '    size_t (*b)(int32_t, int32_t) = gsr_dssim_workspace_bytes;\n'
-                     '    int (*f)(const float *, const float *, float *, float *, float *, int32_t, int32_t, float, int32_t, void *, size_t,\n'
-                     '             void *) = gsr_l1_dssim_loss_grad;\n'
-                     '    int w[2] = {GSR_SSIM_WINDOW_REFERENCE, GSR_SSIM_WINDOW_GAUSSIAN};\n'
-                     '    (void)b; (void)f; (void)w; return 0; }\n')
-    p = subprocess.run(["gcc", "-std=c99", "-pedantic", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(probe),
-                        "-o", str(tmp_path / "probe.o")], capture_output=True, text=True)
-    assert p.returncode == 0, p.stderr
+    compile_c99_probe(tmp_path, '#include "gsr_loss.h"\n'
+                                'int main(void) {\n'
+                                '    size_t (*b)(int32_t, int32_t) = gsr_dssim_workspace_bytes;\n'
+                                '    int (*f)(const float *, const float *, float *, float *, float *, int32_t, int32_t, float, int32_t, void *, size_t,\n'
+                                '             void *) = gsr_l1_dssim_loss_grad;\n'
+                                '    int w[2] = {GSR_SSIM_WINDOW_REFERENCE, GSR_SSIM_WINDOW_GAUSSIAN};\n'
+                                '    (void)b; (void)f; (void)w; return 0; }\n')
 
 
 def test_loss_entry_points_are_exported_bound_and_documented(libpath):
-    code = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", code))
+    declared = declared_names(HDR)
     assert declared == {"gsr_dssim_workspace_bytes", "gsr_l1_dssim_loss_grad"}
     lib = C.CDLL(libpath)
     for name in declared:

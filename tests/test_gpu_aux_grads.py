@@ -322,3 +322,96 @@ def test_alpha_supervision_lowers_the_alpha_error_on_lego(tmp_path):
     print(f"\nalpha L1 {s0['train_alpha_l1_mean']:.6f} -> {s1['train_alpha_l1_mean']:.6f} (gain {gain:.3f}); colour L1 "
           f"{s0['train_l1_mean']:.5f} -> {s1['train_l1_mean']:.5f}")
     assert gain >= ALPHA_GAIN_MIN
+
+
+# ---- 6. every backward export, driven directly: backward() itself calls only three of them ----
+def test_every_backward_export_agrees_with_backward():
+    """All eight backward entry points are one request behind the ABI.  On one frame with the forward's records, masks and a view
+    payload, each export is called through ctypes with equivalent arguments -- whole or split, the pixel gradient alone or with the
+    depth and alpha gradients, flags 0 or GSR_BWD_ABSGRAD -- and must give what backward() gives, under parity.assert_grad's
+    contract (float atomics: not bit for bit)."""
+    import ctypes as C
+    gsr = pkg()
+    _lib, _host = sub("_lib"), sub("_host")
+    L = _lib.lib()
+    W, H, N = 208, 160, 3000
+    sc = gsr.scenes.synthetic_scene(N, 0.05, 0.6, 7)
+    cam = gsr.cameras.nerf_camera(gsr.scenes.LEGO_FRAME0, W, H, gsr.scenes.LEGO_CAMERA_ANGLE_X)
+    kw = render_kwargs(sc, cam, width=W, height=H, bg=(0.1, 0.2, 0.3))
+    _, _, buf = gsr.render_gaussians(**kw)
+    dpix, gD, gA = _rng_grads(H, W, 6)
+    dev, f32 = buf["radii"].device, torch.float32
+    up = lambda a, shape: _host.to_dev(a, f32, dev, shape)
+    t = dict(means=up(sc["means"], (-1, 3)), scales=up(sc["scales"], (-1, 3)), rot=up(sc["rotations"], (-1, 4)),
+             op=up(sc["opacities"], (-1,)), sh=up(sc["shs"], (-1, 3)), dpix=up(dpix, (H, W, 3)), gD=up(gD, (H, W)), gA=up(gA, (H, W)))
+    records = buf["points_xy_image"]._gsr_records[0]
+    masks, _, order = buf["point_list"]._gsr_block_masks
+    D = int(buf["point_list"].shape[0])
+    assert D > 1000 and records.shape == (N, 16) and masks.numel() == D
+    p = _host.ptr
+    scene = _lib.GsrScene(N, p(t["means"]), p(t["scales"]), p(t["rot"]), p(t["op"]), p(t["sh"]), 3, 1.0, 1)
+    camera = _host.make_camera(kw["viewmatrix"], kw["projmatrix"], kw["campos"], kw["background"], kw["tan_fovx"], kw["tan_fovy"], W, H)
+    geom = _lib.GsrGeom(p(buf["radii"]), None, None, None, None, p(buf["cov3Ds"]), None, None, p(buf["clamped_state"]), p(records), None)
+    binning = _lib.GsrBinning(D, p(buf["point_list"]), p(buf["ranges"]), p(masks), p(order), None, 0)
+    img = _lib.GsrImage(None, None, p(buf["final_Ts"]), p(buf["n_contrib"]))
+    head = (C.byref(scene), C.byref(camera), C.byref(geom))
+    mid = (C.byref(binning), C.byref(img))
+    need, off = int(L.gsr_backward_workspace_bytes(N, D, W, H)), int(L.gsr_backward_accumulators_offset(N))
+    stream = _host.raw_stream(dev)
+    refs = {}
+
+    def reference(aux, absgrad):
+        if (aux, absgrad) not in refs:
+            extra = dict(dL_ddepth_image=gD, dL_dalpha_image=gA) if aux else {}
+            g = gsr.backward(**_bkw(sc, cam, kw, buf, dpix), sh_gradient="both", absgrad=absgrad, **extra)
+            assert sub("backward").backward.last_call_used_forward_records and sub("backward").backward.last_call_used_forward_masks
+            refs[aux, absgrad] = {k: parity.to_np(v).copy() for k, v in g.items() if isinstance(v, torch.Tensor)}
+        return refs[aux, absgrad]
+
+    def run(api, split, aux, absgrad):
+        """api: 'plain' (gsr.h), 'aux' (gsr_aux_grads.h) or 'flags' (gsr_densify_stats.h)."""
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        out = dict(dL_dmean3D=torch.empty((N, 3), dtype=f32, device=dev), dL_dscale=torch.empty((N, 3), dtype=f32, device=dev),
+                   dL_drot=torch.empty((N, 4), dtype=f32, device=dev), dL_dopacity=torch.empty((N,), dtype=f32, device=dev),
+                   dL_dshs=torch.empty((16 * N, 3), dtype=f32, device=dev))
+        payload = torch.empty(3 * N + 4, dtype=f32, device=dev)
+        inv = torch.empty((N,), dtype=f32, device=dev) if aux else None
+        grads = _lib.GsrGrads(p(out["dL_dmean3D"]), p(out["dL_dscale"]), p(out["dL_drot"]), p(out["dL_dopacity"]), p(out["dL_dshs"]),
+                              None, None, None, None if split else p(payload))
+        pg = _lib.GsrPixelGrads(p(t["dpix"]), p(t["gD"]) if aux else None, p(t["gA"]) if aux else None)
+        tail = (p(ws), need) + ((_lib.BWD_ABSGRAD if absgrad else 0,) if api == "flags" else ()) + (stream,)
+        pix = p(t["dpix"]) if api == "plain" else C.byref(pg)
+        with _host.on_device(dev):
+            if split:
+                blend = {"plain": L.gsr_backward_blend, "aux": L.gsr_backward_blend_aux, "flags": L.gsr_backward_blend_flags}[api]
+                _lib.check(blend(*head, *mid, pix, p(payload), *tail))
+                if aux:
+                    _lib.check(L.gsr_backward_geom_aux(*head, C.byref(grads), p(inv), p(ws), need, stream))
+                else:
+                    _lib.check(L.gsr_backward_geom(*head, C.byref(grads), p(ws), need, stream))
+            elif api == "plain":
+                _lib.check(L.gsr_backward(*head, *mid, pix, C.byref(grads), *tail))
+            else:
+                whole = L.gsr_backward_aux if api == "aux" else L.gsr_backward_flags
+                _lib.check(whole(*head, *mid, pix, C.byref(grads), p(inv), *tail))
+        acc = ws[off:off + 64 * N].view(f32).view(N, 16)
+        out.update(dL_dcolor=acc[:, 0:3], dL_dmean2D=acc[:, 3:6], dL_dconic=acc[:, 6:10], payload_rows=payload[:3 * N], payload_campos=payload[3 * N:])
+        if aux:
+            out.update(dL_dinv_depths=inv, dL_dinv_depths_column=acc[:, 11])
+        if absgrad:
+            out["dL_dmean2D_abs"] = acc[:, 12:14]
+        return {k: parity.to_np(v).copy() for k, v in out.items()}
+
+    variants = [(api, split, aux, absgrad) for api in ("plain", "aux", "flags") for split in (False, True)
+                for aux in ((False,) if api == "plain" else (False, True)) for absgrad in ((False, True) if api == "flags" else (False,))]
+    assert len(variants) == 14
+    for api, split, aux, absgrad in variants:
+        got, ref = run(api, split, aux, absgrad), reference(aux, absgrad)
+        ref = dict(ref, payload_rows=ref["_view_payload"][:3 * N], payload_campos=ref["_view_payload"][3 * N:])
+        if aux:
+            ref["dL_dinv_depths_column"] = ref["dL_dinv_depths"]
+        assert set(got) <= set(ref), set(got) - set(ref)
+        for k in got:
+            assert np.abs(ref[k]).max() > 0, k
+            frac, worst = parity.assert_grad(f"{api} {'split' if split else 'whole'} aux={aux} absgrad={absgrad} {k}", got[k], ref[k])[:2]
+            print(f"  {api:5s} {'split' if split else 'whole'} aux={aux!s:5s} absgrad={absgrad!s:5s} {k:22s} {frac:.6f} within the tight band, max err {worst:.2e} max|g|")
