@@ -155,6 +155,29 @@ DENSIFY_STATS_EXPORTS = {
 }
 BWD_ABSGRAD = 1             # GSR_BWD_ABSGRAD
 
+# include/gsr_antialias.h: the antialiased mode (opacity compensation of the screen-space blur), selected by one more argument,
+# `aa_scale` (its own header, so its own table)
+ANTIALIAS_EXPORTS = {
+    "gsr_forward_count_aa": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), vp, C.c_size_t,
+                                       C.POINTER(C.c_int64), vp, vp]),
+    "gsr_forward_capacity_aa": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                          C.POINTER(GsrImage), vp, C.c_size_t, vp, C.c_size_t, C.c_int64, vp, vp]),
+    "gsr_backward_aa": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrBinning),
+                                  C.POINTER(GsrImage), C.POINTER(GsrPixelGrads), C.POINTER(GsrGrads), vp, vp, C.c_size_t, C.c_uint32, vp, vp]),
+    "gsr_backward_geom_aa": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), C.POINTER(GsrGrads), vp, vp,
+                                       C.c_size_t, vp, vp]),
+    "gsr_backward_camera_aa": (C.c_int, [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrGeom), vp, vp, C.c_size_t, vp, C.c_size_t,
+                                         vp, vp]),
+}
+RASTERIZE_MODES = ("classic", "antialiased")
+
+
+def check_rasterize_mode(mode):
+    """The `rasterize_mode` keyword of render_gaussians() and backward(): refused before the library is touched."""
+    if mode not in RASTERIZE_MODES:
+        raise ValueError(f"rasterize_mode must be 'classic' or 'antialiased' (got {mode!r})")
+    return mode == "antialiased"
+
 STAGES = ["preprocess", "scan", "depth_sort", "host_gap", "depth_scan", "expand", "tile_sort", "ranges", "blend_fwd",
           "bwd_prep", "blend_bwd", "geom_bwd"]
 
@@ -171,7 +194,7 @@ def lib():
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items())
                                   + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
-                                  + list(DENSIFY_STATS_EXPORTS.items())):
+                                  + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -31,6 +31,13 @@ dL_dmean2D[:, 0:2] (AbsGS).  The flag rides on the one entry point every call ru
 float-atomic order.  Without the keyword the two columns are zero and the key is absent.  Either way the returned `dL_dmean2D`
 carries a private tag (`_gsr_backward_ws`: workspace, its version counter, whether the absolute columns were filled) through
 which densify.DensifyStats.update finds the accumulators.
+
+`rasterize_mode="antialiased"` (include/gsr_antialias.h) is the backward of a frame rendered with that mode: `conic_opacity` must
+be that frame's own view, unwritten, and `opacity` the opacity it was rendered from, unwritten (render_gaussians leaves rho on the
+view as a private tag).  dL_dopacity is then rho times the blend stage's gradient, and the derivative of rho joins dL_dmean3D,
+dL_dscale, dL_drot and, with camera_grad, the camera gradient.  Without a valid tag the call raises: there is nothing to fall back
+to, and classic gradients for an antialiased frame would be silently wrong; an antialiased frame handed to the default
+`rasterize_mode="classic"` raises for the same reason.  It composes with every keyword above and with capacity frames.
 """
 import ctypes as C
 import os
@@ -56,6 +63,26 @@ def _zeros_cov3d(n, dev):
     return z
 
 
+def _aa_scale_of(conic_opacity, opacity, antialiased):
+    """The antialiased forward's tag on its conic_opacity view (forward.py), or an error: an antialiased frame and a classic one
+    are never taken for each other.  Returns the tag (rho, ..., the forward's device copy of a host opacity or None) or None."""
+    tag = getattr(conic_opacity, "_gsr_aa_scale", None)
+    if not antialiased:
+        if tag is not None:
+            raise ValueError("this frame was rendered with rasterize_mode='antialiased': pass the same mode to backward()")
+        return None
+    if tag is None:
+        raise ValueError("backward(rasterize_mode='antialiased') needs the conic_opacity view of a frame rendered with "
+                         "render_gaussians(rasterize_mode='antialiased'), not a copy of it and not a classic frame")
+    _, op_ref, op_ver, rec_ver, _ = tag
+    if conic_opacity._version != rec_ver:
+        raise ValueError("backward(rasterize_mode='antialiased'): the forward's records were written in place after the render")
+    if op_ref is not None and (op_ref() is not opacity or _host.version_of(opacity) != op_ver):
+        raise ValueError("backward(rasterize_mode='antialiased'): `opacity` is not the tensor this frame was rendered from, or was "
+                         "written in place since")
+    return tag
+
+
 def _get(buf, key):
     if buf is None:
         raise NameError(f"backward() needs the forward buffer holding '{key}' (the reference fails the same way, "
@@ -67,7 +94,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256, campos=None,
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
-             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False):
+             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic"):
+    antialiased = _lib.check_rasterize_mode(rasterize_mode)
+    # (before anything touches the GPU: a frame of the other mode, a copy of the view, a write since the render)
+    aa_scale = _aa_scale_of(conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity"),
+                            opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
     aux = dL_ddepth_image is not None or dL_dalpha_image is not None
@@ -87,7 +118,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
     rot = _host.to_dev(rotations, f32, dev, (-1, 4))
-    op = _host.to_dev(opacity, f32, dev, (-1,)) if opacity is not None else means.new_zeros((N,))  # unused (quirk Q7)
+    op = _host.to_dev(opacity, f32, dev, (-1,)) if opacity is not None else means.new_zeros((N,))  # unused in the classic mode (quirk Q7)
     ranges = _get(img_buffer, "ranges")                       # reference backward.py:1084-1090
     final_Ts = _get(img_buffer, "final_Ts")
     n_contrib = _get(img_buffer, "n_contrib")
@@ -164,6 +195,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     D = point_list.shape[0]
     D_bin = D if cap_tag is None else cap_tag[1]
 
+    if antialiased:
+        aa_op = aa_scale[4]
+        if aa_scale[0].device != dev or aa_scale[0].shape[0] != N or op.shape[0] != N or (aa_op is not None and not torch.equal(aa_op, op)):
+            raise ValueError("backward(rasterize_mode='antialiased'): `opacity` is not the opacity this frame was rendered from")
+        aa_scale = aa_scale[0]
     scene = _lib.GsrScene(N, _host.ptr(means), _host.ptr(sc), _host.ptr(rot), _host.ptr(op), _host.ptr(sh), int(degree),
                           float(scale_modifier), 1)
     depths = None
@@ -233,18 +269,27 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
                                                   ws.numel(), flags, stream))
             on_payload(payload)
             grads.dL_drgb = None
-            if aux:
+            if antialiased:     # (the AUX per-Gaussian kernel: without an auxiliary gradient its one extra term is zero)
+                _lib.check(L.gsr_backward_geom_aa(*head, C.byref(grads), None, _host.ptr(ws), ws.numel(), _host.ptr(aa_scale), stream))
+            elif aux:
                 _lib.check(L.gsr_backward_geom_aux(*head, C.byref(grads), None, _host.ptr(ws), ws.numel(), stream))
             else:
                 _lib.check(L.gsr_backward_geom(*head, C.byref(grads), _host.ptr(ws), ws.numel(), stream))
+        elif antialiased:
+            _lib.check(L.gsr_backward_aa(*head, C.byref(binning), C.byref(img), C.byref(pg), C.byref(grads), None, _host.ptr(ws), ws.numel(),
+                                         flags, _host.ptr(aa_scale), stream))
         else:
             _lib.check(L.gsr_backward_flags(*head, C.byref(binning), C.byref(img), C.byref(pg), C.byref(grads), None, _host.ptr(ws), ws.numel(),
                                             flags, stream))
         if camera_grad:     # after the backward, on the same stream and workspace: reads its accumulators, writes only its own output
             dcam = torch.empty(_lib.CAMERA_GRAD_FLOATS, dtype=f32, device=dev)
             scratch = torch.empty(int(L.gsr_backward_camera_scratch_bytes(N)), dtype=torch.uint8, device=dev)
-            _lib.check(L.gsr_backward_camera(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(dcam), _host.ptr(ws), ws.numel(),
-                                             _host.ptr(scratch), scratch.numel(), stream))
+            if antialiased:
+                _lib.check(L.gsr_backward_camera_aa(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(dcam), _host.ptr(ws), ws.numel(),
+                                                    _host.ptr(scratch), scratch.numel(), _host.ptr(aa_scale), stream))
+            else:
+                _lib.check(L.gsr_backward_camera(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(dcam), _host.ptr(ws), ws.numel(),
+                                                 _host.ptr(scratch), scratch.numel(), stream))
     out = {
         "dL_dmean3D": dL_dmean3D, "dL_dcolor": dL_dcolor, "dL_dshs": dL_dsh, "dL_dopacity": dL_dopacity,
         "dL_dscale": dL_dscale, "dL_drot": dL_drot, "dL_dmean2D": dL_dmean2D, "dL_dconic": dL_dconic,

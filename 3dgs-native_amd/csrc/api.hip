@@ -9,6 +9,7 @@
 #include <mutex>
 #include <vector>
 
+#include "gsr_antialias.h"
 #include "gsr_aux_grads.h"
 #include "gsr_camera_grads.h"
 #include "gsr_capacity.h"
@@ -297,10 +298,10 @@ void read_tuning()
 // depth extremes, straight into the pinned words, and rb->ev marks the scan's end: work that does not need D goes out before the
 // host waits for it.  Without one D stays in point_offsets[N-1].
 int enqueue_depth_stage(const GsrScene *scene, const CamK &cam, const GsrGeom *geom, const GeomWs &ws, Readback *rb, int depth_passes, hipStream_t s,
-                        int st)
+                        int st, float *aa_scale)
 {
     mark(st, 0, s);
-    HIP_TRY(gsr_launch_preprocess(*scene, cam, *geom, ws, s, fwd_order_wanted(cam.grid_x * cam.grid_y)));
+    HIP_TRY(gsr_launch_preprocess(*scene, cam, *geom, ws, s, fwd_order_wanted(cam.grid_x * cam.grid_y), aa_scale));
     mark(st, 1, s);
     HIP_TRY(gsr_launch_id_scan(geom->tiles_touched, geom->point_offsets, ws, scene->N, rb ? rb->pinned : nullptr, s));
     mark(st, 2, s);
@@ -335,6 +336,12 @@ GeomWs gsr_carve_geom(void *base, int64_t N)
     w.bytes = c.off + 256;
     return w;
 }
+
+// gsr_forward_count and (include/gsr_antialias.h) gsr_forward_count_aa: aa_scale = NULL is the classic call
+static int forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, void *geom_ws, size_t geom_ws_bytes,
+                         int64_t *num_rendered, float *aa_scale, void *stream);
+static int forward_capacity(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                            void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, int64_t shape_hint, float *aa_scale, void *stream);
 
 extern "C" {
 
@@ -379,6 +386,20 @@ size_t gsr_block_order_ints(int32_t W, int32_t H)
 int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, void *geom_ws, size_t geom_ws_bytes,
                       int64_t *num_rendered, void *stream)
 {
+    return forward_count(scene, camera, geom, geom_ws, geom_ws_bytes, num_rendered, nullptr, stream);
+}
+
+int gsr_forward_count_aa(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, void *geom_ws, size_t geom_ws_bytes,
+                         int64_t *num_rendered, float *aa_scale, void *stream)
+{
+    return forward_count(scene, camera, geom, geom_ws, geom_ws_bytes, num_rendered, aa_scale, stream);
+}
+
+} // extern "C"
+
+static int forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, void *geom_ws, size_t geom_ws_bytes,
+                         int64_t *num_rendered, float *aa_scale, void *stream)
+{
     read_tuning();
     if (int rc = check_scene_cam(scene, camera)) return rc;
     if (!num_rendered) return GSR_E_NULL;
@@ -386,7 +407,7 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     const int64_t N = scene->N;
     if (N == 0) return GSR_OK; // reference behaviour undefined (quirk Q10): empty buffers, D = 0
     if (!geom_ok(geom)) return GSR_E_NULL;
-    if (!geom_aligned(geom) || !gsr_aligned16(geom_ws)) return GSR_E_ALIGN;
+    if (!geom_aligned(geom) || !gsr_aligned16(geom_ws) || !gsr_aligned16(aa_scale)) return GSR_E_ALIGN;
     if (!geom_ws || geom_ws_bytes < gsr_geom_workspace_bytes(N)) return GSR_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const CamK cam = make_cam(camera);
@@ -399,7 +420,7 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     // the previous frame in this workspace needed (its guess; four the first time).  If the guess turns out too low the launched
     // passes leave the data alone and all four are launched once the readback has said so.
     const int guess = (gsr_debug_flags & 256) ? 4 : depth_pass_guess(geom_ws);
-    if (int rc = enqueue_depth_stage(scene, cam, geom, ws, rb, guess, s, st)) return rc;
+    if (int rc = enqueue_depth_stage(scene, cam, geom, ws, rb, guess, s, st, aa_scale)) return rc;
     HIP_TRY(hipEventSynchronize(rb->ev)); // D (and the pass count) are on the host; the GPU keeps sorting
     const int32_t last = *rb->pinned;
     const int needed = gsr_depth_passes_needed(rb->pinned, N);
@@ -412,8 +433,6 @@ int gsr_forward_count(const GsrScene *scene, const GsrCamera *camera, const GsrG
     note_count(geom_ws, N, (int64_t)last, needed);
     return GSR_OK;
 }
-
-} // extern "C"
 
 namespace {
 
@@ -504,6 +523,21 @@ int gsr_forward_render(const GsrScene *scene, const GsrCamera *camera, const Gsr
 int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
                          void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, int64_t shape_hint, void *stream)
 {
+    return forward_capacity(scene, camera, geom, binning, image, geom_ws, geom_ws_bytes, bin_ws, bin_ws_bytes, shape_hint, nullptr, stream);
+}
+
+int gsr_forward_capacity_aa(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                            void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, int64_t shape_hint, float *aa_scale,
+                            void *stream)
+{
+    return forward_capacity(scene, camera, geom, binning, image, geom_ws, geom_ws_bytes, bin_ws, bin_ws_bytes, shape_hint, aa_scale, stream);
+}
+
+} // extern "C"
+
+static int forward_capacity(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                            void *geom_ws, size_t geom_ws_bytes, void *bin_ws, size_t bin_ws_bytes, int64_t shape_hint, float *aa_scale, void *stream)
+{
     read_tuning();
     // every argument is checked before anything is enqueued (include/gsr_capacity.h)
     if (int rc = check_frame(scene, camera, binning, image)) return rc;
@@ -511,7 +545,7 @@ int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const G
     if (shape_hint < 0 || shape_hint > GSR_MAX_RENDERED) return GSR_E_OVERFLOW;
     if (K > 0 && !binning->point_list) return GSR_E_NULL;
     if (N > 0 && !geom_ok(geom)) return GSR_E_NULL;
-    if (!frame_aligned(geom, geom_ws, bin_ws, binning, image) || !gsr_aligned16(binning->block_masks)) return GSR_E_ALIGN;
+    if (!frame_aligned(geom, geom_ws, bin_ws, binning, image) || !gsr_aligned16(binning->block_masks) || !gsr_aligned16(aa_scale)) return GSR_E_ALIGN;
     if (int rc = check_workspaces(N, K, geom_ws, geom_ws_bytes, bin_ws, bin_ws_bytes, camera)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const CamK cam = make_cam(camera);
@@ -521,12 +555,10 @@ int gsr_forward_capacity(const GsrScene *scene, const GsrCamera *camera, const G
     // All four depth passes: with no readback there is no guess to check, and the device plan (DepthCtl) makes the passes this
     // frame does not need return at once -- one or two launches of early-exit workgroups, a few microseconds of GPU time.
     // D stays in point_offsets[N-1], where every D-dependent kernel below reads it.
-    if (int rc = enqueue_depth_stage(scene, cam, geom, gw, nullptr, 4, s, st)) return rc;
+    if (int rc = enqueue_depth_stage(scene, cam, geom, gw, nullptr, 4, s, st, aa_scale)) return rc;
     mark(st, 3, s);
     return enqueue_render(scene, cam, geom, binning, image, gw, carve_bin(bin_ws, K), geom->point_offsets + (N - 1), shape_hint, s, st);
 }
-
-} // extern "C"
 
 namespace {
 
@@ -551,6 +583,7 @@ struct BwdCall {
     int halves;     // BWD_BLEND | BWD_GEOM
     bool geom_aux;  // the AUX per-Gaussian kernel whatever the pixel gradients are (gsr_backward_geom_aux)
     void *stream;
+    const float *aa_scale = nullptr; // the AA per-Gaussian kernel (include/gsr_antialias.h): the forward's rho; NULL = classic
 };
 GsrPixelGrads pix_of(const GsrPixelGrads *pg) { return pg ? *pg : GsrPixelGrads{}; }
 
@@ -584,7 +617,7 @@ int check_bwd(const BwdCall &c)
         if (c.pix.dL_dinv_depth && !g->blend_records && !g->depths) return GSR_E_NULL; // a re-pack without depths would carry invd = 0
     }
     if (!geom_aligned(g) || !gsr_aligned16(c.ws)) return GSR_E_ALIGN;
-    if (per_gaussian && (!grads_aligned(gr) || !gsr_aligned16(c.dL_dinv_depths))) return GSR_E_ALIGN;
+    if (per_gaussian && (!grads_aligned(gr) || !gsr_aligned16(c.dL_dinv_depths) || !gsr_aligned16(c.aa_scale))) return GSR_E_ALIGN;
     if (blend) {
         if (!gsr_aligned16(b->point_list) || !gsr_aligned16(b->ranges) || !gsr_aligned16(b->block_masks) || !gsr_aligned16(b->block_order) ||
             !gsr_aligned16(img->final_T) || !gsr_aligned16(img->n_contrib) || !gsr_aligned16(c.pix.dL_dpixels) || !gsr_aligned16(c.payload) ||
@@ -620,7 +653,7 @@ int enqueue_bwd_blend(const BwdCall &c, const CamK &cam, const BwdWs &bw, hipStr
 int enqueue_bwd_geom(const BwdCall &c, const CamK &cam, const BwdWs &bw, hipStream_t s, int st)
 {
     const bool aux = c.geom_aux || c.pix.dL_dinv_depth || c.pix.dL_dalpha || c.dL_dinv_depths;
-    HIP_TRY(gsr_launch_geom_backward(*c.scene, cam, *c.geom, bw.acc, *c.grads, s, aux));
+    HIP_TRY(gsr_launch_geom_backward(*c.scene, cam, *c.geom, bw.acc, *c.grads, s, aux, c.aa_scale));
     if (c.dL_dinv_depths) // column 11 of the accumulator records (gsr_gradrec_slot(9)), packed
         HIP_TRY(hipMemcpy2DAsync(c.dL_dinv_depths, sizeof(float), &bw.acc[0].f[gsr_gradrec_slot(9)], sizeof(GradRec), sizeof(float),
                                  (size_t)c.scene->N, hipMemcpyDeviceToDevice, s));
@@ -682,6 +715,21 @@ int gsr_backward_geom_aux(const GsrScene *scene, const GsrCamera *camera, const 
     return run_bwd({scene, camera, geom, nullptr, nullptr, {}, nullptr, grads, dL_dinv_depths, ws, ws_bytes, 0, BWD_GEOM, true, stream});
 }
 
+// (include/gsr_antialias.h) the whole call and the geom half of an antialiased frame; aa_scale = NULL is the call above
+int gsr_backward_aa(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
+                    const GsrPixelGrads *pixel_grads, const GsrGrads *grads, float *dL_dinv_depths, void *ws, size_t ws_bytes, uint32_t flags,
+                    const float *aa_scale, void *stream)
+{
+    return run_bwd({scene, camera, geom, binning, image, pix_of(pixel_grads), nullptr, grads, dL_dinv_depths, ws, ws_bytes, flags,
+                    BWD_BLEND | BWD_GEOM, false, stream, aa_scale});
+}
+
+int gsr_backward_geom_aa(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrGrads *grads, float *dL_dinv_depths,
+                         void *ws, size_t ws_bytes, const float *aa_scale, void *stream)
+{
+    return run_bwd({scene, camera, geom, nullptr, nullptr, {}, nullptr, grads, dL_dinv_depths, ws, ws_bytes, 0, BWD_GEOM, true, stream, aa_scale});
+}
+
 // (include/gsr.h) the same three with the colour image's gradient alone
 int gsr_backward(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, const GsrBinning *binning, const GsrImage *image,
                  const float *dL_dpixels, const GsrGrads *grads, void *ws, size_t ws_bytes, void *stream)
@@ -709,10 +757,17 @@ size_t gsr_backward_camera_scratch_bytes(int64_t N) { return gsr_camera_scratch_
 int gsr_backward_camera(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, float *dL_dcamera, const void *ws, size_t ws_bytes,
                         void *scratch, size_t scratch_bytes, void *stream)
 {
+    return gsr_backward_camera_aa(scene, camera, geom, dL_dcamera, ws, ws_bytes, scratch, scratch_bytes, nullptr, stream);
+}
+
+// (include/gsr_antialias.h) aa_scale = NULL is the call above
+int gsr_backward_camera_aa(const GsrScene *scene, const GsrCamera *camera, const GsrGeom *geom, float *dL_dcamera, const void *ws, size_t ws_bytes,
+                           void *scratch, size_t scratch_bytes, const float *aa_scale, void *stream)
+{
     read_tuning();
     if (int rc = check_scene_cam(scene, camera)) return rc;
     if (!dL_dcamera) return GSR_E_NULL;
-    if (!gsr_aligned16(dL_dcamera) || !gsr_aligned16(ws) || !gsr_aligned16(scratch)) return GSR_E_ALIGN;
+    if (!gsr_aligned16(dL_dcamera) || !gsr_aligned16(ws) || !gsr_aligned16(scratch) || !gsr_aligned16(aa_scale)) return GSR_E_ALIGN;
     const int64_t N = scene->N;
     if (N > 0) { // (the backward's own checks of geom and ws; cov3D and sh_dir_grad are optional)
         if (!geom_core(geom)) return GSR_E_NULL;
@@ -722,7 +777,7 @@ int gsr_backward_camera(const GsrScene *scene, const GsrCamera *camera, const Gs
     }
     const CamK cam = make_cam(camera);
     const GradRec *acc = N > 0 ? carve_bwd(const_cast<void *>(ws), N).acc : nullptr;
-    HIP_TRY(gsr_launch_camera_backward(*scene, cam, N > 0 ? *geom : GsrGeom{}, acc, dL_dcamera, scratch, (hipStream_t)stream));
+    HIP_TRY(gsr_launch_camera_backward(*scene, cam, N > 0 ? *geom : GsrGeom{}, acc, dL_dcamera, scratch, (hipStream_t)stream, aa_scale));
     return GSR_OK;
 }
 

@@ -40,10 +40,13 @@ __device__ __forceinline__ float dot3(const float a[3], const float b[3])
 }
 
 // One Gaussian's term, added into acc[27] (slot order of kOut).
+// AA (include/gsr_antialias.h): the forward drew with opacity * rho, so column 10 (dL/d(opacity * rho)) times opacity times
+// d(rho)/d(a, b, c) joins the cotangent of the blurred covariance; rho is the forward's own (aa_scale), these are its (a, b, c).
+template <bool AA, class... AaIn>
 __device__ __forceinline__ void camera_term(int64_t i, const float *__restrict__ means, const float *__restrict__ scales,
                                             const float *__restrict__ rots, const float *__restrict__ shs, int degree, float scale_mod,
                                             const CamK &cam, const float *__restrict__ cov3Ds, const float *__restrict__ clamped_state,
-                                            const GradRec *__restrict__ accs, const float *__restrict__ sh_dir_grad, float acc[kSlots])
+                                            const GradRec *__restrict__ accs, const float *__restrict__ sh_dir_grad, float acc[kSlots], AaIn... aa_in)
 {
     const float4 *ap = reinterpret_cast<const float4 *>(accs + i);
     const float4 a0 = ap[0], a1 = ap[1], a2 = ap[2];
@@ -117,9 +120,19 @@ __device__ __forceinline__ void camera_term(int64_t i, const float *__restrict__
         const float det = a * c - b * b;
         const float gA = a1.z, gB = 2.0f * a1.w, gC = a2.y; // column 7 holds half of dL/dB (conic_b_half)
         const float id2 = 1.0f / (det * det);
-        const float dLa = (-c * c * gA + b * c * gB - b * b * gC) * id2;
-        const float dLb = (2.0f * b * c * gA - (det + 2.0f * b * b) * gB + 2.0f * a * b * gC) * id2;
-        const float dLc = (-b * b * gA + a * b * gB - a * a * gC) * id2;
+        float dLa = (-c * c * gA + b * c * gB - b * b * gC) * id2;
+        float dLb = (2.0f * b * c * gA - (det + 2.0f * b * b) * gB + 2.0f * a * b * gC) * id2;
+        float dLc = (-b * b * gA + a * b * gB - a * a * gC) * id2;
+        if constexpr (AA) {
+            const float a0 = dot3(TS[0], T[0]), c0 = dot3(TS[1], T[1]), bb = b * b;
+            if ((a0 * c0 - bb) / det > 0.000025f) { // on the floor rho is constant
+                const float *const aa_arr[] = {aa_in...}; // opacity, aa_scale
+                const float kh = aa_arr[0][i] * a2.z * 0.3f * id2 / (2.0f * aa_arr[1][i]);
+                dLa += kh * (c * c0 + bb);
+                dLc += kh * (a * a0 + bb);
+                dLb -= kh * 2.0f * b * (a + c0);
+            }
+        }
         // dL/dT = 2 G T Sigma3D, G = [[dLa, dLb/2], [dLb/2, dLc]]
         float dT[2][3];
 #pragma unroll
@@ -183,20 +196,24 @@ __device__ __forceinline__ void camera_term(int64_t i, const float *__restrict__
     }
 }
 
+// (the two arrays of the AA kernel -- opacity, aa_scale -- are its parameters alone, so the classic kernel's argument block is unchanged)
+template <bool AA = false, class... AaIn>
 __global__ __launch_bounds__(256) void camera_partials_kernel(int64_t N, const float *__restrict__ means, const float *__restrict__ scales,
                                                               const float *__restrict__ rots, const float *__restrict__ shs, int degree,
                                                               float scale_mod, CamK cam, const int32_t *__restrict__ radii,
                                                               const float *__restrict__ cov3Ds, const float *__restrict__ clamped_state,
                                                               const GradRec *__restrict__ accs, const float *__restrict__ sh_dir_grad,
-                                                              double *__restrict__ partials)
+                                                              double *__restrict__ partials, AaIn... aa_in)
 {
+    static_assert(sizeof...(AaIn) == (AA ? 2 : 0), "opacity and aa_scale, in the AA kernel only");
     __shared__ double s_wave[4][kSlots];
     float acc[kSlots];
 #pragma unroll
     for (int k = 0; k < kSlots; ++k) acc[k] = 0.0f;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride)
-        if (radii[i] > 0) camera_term(i, means, scales, rots, shs, degree, scale_mod, cam, cov3Ds, clamped_state, accs, sh_dir_grad, acc);
+        if (radii[i] > 0)
+            camera_term<AA>(i, means, scales, rots, shs, degree, scale_mod, cam, cov3Ds, clamped_state, accs, sh_dir_grad, acc, aa_in...);
     // the wave's sums (butterfly: every lane ends with the same bits), then the four waves in float64, in wave order
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 #pragma unroll
@@ -260,13 +277,17 @@ int gsr_camera_blocks(int64_t N) { return N <= 0 ? 0 : (int)std::min<int64_t>(gs
 size_t gsr_camera_scratch_bytes(int64_t N) { return (size_t)gsr_camera_blocks(N) * kRow * sizeof(double); }
 
 hipError_t gsr_launch_camera_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *dL_dcamera, void *scratch,
-                                      hipStream_t s)
+                                      hipStream_t s, const float *aa_scale)
 {
     const int nblk = gsr_camera_blocks(sc.N);
     if (nblk == 0) return hipMemsetAsync(dL_dcamera, 0, 36 * sizeof(float), s);
     double *partials = (double *)scratch;
-    hipLaunchKernelGGL(camera_partials_kernel, dim3((unsigned)nblk), dim3(256), 0, s, sc.N, sc.means, sc.scales, sc.rotations, sc.sh,
-                       sc.sh_degree, sc.scale_modifier, cam, g.radii, g.cov3D, g.clamped_state, acc, g.sh_dir_grad, partials);
+#define CAMERA_ARGS                                                                                                           \
+    dim3((unsigned)nblk), dim3(256), 0, s, sc.N, sc.means, sc.scales, sc.rotations, sc.sh, sc.sh_degree, sc.scale_modifier, cam,      \
+        g.radii, g.cov3D, g.clamped_state, acc, g.sh_dir_grad, partials
+    if (aa_scale) hipLaunchKernelGGL((camera_partials_kernel<true, const float *, const float *>), CAMERA_ARGS, sc.opacity, aa_scale);
+    else hipLaunchKernelGGL(camera_partials_kernel<false>, CAMERA_ARGS);
+#undef CAMERA_ARGS
     hipLaunchKernelGGL(camera_finish_kernel, dim3(1), dim3(256), 0, s, nblk, partials, dL_dcamera);
     return hipGetLastError();
 }

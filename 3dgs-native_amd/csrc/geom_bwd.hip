@@ -63,15 +63,22 @@ __device__ __forceinline__ float dot3(const float a[3], const float b[3])
 // preprocess stores in `depths`, t[2] below).  Its true derivative, -dL/dinvd / z^2 * dz/dmean with dz/dmean_k = view[4k + 2], is
 // added to dL_dmean3D beside the reference's dt transform (so without quirk Q3's view[j][3] term).  The AUX = false kernels are
 // the product's machine code unchanged (tools/kernel_disasm_diff.py).
-template <bool DIRGRAD, bool AUX = false>
+// AA (include/gsr_antialias.h): the forward drew the Gaussian with opacity * rho, rho = sqrt(max(0.000025, det0 / det1)) of the
+// projected covariance before (det0) and after (det1) the 0.3 blur, and left rho in aa_scale.  Column 10 of the record is then
+// g = dL/d(opacity * rho): dL_dopacity = aa_scale * g, and opacity * g times d(rho)/d(a, b, c), at this kernel's own (a, b, c) as the
+// conic's derivative is (Q1), joins dL_da / dL_db / dL_dc before they are chained on.  The plain 1 / det1^2: the 1e-7 belongs to
+// the conic inversion.  The AA = false kernels are likewise the product's machine code unchanged: the two arrays (opacity, aa_scale)
+// are parameters of the AA = true kernels alone (AaIn = two const float *), so the classic argument block keeps its kernarg offsets.
+template <bool DIRGRAD, bool AUX = false, bool AA = false, class... AaIn>
 __global__ __launch_bounds__(256) void geom_backward_kernel(
     int64_t N, const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ rots,
     const float *__restrict__ shs, int degree, CamK cam, float h_x, float h_y, const int32_t *__restrict__ radii,
     const float *__restrict__ cov3Ds, const float *__restrict__ clamped_state, const GradRec *__restrict__ acc,
     float *__restrict__ dL_dmean3D, float *__restrict__ dL_dscale, float *__restrict__ dL_drot, float *__restrict__ dL_dopacity,
     float *__restrict__ dL_dshs, float *__restrict__ dL_dcolor, float *__restrict__ dL_dmean2D, float *__restrict__ dL_dconic,
-    float *__restrict__ dL_drgb, const float *__restrict__ sh_dir_grad, float scale_mod)
+    float *__restrict__ dL_drgb, const float *__restrict__ sh_dir_grad, float scale_mod, AaIn... aa_in)
 {
+    static_assert(sizeof...(AaIn) == (AA ? 2 : 0), "opacity and aa_scale, in the AA kernels only");
     // SH rows (input coefficients, then in place the output gradients) live in LDS; moved cooperatively
     __shared__ float4 s_rows[4 * SH_WAVE_F4];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -126,9 +133,19 @@ __global__ __launch_bounds__(256) void geom_backward_kernel(
     // API-layout copies of the blend-stage gradients, for a caller that wants packed arrays (NULL: it reads the record's columns)
     // (dL_dcolor and dL_dmean2D: 12-byte rows, written wave-cooperatively at the end of the kernel)
     if (dL_dconic) *reinterpret_cast<float4 *>(dL_dconic + 4 * idx) = make_float4(g_con[0], g_con[1], 0.0f, g_con[2]);
-    gsr_st1<GSR_NT_MISC_STORE != 0>(dL_dopacity + idx, a8);
+    if constexpr (!AA) gsr_st1<GSR_NT_MISC_STORE != 0>(dL_dopacity + idx, a8);
 
     vis = my_radius > 0;
+    float g_rho = 0.0f; // AA: opacity * g, the cotangent of rho
+    if constexpr (AA) {
+        float rho_fwd = 1.0f;
+        const float *const aa_arr[] = {aa_in...}; // opacity, aa_scale
+        if (vis) { // requested with the other per-Gaussian inputs below, not behind the covariance math
+            g_rho = gsr_ld1<GSR_NT_INPUTS != 0>(aa_arr[0] + idx) * a8;
+            rho_fwd = gsr_ld1<GSR_NT_INPUTS != 0>(aa_arr[1] + idx);
+        }
+        gsr_st1<GSR_NT_MISC_STORE != 0>(dL_dopacity + idx, rho_fwd * a8); // (a culled Gaussian's record is zero)
+    }
     if (vis) {
         mean[0] = gsr_ld1<GSR_NT_INPUTS != 0>(means + 3 * idx); mean[1] = gsr_ld1<GSR_NT_INPUTS != 0>(means + 3 * idx + 1); mean[2] = gsr_ld1<GSR_NT_INPUTS != 0>(means + 3 * idx + 2);
         // (scale and quaternion: the cov3d backward at the end needs them, and so does Sigma3D when it is recomputed)
@@ -179,6 +196,17 @@ __global__ __launch_bounds__(256) void geom_backward_kernel(
                 dL_da = denom2inv * (-c * c * g_con[0] + 2.0f * b * c * g_con[1] + (denom - a * c) * g_con[2]);
                 dL_dc = denom2inv * (-a * a * g_con[2] + 2.0f * a * b * g_con[1] + (denom - a * c) * g_con[0]);
                 dL_db = denom2inv * 2.0f * (b * c * g_con[0] - (denom + 2.0f * b * b) * g_con[1] + a * b * g_con[2]);
+                if constexpr (AA) {
+                    // d rho / d(a, b, c) with a0 = a - 0.3, c0 = c - 0.3 as they came out of the projection: sums of products, nothing cancels
+                    const float a0 = c2.m[0][0], c0 = c2.m[1][1], bb = b * b;
+                    const float r = (a0 * c0 - bb) / denom;
+                    if (r > 0.000025f) { // on the floor rho is constant
+                        const float kh = g_rho * 0.3f / (2.0f * sqrtf(r) * (denom * denom));
+                        dL_da += kh * (c * c0 + bb);
+                        dL_dc += kh * (a * a0 + bb);
+                        dL_db -= kh * 2.0f * b * (a + c0);
+                    }
+                }
             }
 #define Tm(i, j) T.m[i][j]
 #define V(i, j) Vrk.m[i][j]
@@ -421,7 +449,7 @@ __global__ __launch_bounds__(256) void sh_grad_from_views_kernel(int64_t N, cons
 } // namespace
 
 hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, const GsrGrads &gr,
-                                    hipStream_t s, bool aux)
+                                    hipStream_t s, bool aux, const float *aa_scale)
 {
     if (sc.N <= 0) return hipSuccess;
     // focal lengths come from the host, formed in float64 and rounded once (reference backward.py:1044-1045, quirk Q8)
@@ -432,11 +460,19 @@ hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const G
         gr.dL_dcolor, gr.dL_dmean2D, gr.dL_dconic, gr.dL_drgb, g.sh_dir_grad, sc.scale_modifier
 #define GEOM_BWD(DG) hipLaunchKernelGGL(geom_backward_kernel<DG>, GEOM_ARGS)
 #define GEOM_BWD_AUX(DG) hipLaunchKernelGGL((geom_backward_kernel<DG, true>), GEOM_ARGS)
-    if (aux) {
+#define GEOM_BWD_AA(DG, AUX) hipLaunchKernelGGL((geom_backward_kernel<DG, AUX, true, const float *, const float *>), GEOM_ARGS, sc.opacity, aa_scale)
+    if (aa_scale) {
+        if (aux) {
+            if (g.sh_dir_grad) GEOM_BWD_AA(true, true);
+            else GEOM_BWD_AA(false, true);
+        } else if (g.sh_dir_grad) GEOM_BWD_AA(true, false);
+        else GEOM_BWD_AA(false, false);
+    } else if (aux) {
         if (g.sh_dir_grad) GEOM_BWD_AUX(true);
         else GEOM_BWD_AUX(false);
     } else if (g.sh_dir_grad) GEOM_BWD(true);
     else GEOM_BWD(false);
+#undef GEOM_BWD_AA
 #undef GEOM_BWD_AUX
 #undef GEOM_ARGS
 #undef GEOM_BWD

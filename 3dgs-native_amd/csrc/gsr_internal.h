@@ -61,7 +61,8 @@ GeomWs gsr_carve_geom(void *base, int64_t N);
 
 // ---- launchers (host functions; each enqueues on `s` and returns hipGetLastError()) ----
 hipError_t gsr_launch_preprocess(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GeomWs &ws, hipStream_t s,
-                                 bool make_fwd_order /* a spare workgroup turns ws.fwd_cost into ws.fwd_order */);
+                                 bool make_fwd_order /* a spare workgroup turns ws.fwd_cost into ws.fwd_order */,
+                                 float *aa_scale = nullptr /* antialiased mode (include/gsr_antialias.h): out [N]; NULL = classic */);
 
 // The depth sort's pass plan from the frame's visible depth extremes (bit patterns of positive floats).  Shared by the device
 // (every depth kernel derives it from DepthCtlRaw) and the host (its launch guess for the next frame, from the pinned words).
@@ -262,7 +263,8 @@ hipError_t gsr_launch_blend_backward_splat(const CamK &cam, const int32_t *range
                                            bool absgrad /* the ABS kernels (include/gsr_densify_stats.h): |dL/dmean2D| terms into columns 12-13 */);
 // aux: the AUX instantiation, which also adds the inverse-depth gradient's z term (GradRec slot 11) into dL_dmean3D
 hipError_t gsr_launch_geom_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc,
-                                    const GsrGrads &gr, hipStream_t s, bool aux);
+                                    const GsrGrads &gr, hipStream_t s, bool aux,
+                                    const float *aa_scale = nullptr /* the AA instantiation (include/gsr_antialias.h): the forward's [N] */);
 
 // tuning knobs (read once from the environment by api.hip; defaults are the measured best)
 hipError_t gsr_launch_view_payload(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *payload, hipStream_t s);
@@ -272,7 +274,7 @@ hipError_t gsr_launch_view_payload(const GsrScene &sc, const CamK &cam, const Gs
 int gsr_camera_blocks(int64_t N);
 size_t gsr_camera_scratch_bytes(int64_t N);
 hipError_t gsr_launch_camera_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *dL_dcamera, void *scratch,
-                                      hipStream_t s);
+                                      hipStream_t s, const float *aa_scale = nullptr /* the AA instantiation, as above */);
 // GSR_DEBUG (environment, read once by api.hip): every bit forces at any size a path that some frame size takes anyway, so the
 // oracle comparison covers it -- same results by other code paths (tests/test_gpu_alt_paths.py):
 //   bit  5 (32)    64-bit tile items (tile bits + id bits > 32)

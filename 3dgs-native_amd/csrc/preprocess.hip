@@ -60,6 +60,11 @@ __device__ __forceinline__ float ndc2pix(float x, float size) { return ((x + 1.0
 
 __device__ __forceinline__ int f2i(float v) { return (int)v; } // v_cvt_i32_f32: truncation
 
+// AA (include/gsr_antialias.h): the opacity compensation of the 0.3 blur.  rho = sqrt(max(0.000025, det(Sigma2D) / det(Sigma2D + 0.3 I)))
+// goes to aa_scale[i] (0 for culled Gaussians) and opacity * rho into the record and conic_opacity[3]; nothing else changes.  The
+// AA = false kernel is the product's machine code unchanged (tools/kernel_disasm_diff.py): aa_scale is a parameter of the AA = true
+// kernel alone (AaOut = float *), so the classic kernel's argument block, and with it every kernarg offset, is what it was.
+template <bool AA = false, class... AaOut>
 __global__ __launch_bounds__(256) void preprocess_kernel(
     int64_t N, const float *__restrict__ means, const float *__restrict__ scales, const float *__restrict__ rots,
     const float *__restrict__ opac, const float *__restrict__ shs, int degree, int clamped, float scale_mod, CamK cam,
@@ -68,8 +73,9 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     float *__restrict__ clamped_state, BlendRec *__restrict__ rec, TileRect *__restrict__ rect,
     uint64_t *__restrict__ depth_item, int32_t *__restrict__ zero_acc, int zero_n, int32_t *__restrict__ block_tile_sums,
     float *__restrict__ sh_dir_grad, uint32_t *__restrict__ blk_minmax, int dbg, const int32_t *__restrict__ fwd_cost,
-    int32_t *__restrict__ fwd_order, int n_tiles)
+    int32_t *__restrict__ fwd_order, int n_tiles, AaOut... aa_out)
 {
+    static_assert(sizeof...(AaOut) == (AA ? 1 : 0), "aa_scale, in the AA kernel only");
     const unsigned nblk = gridDim.x - (fwd_order ? 1u : 0u); // the workgroups that hold Gaussians
     __shared__ int s_tiles[4];
     __shared__ uint32_t s_dmin[4], s_dmax[4], s_dvis[4];
@@ -95,6 +101,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     float o_dg[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; // d(colour)/d(direction) for the backward (GsrGeom.sh_dir_grad), when asked for
     TileRect o_rect = {0, 0, 0, 0};
     bool visible = false, need_sh = false;
+    float o_rho = 0.0f; // AA
 
     constexpr bool NTI = GSR_NT_INPUTS != 0, NTM = GSR_NT_MISC_STORE != 0;
     const float px = gsr_ld1<NTI>(means + 3 * i), py = gsr_ld1<NTI>(means + 3 * i + 1), pz = gsr_ld1<NTI>(means + 3 * i + 2);
@@ -162,6 +169,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
                 o_radius = f2i(my_radius);
                 o_xy[0] = pim_x; o_xy[1] = pim_y;
                 o_con[0] = cb2 * det_inv; o_con[1] = -cb1 * det_inv; o_con[2] = cb0 * det_inv; o_con[3] = opacity_i;
+                if constexpr (AA) {
+                    // the one cancellation is a0 c0 - b^2 (a sub-pixel needle); below the floor (the Inria rasterizer's) rho is constant
+                    o_rho = sqrtf(fmaxf(0.000025f, (c2.m[0][0] * c2.m[1][1] - cb1 * cb1) * det_inv));
+                    o_con[3] = opacity_i * o_rho;
+                }
                 o_tiles = tiles;
                 o_rect.x0 = (uint16_t)rx0; o_rect.y0 = (uint16_t)ry0; o_rect.x1 = (uint16_t)rx1; o_rect.y1 = (uint16_t)ry1;
             }
@@ -280,6 +292,10 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     tiles_touched[i] = o_tiles;
     if (xy) *reinterpret_cast<float2 *>(xy + 2 * i) = make_float2(o_xy[0], o_xy[1]);
     gsr_st1<NTM>(depths + i, o_depth);
+    if constexpr (AA) {
+        float *const aa_scale[] = {aa_out...};
+        gsr_st1<NTM>(aa_scale[0] + i, o_rho);
+    }
     if (conic_opacity) *reinterpret_cast<float4 *>(conic_opacity + 4 * i) = make_float4(o_con[0], o_con[1], o_con[2], o_con[3]);
     }
 
@@ -291,16 +307,22 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
 
 } // namespace
 
-hipError_t gsr_launch_preprocess(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GeomWs &ws, hipStream_t s, bool make_fwd_order)
+hipError_t gsr_launch_preprocess(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GeomWs &ws, hipStream_t s, bool make_fwd_order,
+                                 float *aa_scale)
 {
     if (sc.N == 0) return hipSuccess;
     const int threads = 256;
     const unsigned blocks = (unsigned)gsr_div_up(sc.N, threads) + (make_fwd_order ? 1u : 0u);
-    hipLaunchKernelGGL(preprocess_kernel, dim3(blocks), dim3(threads), 0, s, sc.N, sc.means, sc.scales, sc.rotations,
-                       sc.opacity, sc.sh, sc.sh_degree, sc.clamped, sc.scale_modifier, cam, g.radii, g.xy, g.depths,
-                       g.cov3D, g.rgb, g.conic_opacity, g.tiles_touched, g.clamped_state,
-                       g.blend_records ? (BlendRec *)g.blend_records : ws.rec /* the caller's record buffer, else the workspace's */, ws.rect, ws.depth_item, ws.acc[0],
-                       3 * (int)gsr_radix_acc_ints(sc.N) /* acc[0], acc[1] (the depth sort may start at a later pass) and acc_first */, ws.scan_tmp, g.sh_dir_grad,
-                       ws.blk_minmax, gsr_debug_flags, ws.fwd_cost, make_fwd_order ? ws.fwd_order : nullptr, cam.grid_x * cam.grid_y);
+#define PREPROCESS_ARGS                                                                                                       \
+    dim3(blocks), dim3(threads), 0, s, sc.N, sc.means, sc.scales, sc.rotations, sc.opacity, sc.sh, sc.sh_degree, sc.clamped,  \
+        sc.scale_modifier, cam, g.radii, g.xy, g.depths, g.cov3D, g.rgb, g.conic_opacity, g.tiles_touched, g.clamped_state,   \
+        g.blend_records ? (BlendRec *)g.blend_records : ws.rec /* the caller's record buffer, else the workspace's */, ws.rect, \
+        ws.depth_item, ws.acc[0],                                                                                             \
+        3 * (int)gsr_radix_acc_ints(sc.N) /* acc[0], acc[1] (the depth sort may start at a later pass) and acc_first */,      \
+        ws.scan_tmp, g.sh_dir_grad, ws.blk_minmax, gsr_debug_flags, ws.fwd_cost, make_fwd_order ? ws.fwd_order : nullptr,      \
+        cam.grid_x * cam.grid_y
+    if (aa_scale) hipLaunchKernelGGL((preprocess_kernel<true, float *>), PREPROCESS_ARGS, aa_scale);
+    else hipLaunchKernelGGL(preprocess_kernel<false>, PREPROCESS_ARGS);
+#undef PREPROCESS_ARGS
     return hipGetLastError();
 }

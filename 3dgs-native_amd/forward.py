@@ -27,15 +27,21 @@ _NO_COV_RECOMPUTE = bool(int(os.environ.get("GSR_NO_COV_RECOMPUTE", "0")))   # A
 def render_gaussians(background, means3D, colors=None, opacity=None, scales=None, rotations=None, scale_modifier=1.0,
                      viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256,
                      sh=None, degree=3, campos=None, prefiltered=False, antialiasing=False, clamped=True, debug=False, *,
-                     capacity=None, capacity_hint=None, capacity_buffers=None):
+                     capacity=None, capacity_hint=None, capacity_buffers=None, rasterize_mode="classic"):
     """Render 3D Gaussians.  `colors`, `prefiltered`, `antialiasing` are accepted and ignored exactly as in
     the reference.  Returns (image (H,W,3) f32, inverse-depth (H,W) f32, buffers).
+
+    rasterize_mode="antialiased" (include/gsr_antialias.h) is the live switch: every Gaussian is drawn with opacity * rho,
+    rho = sqrt(max(0.000025, det(Sigma2D) / det(Sigma2D + 0.3 I))), so a sub-pixel Gaussian keeps its energy under the 0.3-pixel
+    blur.  The dict has the same twelve keys; `conic_opacity[:, 3]` is then the effective opacity, and rho rides on that view
+    (a private tag) for backward(rasterize_mode="antialiased").
 
     capacity=K (an int, 0 <= K <= 2^30) selects capacity mode (include/gsr_capacity.h): the whole forward is enqueued without
     waiting for the pair count D.  `point_list` then has K entries, of which the first D are valid, and the frame is to be
     trusted only once rendered_count(buffers) has said D <= K.  capacity_hint: the last D the caller knows (default K), which
     picks the backward's blend block shape; backward() passes the same value.  capacity_buffers: optional caller-owned
     {"point_list": int32 [K], "block_masks": uint8 view [K] of >= K + 16 bytes, "binning_ws": uint8 >= gsr_binning_workspace_bytes}."""
+    antialiased = _lib.check_rasterize_mode(rasterize_mode)
     if capacity is not None:
         capacity, capacity_hint = _check_capacity(capacity, capacity_hint)
     L = _lib.lib()
@@ -67,6 +73,7 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
     if _NO_RECORD_VIEWS:
         xy, conic_opacity, rgb = e((N, 2), f32), e((N, 4), f32), e((N, 3), f32)
     depths, cov3Ds, clamped_state = e((N,), f32), e((N, 6), f32), e((N, 3), f32)
+    aa_scale = e((N,), f32) if antialiased else None      # rho per Gaussian (0 where culled): selects the _aa entry points
     # d(colour)/d(direction), nine floats per Gaussian: what the SH backward needs of the 48 coefficients (GsrGeom.sh_dir_grad).
     # Only worth its 36 bytes per Gaussian when the caller's SH / position tensors can be recognised again by backward(), i.e.
     # when they are device tensors used in place.
@@ -85,11 +92,15 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
         gws = _host.workspace("geom", L.gsr_geom_workspace_bytes(N), dev, stream)
         if capacity is not None:
             point_list, block_masks, block_order, bwd_ws = _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev,
-                                                                            stream, capacity, capacity_hint, capacity_buffers or {})
+                                                                            stream, capacity, capacity_hint, capacity_buffers or {}, aa_scale)
         else:
             D = C.c_int64(0)
-            _lib.check(L.gsr_forward_count(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
-                                           C.byref(D), stream))
+            if antialiased:
+                _lib.check(L.gsr_forward_count_aa(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
+                                                  C.byref(D), _host.ptr(aa_scale), stream))
+            else:
+                _lib.check(L.gsr_forward_count(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
+                                               C.byref(D), stream))
             D = D.value
             if debug:
                 print(f"gsr: {W}x{H}, N={N}, D={D}, SH degree {degree}")
@@ -126,6 +137,15 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
             # writers, Adam and the opacity reset, bump them too: _host.written_in_place)
             clamped_state._gsr_sh_dir = (sh_dir, weakref.ref(sh), weakref.ref(means3D), tuple(cam.campos), int(degree),
                                          sh._version, means3D._version)
+        if antialiased:
+            # rho rides on the conic_opacity view, valid for this opacity (a device tensor used in place: by identity and version
+            # counter; anything else, which was copied to the device: by value against that copy) and while the view (column 5 of
+            # the records holds opacity * rho; views share their base's counter) has not been written:
+            # backward(rasterize_mode="antialiased") refuses anything else
+            if in_place(opacity, op):
+                conic_opacity._gsr_aa_scale = (aa_scale, weakref.ref(opacity), opacity._version, conic_opacity._version, None)
+            else:
+                conic_opacity._gsr_aa_scale = (aa_scale, None, None, conic_opacity._version, op)
         if in_place(scales, sc) and in_place(rotations, rot) and not _NO_COV_RECOMPUTE:
             # backward() need not read cov3Ds back when it is handed this very tensor, unwritten, with these very scales / rotations
             # (unwritten too) and the same scale_modifier: the kernel recomputes Sigma3D with the forward's instructions (gsr.h GsrGeom.cov3D)
@@ -160,7 +180,7 @@ def _check_capacity(capacity, hint):
     return out[0], out[1]
 
 
-def _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev, stream, K, hint, bufs):
+def _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev, stream, K, hint, bufs, aa_scale=None):
     """gsr_forward_capacity: buffers for K pairs, no wait for D.  The count is copied (non-blocking) into pinned memory behind an
     event; it rides on the point_list tensor (`_gsr_capacity`) for rendered_count() and backward()."""
     e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
@@ -186,8 +206,12 @@ def _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W
         bws = _host.workspace("bin", need, dev, stream)
     elif bws.numel() < need:
         raise ValueError(f"capacity_buffers: binning_ws needs {need} bytes")
-    _lib.check(L.gsr_forward_capacity(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws), gws.numel(),
-                                      _host.ptr(bws), bws.numel(), hint, stream))
+    if aa_scale is not None:      # antialiased mode (include/gsr_antialias.h)
+        _lib.check(L.gsr_forward_capacity_aa(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws),
+                                             gws.numel(), _host.ptr(bws), bws.numel(), hint, _host.ptr(aa_scale), stream))
+    else:
+        _lib.check(L.gsr_forward_capacity(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws), gws.numel(),
+                                          _host.ptr(bws), bws.numel(), hint, stream))
     count = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
     if N > 0:
         count.copy_(point_offsets[N - 1:N], non_blocking=True)

@@ -92,8 +92,11 @@ def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
     return out
 
 
+MODE_KW = {}     # --rasterize-mode antialiased: {"rasterize_mode": "antialiased"} for every render and backward of the run
+
+
 def render_view(P, c, bg):
-    return gsr.render_gaussians(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
+    return gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
                                 viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"], tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"],
                                 image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"])[0]
 
@@ -116,7 +119,7 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg):
     """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets."""
     dl, al = [], []
     for k, c in enumerate(cams):
-        _, dep, buf = gsr.render_gaussians(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
+        _, dep, buf = gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
                                            rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
                                            tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
                                            sh=P["shs"], degree=3, campos=c["camera_center"])
@@ -250,7 +253,12 @@ def main():
                     "largest screen radius exceeded PX pixels (0 = off; applies after the first opacity reset)")
     ap.add_argument("--prune-world-size", type=float, default=0.0, metavar="FRAC", help="with --densify-stat screen: prune Gaussians whose "
                     "largest scale exceeds FRAC of the scene extent (0 = off; applies after the first opacity reset)")
+    ap.add_argument("--rasterize-mode", default="classic", choices=["classic", "antialiased"], help="antialiased: every Gaussian is drawn "
+                    "with its opacity scaled by sqrt(det(Sigma2D) / det(Sigma2D + 0.3 I)), forward and backward (include/gsr_antialias.h); "
+                    "training, evaluation and target renders all use the mode")
     args = ap.parse_args()
+    if args.rasterize_mode != "classic":
+        MODE_KW["rasterize_mode"] = args.rasterize_mode
     if not args.densify_grad_threshold >= 0.0 or not args.prune_screen_size >= 0.0 or not args.prune_world_size >= 0.0:
         raise SystemExit("--densify-grad-threshold, --prune-screen-size and --prune-world-size must be >= 0")
     if args.densify_stat != "screen" and (args.absgrad or args.prune_screen_size > 0.0 or args.prune_world_size > 0.0):
@@ -294,7 +302,7 @@ def main():
         hidden = gsr.scenes.synthetic_scene(args.gaussians, 0.05, 0.5, seed=7)
         targets, depth_targets, alpha_targets = [], [], []
         for c in cams:
-            img, dep, hb = gsr.render_gaussians(background=bg, means3D=hidden["means"], opacity=hidden["opacities"], scales=hidden["scales"],
+            img, dep, hb = gsr.render_gaussians(**MODE_KW, background=bg, means3D=hidden["means"], opacity=hidden["opacities"], scales=hidden["scales"],
                                              rotations=hidden["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
                                              tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
                                              sh=hidden["shs"], degree=3, campos=c["camera_center"])
@@ -371,7 +379,7 @@ def main():
             c = cams[v]
             kw = dict(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
                       viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"], tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"],
-                      image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"])
+                      image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"], **MODE_KW)
             if capacity is None:
                 img, dep, buf = gsr.render_gaussians(**kw)
                 if args.capacity:
@@ -399,7 +407,7 @@ def main():
                              radii=buf["radii"], means2D=buf["points_xy_image"], conic_opacity=buf["conic_opacity"], rgb=buf["colors"],
                              cov3Ds=buf["cov3Ds"], clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
                              img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
-                             sh_gradient="factored" if factored else "dense", camera_grad=args.optimize_poses, **aux_kw, **abs_kw)
+                             sh_gradient="factored" if factored else "dense", camera_grad=args.optimize_poses, **aux_kw, **abs_kw, **MODE_KW)
             if screen_stats:
                 if capacity is None:                                        # this view's statistics, on this view's stream
                     model.stats.update(buf["radii"], g, use_abs=args.absgrad)

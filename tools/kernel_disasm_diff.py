@@ -5,7 +5,11 @@ llvm-objdump disassembles each offload bundle; branch targets, comments and inte
 radix_scatter_kernel gained a trailing template flag CAP (capacity mode, default false), blend_backward_splat_kernel and
 geom_backward_kernel one named AUX (include/gsr_aux_grads.h, default false; the blend kernel also two trailing pointer
 arguments), and blend_backward_splat_kernel a second one named ABS behind it (include/gsr_densify_stats.h, default false, no new
-arguments): an old instantiation is compared with its flag = false namesake.  Prints the counts and the symbols that differ, were removed or were added (JSON)."""
+arguments), and geom_backward_kernel a second one named AA behind AUX (include/gsr_antialias.h, default false) whose two pointer
+arguments are a trailing parameter pack, empty when AA is false, so that the classic kernels keep their argument block: an old
+instantiation is compared with its flag = false namesake.  preprocess_kernel and camera_partials_kernel were plain functions and
+became templates on that same AA flag and pack: a template's mangled name differs throughout, so these two are matched by their
+demangled names.  Prints the counts and the symbols that differ, were removed or were added (JSON)."""
 import glob, os, re, shutil, subprocess, sys, tempfile, json
 OBJ = "/opt/rocm/llvm/bin/llvm-objdump"
 def kernels(so):
@@ -38,10 +42,26 @@ for k in list(a):
         nk = k[:i] + "ELb0" + k[i:]
         if nk not in b:   # the flag may come with trailing arguments (blend_backward_splat_kernel: the AUX pointers)
             cand = [c for c in b if c not in a and c.startswith(k[:i] + "ELb0EEEv") and c.startswith(nk)]
+            # ... or with a trailing parameter pack that is empty when the flag is false (geom_backward_kernel: the AA arrays)
+            cand += [c for c in b if c not in a and c.startswith(k[:i] + "ELb0EJE" + k[i + 1:])]
             nk = cand[0] if len(cand) == 1 else nk
         if nk in b:
             renamed[k] = nk
             b[k] = b.pop(nk)
+# plain kernels that became templates on one flag (default false, trailing arguments if any): match "name(args" against "name<false>(args"
+TEMPLATED = ("preprocess_kernel", "camera_partials_kernel")
+def demangled(names):
+    out = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n")
+    return {n: d.replace("void ", "", 1) if d.startswith("void ") else d for n, d in zip(names, out)}
+gone_t = [k for k in a if k not in b and any(t in k for t in TEMPLATED)]
+if gone_t:
+    da, db = demangled(gone_t), demangled([c for c in b if c not in a])
+    for k in gone_t:
+        head = da[k][:-1]     # without the closing parenthesis
+        cand = [c for c, d in db.items() if any(d.replace(t + "<false>", t) .startswith(head) and t + "<false>" in d for t in TEMPLATED)]
+        if len(cand) == 1:
+            renamed[k] = cand[0]
+            b[k] = b.pop(cand[0])
 print("renamed (old -> old + trailing flag = false):", len(renamed))
 same = [k for k in a if k in b and a[k] == b[k]]
 diff = [k for k in a if k in b and a[k] != b[k]]
