@@ -172,6 +172,21 @@ ANTIALIAS_EXPORTS = {
 RASTERIZE_MODES = ("classic", "antialiased")
 
 
+class GsrFilterView(C.Structure):
+    _fields_ = [("view", C.c_float * 16), ("focal", C.c_float), ("W", C.c_int32), ("H", C.c_int32), ("pad", C.c_int32)]   # 80 bytes
+
+
+# include/gsr_filter3d.h: the 3D smoothing filter (Mip-Splatting): sampling rates from the training views, the map on
+# (scales, opacity) and its transpose (its own header, so its own table)
+FILTER3D_EXPORTS = {
+    "gsr_filter3d_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_filter3d_from_views": (C.c_int, [C.c_int64, vp, C.c_int32, vp, C.c_float, vp, vp, C.c_size_t, vp]),
+    "gsr_filter3d_apply": (C.c_int, [C.c_int64, vp, vp, vp, vp, vp, vp]),
+    "gsr_filter3d_backward": (C.c_int, [C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]),
+}
+FILTER3D_VARIANCE = 0.2     # GSR_FILTER3D_VARIANCE
+
+
 def check_rasterize_mode(mode):
     """The `rasterize_mode` keyword of render_gaussians() and backward(): refused before the library is touched."""
     if mode not in RASTERIZE_MODES:
@@ -194,7 +209,8 @@ def lib():
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items())
                                   + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
-                                  + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())):
+                                  + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
+                                  + list(FILTER3D_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

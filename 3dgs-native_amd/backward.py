@@ -32,6 +32,12 @@ float-atomic order.  Without the keyword the two columns are zero and the key is
 carries a private tag (`_gsr_backward_ws`: workspace, its version counter, whether the absolute columns were filled) through
 which densify.DensifyStats.update finds the accumulators.
 
+`filter_3d=f` (include/gsr_filter3d.h) is the backward of a frame rendered with render_gaussians(filter_3d=f): `scales` and `opacity`
+are the RAW parameters again, unwritten since the render, `f` the very tensor, unwritten too, and `conic_opacity` that frame's own
+view.  The call is the backward of the filtered scene (the frame carries its tensors) followed by the transpose of the map
+(filter3d.filter_3d_backward, in place in the arena): dL_dscale and dL_dopacity come back with respect to the raw parameters, every
+other key is the filtered scene's.  Anything else raises, as for the antialiased mode, with which it composes, as with every other keyword.
+
 `rasterize_mode="antialiased"` (include/gsr_antialias.h) is the backward of a frame rendered with that mode: `conic_opacity` must
 be that frame's own view, unwritten, and `opacity` the opacity it was rendered from, unwritten (render_gaussians leaves rho on the
 view as a private tag).  dL_dopacity is then rho times the blend stage's gradient, and the derivative of rho joins dL_dmean3D,
@@ -46,6 +52,7 @@ import torch
 
 from . import _host, _lib
 from . import dist as _dist
+from . import filter3d as _filter3d
 from . import forward as _forward
 
 _ZERO = {}
@@ -94,11 +101,20 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256, campos=None,
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
-             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic"):
+             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic", filter_3d=None):
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
+    frame_co = conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity")
+    # (before anything touches the GPU: a frame rendered without the filter or with another one, raw tensors written since the render)
+    if filter_3d is not None:
+        _filter3d.check_filter_3d(filter_3d, means3D)
+    filt = _filter3d.frame_tag(frame_co, filter_3d, scales, opacity)
+    if filt is not None:
+        # substitution, exactly: the backward below is that of the filtered scene the frame was rendered from (its own tensors, so
+        # the antialiased tag and the Sigma3D recompute recognise them); the transpose of the map follows it, in place in the arena
+        raw_scales, raw_opacity = scales, opacity
+        scales, opacity = filt[0], filt[1]
     # (before anything touches the GPU: a frame of the other mode, a copy of the view, a write since the render)
-    aa_scale = _aa_scale_of(conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity"),
-                            opacity, antialiased)
+    aa_scale = _aa_scale_of(frame_co, opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
     aux = dL_ddepth_image is not None or dL_dalpha_image is not None
@@ -290,6 +306,8 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
             else:
                 _lib.check(L.gsr_backward_camera(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(dcam), _host.ptr(ws), ws.numel(),
                                                  _host.ptr(scratch), scratch.numel(), stream))
+        if filt is not None:
+            _filter3d.filter_3d_backward(*_filter3d.raw_inputs(filt, raw_scales, raw_opacity, dev, N), filter_3d, dL_dscale, dL_dopacity)
     out = {
         "dL_dmean3D": dL_dmean3D, "dL_dcolor": dL_dcolor, "dL_dshs": dL_dsh, "dL_dopacity": dL_dopacity,
         "dL_dscale": dL_dscale, "dL_drot": dL_drot, "dL_dmean2D": dL_dmean2D, "dL_dconic": dL_dconic,

@@ -11,6 +11,7 @@ import weakref
 import torch
 
 from . import _host, _lib
+from . import filter3d as _filter3d
 from .config import TILE_M, TILE_N
 
 # Training use (the default): the forward blend kernel's spare workgroups clear the accumulators of the backward workspace while
@@ -27,7 +28,7 @@ _NO_COV_RECOMPUTE = bool(int(os.environ.get("GSR_NO_COV_RECOMPUTE", "0")))   # A
 def render_gaussians(background, means3D, colors=None, opacity=None, scales=None, rotations=None, scale_modifier=1.0,
                      viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256,
                      sh=None, degree=3, campos=None, prefiltered=False, antialiasing=False, clamped=True, debug=False, *,
-                     capacity=None, capacity_hint=None, capacity_buffers=None, rasterize_mode="classic"):
+                     capacity=None, capacity_hint=None, capacity_buffers=None, rasterize_mode="classic", filter_3d=None):
     """Render 3D Gaussians.  `colors`, `prefiltered`, `antialiasing` are accepted and ignored exactly as in
     the reference.  Returns (image (H,W,3) f32, inverse-depth (H,W) f32, buffers).
 
@@ -36,16 +37,28 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
     blur.  The dict has the same twelve keys; `conic_opacity[:, 3]` is then the effective opacity, and rho rides on that view
     (a private tag) for backward(rasterize_mode="antialiased").
 
+    filter_3d=f (include/gsr_filter3d.h; filter3d.compute_filter_3d) renders the scene under Mip-Splatting's 3D smoothing filter:
+    exactly the call with filter3d.apply_filter_3d(scales, opacity, f) in place of (scales, opacity) -- scale_modifier applies
+    after the filter.  The filtered tensors ride on the conic_opacity view (a private tag) for backward(filter_3d=f), which takes
+    the RAW scales and opacity again.  None is the unfiltered call.
+
     capacity=K (an int, 0 <= K <= 2^30) selects capacity mode (include/gsr_capacity.h): the whole forward is enqueued without
     waiting for the pair count D.  `point_list` then has K entries, of which the first D are valid, and the frame is to be
     trusted only once rendered_count(buffers) has said D <= K.  capacity_hint: the last D the caller knows (default K), which
     picks the backward's blend block shape; backward() passes the same value.  capacity_buffers: optional caller-owned
     {"point_list": int32 [K], "block_masks": uint8 view [K] of >= K + 16 bytes, "binning_ws": uint8 >= gsr_binning_workspace_bytes}."""
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
+    if filter_3d is not None:
+        _filter3d.check_filter_3d(filter_3d, means3D)
     if capacity is not None:
         capacity, capacity_hint = _check_capacity(capacity, capacity_hint)
     L = _lib.lib()
     dev = _host.device_of(means3D, sh, opacity, scales, rotations)
+    if filter_3d is not None:
+        # substitution, exactly: from here on `scales` / `opacity` are the filtered device tensors, and everything below -- the tags
+        # of the antialiased mode and of the Sigma3D recompute included -- is what a caller who passed them would get
+        raw = (scales, _host.to_dev(scales, torch.float32, dev, (-1, 3)), opacity, _host.to_dev(opacity, torch.float32, dev, (-1,)))
+        scales, opacity = _filter3d.apply_filter_3d(raw[1], raw[3], filter_3d)
     H, W = int(image_height), int(image_width)
     f32, i32 = torch.float32, torch.int32
     means = _host.to_dev(means3D, f32, dev, (-1, 3))
@@ -146,6 +159,8 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
                 conic_opacity._gsr_aa_scale = (aa_scale, weakref.ref(opacity), opacity._version, conic_opacity._version, None)
             else:
                 conic_opacity._gsr_aa_scale = (aa_scale, None, None, conic_opacity._version, op)
+        if filter_3d is not None:
+            _filter3d.tag_frame(conic_opacity, filter_3d, *raw, scales, opacity)
         if in_place(scales, sc) and in_place(rotations, rot) and not _NO_COV_RECOMPUTE:
             # backward() need not read cov3Ds back when it is handed this very tensor, unwritten, with these very scales / rotations
             # (unwritten too) and the same scale_modifier: the kernel recomputes Sigma3D with the forward's instructions (gsr.h GsrGeom.cov3D)

@@ -60,8 +60,15 @@ def ply_header(n):
     return ("\n".join(lines) + "\n").encode("ascii")
 
 
-def save_ply(params, filepath, num_points, colors=None):
-    """reference utils/point_cloud_utils.py:10 -- same signature."""
+def save_ply(params, filepath, num_points, colors=None, filter_3d=None):
+    """reference utils/point_cloud_utils.py:10 -- same signature, plus `filter_3d`: with the (N,) filter a model was trained under
+    (include/gsr_filter3d.h) the file holds the fused scales and opacities (filter3d.apply_filter_3d; Mip-Splatting's
+    create_fused_ply), so a standard viewer shows what was trained."""
+    if filter_3d is not None:
+        from . import filter3d
+        n = int(num_points)
+        scales, opacities = filter3d.apply_filter_3d(params["scales"].reshape(-1, 3)[:n], params["opacities"].reshape(-1)[:n], filter_3d)
+        params = {**params, "scales": scales, "opacities": opacities}
     v = vertex_records(params, num_points, colors)
     d = os.path.dirname(str(filepath))
     if d:

@@ -30,6 +30,9 @@ view's stream), marks clone / split candidates from the average against --densif
 --prune-screen-size (pixels) and --prune-world-size (fraction of the scene extent) once past the first opacity reset.  --absgrad
 accumulates the sums of per-pixel magnitudes instead (AbsGS; thresholds of 2-4x the signed one are usual).  The default,
 --densify-stat reference, is the reference trainer's rule: the 3D position gradient of the last view.
+
+3D smoothing filter (include/gsr_filter3d.h, filter3d.py): --filter-3d trains under Mip-Splatting's 3D filter, the other half of
+--rasterize-mode antialiased; --eval-scales 1,2,4,8 scores the result at lower resolutions, where the two matter.
 """
 import argparse
 import importlib
@@ -92,7 +95,34 @@ def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
     return out
 
 
-MODE_KW = {}     # --rasterize-mode antialiased: {"rasterize_mode": "antialiased"} for every render and backward of the run
+MODE_KW = {}     # --rasterize-mode antialiased: {"rasterize_mode": "antialiased"} for every render and backward of the run;
+                 # --filter-3d: also {"filter_3d": the current filter}, replaced at every recomputation
+
+
+def parse_eval_scales(text, W, H):
+    """--eval-scales "1,2,4": integers >= 1 that divide W and H (the target is box-averaged by s x s)."""
+    if not text:
+        return []
+    try:
+        scales = [int(x) for x in text.split(",")]
+    except ValueError:
+        raise SystemExit(f"--eval-scales takes integers separated by commas (got {text!r})") from None
+    for sc in scales:
+        if sc < 1 or W % sc or H % sc:
+            raise SystemExit(f"--eval-scales: {sc} does not divide the {W} x {H} image")
+    return scales
+
+
+def score_scales(P, cams, targets, bg, scales):
+    """{s: {"psnr", "ssim"}}: every view also rendered at W/s x H/s with the same field of view, against its target box-averaged by
+    s x s (what a camera s times as far away, or a zoom-out by s, would record)."""
+    out = {}
+    for sc in scales:
+        small = [dict(c, width=c["width"] // sc, height=c["height"] // sc) for c in cams]
+        tg = [t.reshape(c["height"] // sc, sc, c["width"] // sc, sc, 3).mean((1, 3)).contiguous() for c, t in zip(cams, targets)]
+        rows, _ = score_views(P, small, tg, bg)
+        out[str(sc)] = {"psnr": float(np.mean([r["psnr"] for r in rows])), "ssim": float(np.mean([r["ssim"] for r in rows]))}
+    return out
 
 
 def render_view(P, c, bg):
@@ -133,7 +163,7 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg):
 
 
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
-           alpha_targets=None, poses=None):
+           alpha_targets=None, poses=None, filter_log=(), eval_scales=()):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -155,10 +185,18 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
-        hrows, _ = score_views(P, hc, [torch.as_tensor(t).to(dev) for t in ht], bg)
+        ht = [torch.as_tensor(t).to(dev) for t in ht]
+        hrows, _ = score_views(P, hc, ht, bg)
+        if eval_scales:
+            summary["holdout_eval_scales"] = score_scales(P, hc, ht, bg, eval_scales)
         summary.update({"holdout": args.holdout, "holdout_views": hrows, "holdout_l1_mean": float(np.mean([r["l1"] for r in hrows])),
                         "holdout_psnr_mean": float(np.mean([r["psnr"] for r in hrows])),
                         "holdout_ssim_mean": float(np.mean([r["ssim"] for r in hrows]))})
+    if eval_scales:
+        summary["train_eval_scales"] = score_scales(P, cams, targets, bg, eval_scales)
+        for name in ("train_eval_scales", "holdout_eval_scales"):
+            if name in summary:
+                print(name + ": " + "; ".join(f"1/{k}: PSNR {v['psnr']:.2f} dB SSIM {v['ssim']:.4f}" for k, v in summary[name].items()), flush=True)
     print(f"trained {args.iterations} iterations in {wall:.2f} s ({summary['iterations_per_s']} it/s); {summary['points_start']} -> "
           f"{model.num_points} points; train L1 {summary['train_l1_mean']:.5f} PSNR {summary['train_psnr_mean']:.2f} dB"
           + (f"; holdout PSNR {summary['holdout_psnr_mean']:.2f} dB" if "holdout_psnr_mean" in summary else "")
@@ -173,6 +211,8 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
                 f.write(json.dumps({"record": "density_control", **d}) + "\n")
             for d in capacity_log:
                 f.write(json.dumps({"record": "capacity_retry", **d}) + "\n")
+            for d in filter_log:
+                f.write(json.dumps({"record": "filter_3d", **d}) + "\n")
             for i in range(0, len(curve), 100):               # every iteration's loss, 100 per line
                 rec = {"record": "loss", "from_iteration": i, "l1": [round(float(x), 6) for x in curve[i:i + 100]]}
                 if scurve is not None:                        # --lambda-dssim > 0: the mean SSIM of the same iterations
@@ -256,7 +296,21 @@ def main():
     ap.add_argument("--rasterize-mode", default="classic", choices=["classic", "antialiased"], help="antialiased: every Gaussian is drawn "
                     "with its opacity scaled by sqrt(det(Sigma2D) / det(Sigma2D + 0.3 I)), forward and backward (include/gsr_antialias.h); "
                     "training, evaluation and target renders all use the mode")
+    ap.add_argument("--filter-3d", action="store_true", help="train under Mip-Splatting's 3D smoothing filter (include/gsr_filter3d.h): "
+                    "every Gaussian is rendered with scales sqrt(s^2 + f^2) and its opacity scaled to keep its integral, f from the "
+                    "sampling rate of all training cameras; recomputed before the first iteration, after every density-control call "
+                    "that changes the point set, after an opacity reset, and every --filter-3d-interval iterations once density control "
+                    "has ended.  Density control and pruning keep testing the raw parameters; checkpoints hold the fused ones")
+    ap.add_argument("--filter-3d-variance", type=float, default=0.2, help="variance of the 3D filter in squared sampling intervals")
+    ap.add_argument("--filter-3d-interval", type=int, default=100, help="iterations between recomputations after density control has ended")
+    ap.add_argument("--eval-scales", default="", metavar="S,S,...", help="after training, also score every scored view (the training views, "
+                    "and --holdout's) rendered at W/s x H/s with the same field of view against its target box-averaged by s x s; "
+                    "PSNR and SSIM per scale go to the summary.  Every s must divide W and H")
     args = ap.parse_args()
+    if not (args.filter_3d_variance > 0.0 and np.isfinite(args.filter_3d_variance)) or args.filter_3d_interval < 1:
+        raise SystemExit("--filter-3d-variance must be positive and finite, --filter-3d-interval >= 1")
+    if not args.dataset:
+        parse_eval_scales(args.eval_scales, args.size, args.size)          # (a dataset's size is known once it is loaded)
     if args.rasterize_mode != "classic":
         MODE_KW["rasterize_mode"] = args.rasterize_mode
     if not args.densify_grad_threshold >= 0.0 or not args.prune_screen_size >= 0.0 or not args.prune_world_size >= 0.0:
@@ -309,6 +363,7 @@ def main():
             targets.append(img)
             depth_targets.append(dep.reshape(c["height"], c["width"]).clone())
             alpha_targets.append((1.0 - hb["final_Ts"].reshape(c["height"], c["width"])).contiguous())
+    eval_scales = parse_eval_scales(args.eval_scales, cams[0]["width"], cams[0]["height"])
     # --pose-noise-*: the poses the trainer starts from; the dataset's stay in true_cams for the pose error (the targets are the
     # dataset's images, or renders of the hidden scene from the dataset poses)
     true_cams = cams
@@ -363,11 +418,25 @@ def main():
 
     if args.optimize_poses:
         cams = list(cams)
+    filter_log = []
+
+    def recompute_filter(it, why):
+        """--filter-3d: the filter of the current point set from ALL training cameras at their current poses (every rank computes
+        the same bits: no collective).  One record per call; its statistics are the one read-back."""
+        f = gsr.filter3d.compute_filter_3d(model.params["positions"], cams, args.filter_3d_variance)
+        assert f.shape[0] == model.num_points == model.params["scales"].shape[0], (f.shape, model.num_points)
+        MODE_KW["filter_3d"] = f
+        q = torch.stack((f.min(), f.median(), f.max())).tolist() if f.numel() else [0.0, 0.0, 0.0]
+        filter_log.append({"iteration": it, "why": why, "points": model.num_points, "min": q[0], "median": q[1], "max": q[2]})
+
+    if args.filter_3d:
+        recompute_filter(-1, "start")
     import time
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
     for it in range(args.iterations):
         P, M, V, n = model.params, model.adam_m, model.adam_v, model.num_points
+        assert not args.filter_3d or MODE_KW["filter_3d"].shape[0] == n             # never a filter of another point set
         batch = rng.choice(len(cams), size=args.views_per_step, replace=False)
         mine = [int(batch[i]) for i in gsr.dist.views_for_rank(len(batch), rank, world)]
         arena, loss_acc, payloads = None, (torch.zeros(1, device=dev) if len(mine) > 1 else None), []
@@ -499,11 +568,19 @@ def main():
             density_log.append({"iteration": it, "cloned": log["cloned"], "split": log["split"], "split_removed": log["split_removed"],
                                 "pruned": log["pruned"], "prune_skipped": log["prune_skipped"], "opacity_reset": log["opacity_reset"],
                                 "points": model.num_points})
+        if args.filter_3d:
+            if model.num_points != n or log["cloned"] or log["split"] or log["pruned"]:
+                recompute_filter(it, "density_control")
+            elif log["opacity_reset"]:
+                recompute_filter(it, "opacity_reset")
+            elif it >= args.densify_until and it % args.filter_3d_interval == 0:
+                recompute_filter(it, "interval")
         if rank == 0 and (log["cloned"] or log["split"] or log["pruned"] or log["opacity_reset"]):
             print(f"iter {it:5d}  densify: +{log['cloned']} cloned, {log['split']} split, -{log['pruned']} pruned"
                   f"{', opacity reset' if log['opacity_reset'] else ''} -> {model.num_points} points")
         if rank == 0 and args.output and (it % args.save_interval == 0 or it == args.iterations - 1):
-            gsr.point_cloud.save_ply(model.params, os.path.join(args.output, "point_cloud", f"iteration_{it}", "point_cloud.ply"), model.num_points)
+            gsr.point_cloud.save_ply(model.params, os.path.join(args.output, "point_cloud", f"iteration_{it}", "point_cloud.ply"), model.num_points,
+                                    filter_3d=MODE_KW.get("filter_3d"))
         if rank == 0 and (it % args.print_interval == 0 or it == args.iterations - 1):
             if dssim:                                                       # the combined loss (one read of both slots)
                 l1_v, ssim_v = torch.stack([loss_hist[it], ssim_hist[it]]).tolist()
@@ -528,7 +605,7 @@ def main():
                      "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses)
+               poses, filter_log, eval_scales)
 
 
 if __name__ == "__main__":
