@@ -186,6 +186,19 @@ FILTER3D_EXPORTS = {
 }
 FILTER3D_VARIANCE = 0.2     # GSR_FILTER3D_VARIANCE
 
+# include/gsr_exposure.h: per-view exposure compensation, c' = c A + b on the rendered image, its backward and the Adam step of
+# one view's 12 numbers (its own header, so its own table)
+EXPOSURE_EXPORTS = {
+    "gsr_exposure_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_exposure_apply": (C.c_int, [vp, vp, vp, C.c_int32, C.c_int32, vp]),
+    "gsr_exposure_backward": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, C.c_size_t, vp]),
+    "gsr_exposure_adam": (C.c_int, [vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, vp]),
+}
+EXPOSURE_FLOATS = 12            # GSR_EXPOSURE_FLOATS
+EXPOSURE_BLOCK_PIXELS = 1024    # GSR_EXPOSURE_BLOCK_PIXELS
+EXPOSURE_MAX_BLOCKS = 1024      # GSR_EXPOSURE_MAX_BLOCKS
+EXPOSURE_RECORD_BYTES = 64      # GSR_EXPOSURE_RECORD_BYTES
+
 
 def check_rasterize_mode(mode):
     """The `rasterize_mode` keyword of render_gaussians() and backward(): refused before the library is touched."""
@@ -210,7 +223,7 @@ def lib():
         for name, (res, args) in (list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items())
                                   + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
                                   + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
-                                  + list(FILTER3D_EXPORTS.items())):
+                                  + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -33,6 +33,12 @@ accumulates the sums of per-pixel magnitudes instead (AbsGS; thresholds of 2-4x 
 
 3D smoothing filter (include/gsr_filter3d.h, filter3d.py): --filter-3d trains under Mip-Splatting's 3D filter, the other half of
 --rasterize-mode antialiased; --eval-scales 1,2,4,8 scores the result at lower resolutions, where the two matter.
+
+Exposure compensation (include/gsr_exposure.h, exposure.py): --optimize-exposure keeps an affine colour transform E_v per training
+view (12 numbers, c' = c A + b) and trains it with Adam (--exposure-lr-init -> --exposure-lr-final) beside the Gaussians: the loss sees
+the corrected render, and the step stays free of host waits.  --exposure-noise S (seed --exposure-seed) perturbs every training target
+once at load, for experiments.  Training views are then scored through their learned E_v, held-out views with the identity; the
+matrices go to the summary and to exposure.json beside each PLY.  One GPU only, and not with --capacity.
 """
 import argparse
 import importlib
@@ -52,8 +58,11 @@ def _self_launch():
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--optimize-poses", action="store_true")
+    ap.add_argument("--optimize-exposure", action="store_true")
     known = ap.parse_known_args()[0]
     gpus = known.gpus
+    if known.optimize_exposure and gpus > 1:
+        raise SystemExit("--optimize-exposure trains on one GPU only (per-rank exposure ownership is not implemented): drop --gpus")
     if known.optimize_poses and gpus > 1:
         raise SystemExit("--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus")
     if gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -113,14 +122,14 @@ def parse_eval_scales(text, W, H):
     return scales
 
 
-def score_scales(P, cams, targets, bg, scales):
+def score_scales(P, cams, targets, bg, scales, exposure=None):
     """{s: {"psnr", "ssim"}}: every view also rendered at W/s x H/s with the same field of view, against its target box-averaged by
     s x s (what a camera s times as far away, or a zoom-out by s, would record)."""
     out = {}
     for sc in scales:
         small = [dict(c, width=c["width"] // sc, height=c["height"] // sc) for c in cams]
         tg = [t.reshape(c["height"] // sc, sc, c["width"] // sc, sc, 3).mean((1, 3)).contiguous() for c, t in zip(cams, targets)]
-        rows, _ = score_views(P, small, tg, bg)
+        rows, _ = score_views(P, small, tg, bg, exposure)
         out[str(sc)] = {"psnr": float(np.mean([r["psnr"] for r in rows])), "ssim": float(np.mean([r["ssim"] for r in rows]))}
     return out
 
@@ -131,12 +140,14 @@ def render_view(P, c, bg):
                                 image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"])[0]
 
 
-def score_views(P, cams, targets, bg):
+def score_views(P, cams, targets, bg, exposure=None):
     """Per-view mean L1, PSNR (10 log10(1 / MSE), colours in [0, 1]) and SSIM (gaussian window, gsr_loss.h) of the current model;
-    the images come back too."""
+    the images come back too.  `exposure` (an ExposureModel whose rows are these views): view k is scored through its E_k."""
     rows, images = [], []
-    for c, t in zip(cams, targets):
+    for k, (c, t) in enumerate(zip(cams, targets)):
         img = render_view(P, c, bg).reshape(t.shape)
+        if exposure is not None:
+            img = gsr.exposure.apply_exposure(img, exposure.matrix(k), out=img)
         d = img - t
         mse = float((d * d).mean().item())
         rows.append({"l1": float(d.abs().mean().item()), "psnr": (10.0 * np.log10(1.0 / mse)) if mse > 0 else float("inf"),
@@ -163,12 +174,12 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg):
 
 
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
-           alpha_targets=None, poses=None, filter_log=(), eval_scales=()):
+           alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
     finite = {k: bool(torch.isfinite(P[k]).all().item()) for k in gsr.optimizer.GROUPS}
-    rows, images = score_views(P, cams, targets, bg)
+    rows, images = score_views(P, cams, targets, bg, exposure)
     summary = {"iterations": args.iterations, "wall_s": round(wall, 3), "iterations_per_s": round(args.iterations / wall, 1) if wall > 0 else None,
                "points_start": density_log[0]["points"], "points_final": model.num_points, "density_control_calls": len(density_log) - 1,
                "parameters_finite": finite, "train_views": rows, "train_l1_mean": float(np.mean([r["l1"] for r in rows])),
@@ -177,6 +188,10 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
         summary["capacity_retries"] = len(capacity_log)
     if poses is not None:                                                   # --pose-noise-* / --optimize-poses: error vs the dataset poses
         summary.update(poses)
+    if exposure is not None:                                                # --optimize-exposure: which rows went through a matrix, and the matrices
+        summary["exposure_applied"] = {"train_views": True, "train_eval_scales": True, "holdout_views": False, "holdout_eval_scales": False}
+        summary["exposure_final"] = exposure.state_dict()["E"]
+        summary["exposure_steps"] = list(exposure.steps)
     d_l1, a_l1 = aux_scores(P, cams, depth_targets, alpha_targets, bg)
     if d_l1 is not None:
         summary["train_depth_l1_mean"] = d_l1
@@ -193,7 +208,7 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
                         "holdout_psnr_mean": float(np.mean([r["psnr"] for r in hrows])),
                         "holdout_ssim_mean": float(np.mean([r["ssim"] for r in hrows]))})
     if eval_scales:
-        summary["train_eval_scales"] = score_scales(P, cams, targets, bg, eval_scales)
+        summary["train_eval_scales"] = score_scales(P, cams, targets, bg, eval_scales, exposure)
         for name in ("train_eval_scales", "holdout_eval_scales"):
             if name in summary:
                 print(name + ": " + "; ".join(f"1/{k}: PSNR {v['psnr']:.2f} dB SSIM {v['ssim']:.4f}" for k, v in summary[name].items()), flush=True)
@@ -306,7 +321,23 @@ def main():
     ap.add_argument("--eval-scales", default="", metavar="S,S,...", help="after training, also score every scored view (the training views, "
                     "and --holdout's) rendered at W/s x H/s with the same field of view against its target box-averaged by s x s; "
                     "PSNR and SSIM per scale go to the summary.  Every s must divide W and H")
+    ap.add_argument("--optimize-exposure", action="store_true", help="learn an affine colour transform per training view (include/"
+                    "gsr_exposure.h: 12 numbers, c' = c A + b), applied to the render before the loss, with Adam beside the Gaussians; no "
+                    "host wait is added to the step.  Training views are scored through their matrix, --holdout views with the identity; "
+                    "the matrices go to the summary and to exposure.json beside each PLY.  One GPU; not with --capacity")
+    ap.add_argument("--exposure-lr-init", type=float, default=0.01, help="Adam learning rate of the exposure matrices at the first iteration")
+    ap.add_argument("--exposure-lr-final", type=float, default=0.001, help="... and at the last (geometric decay, scheduler.decayed_lr)")
+    ap.add_argument("--exposure-noise", type=float, default=0.0, metavar="S", help="replace every training target once, at load, by "
+                    "clamp(t A_v + b_v, 0, 1): A_v = diag(exp(u_v + w_v)), u_v ~ N(0, S^2) per channel, w_v ~ N(0, S^2) shared, "
+                    "b_v ~ N(0, (S/4)^2) per channel (exposure.random_exposures)")
+    ap.add_argument("--exposure-seed", type=int, default=0, help="seed of the exposure perturbation")
     args = ap.parse_args()
+    if not (args.exposure_lr_init > 0.0 and args.exposure_lr_final > 0.0 and np.isfinite(args.exposure_lr_init + args.exposure_lr_final)):
+        raise SystemExit("--exposure-lr-init and --exposure-lr-final must be positive and finite")
+    if not (args.exposure_noise >= 0.0 and np.isfinite(args.exposure_noise)):
+        raise SystemExit("--exposure-noise must be >= 0 and finite")
+    if args.optimize_exposure and args.capacity:
+        raise SystemExit("--optimize-exposure does not combine with --capacity (an overflowed frame's exposure step would have to be undone): drop one")
     if not (args.filter_3d_variance > 0.0 and np.isfinite(args.filter_3d_variance)) or args.filter_3d_interval < 1:
         raise SystemExit("--filter-3d-variance must be positive and finite, --filter-3d-interval >= 1")
     if not args.dataset:
@@ -331,6 +362,8 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.optimize_poses and (args.gpus > 1 or world > 1):
         raise SystemExit("--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus")
+    if args.optimize_exposure and (args.gpus > 1 or world > 1):
+        raise SystemExit("--optimize-exposure trains on one GPU only (per-rank exposure ownership is not implemented): drop --gpus")
     if args.gpus > 1 and world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
     if not 1 <= args.views_per_step <= args.views:
@@ -364,6 +397,10 @@ def main():
             depth_targets.append(dep.reshape(c["height"], c["width"]).clone())
             alpha_targets.append((1.0 - hb["final_Ts"].reshape(c["height"], c["width"])).contiguous())
     eval_scales = parse_eval_scales(args.eval_scales, cams[0]["width"], cams[0]["height"])
+    if args.exposure_noise > 0.0:                                            # every target as a camera with that exposure error stored it
+        noise = gsr.exposure.random_exposures(len(targets), args.exposure_noise, args.exposure_seed)
+        targets = [gsr.exposure.perturbed_target(t.reshape(c["height"], c["width"], 3), e) for t, c, e in zip(targets, cams, noise)]
+    expo = gsr.exposure.ExposureModel(len(cams), dev) if args.optimize_exposure else None
     # --pose-noise-*: the poses the trainer starts from; the dataset's stay in true_cams for the pose error (the targets are the
     # dataset's images, or renders of the hidden scene from the dataset poses)
     true_cams = cams
@@ -455,6 +492,10 @@ def main():
                     sized_D.append(int(buf["point_list"].shape[0]))        # (the sized path's D: what --capacity learns K from)
             else:
                 img, dep, buf = gsr.render_gaussians(**kw, capacity=capacity, capacity_hint=cap["D_of"].get(v, cap["max_D"]))
+            raw = img
+            if expo is not None:                                            # the loss (and its curve) sees the corrected render
+                raw = img.reshape(c["height"], c["width"], 3)
+                img = gsr.exposure.apply_exposure(raw, expo.matrix(v))
             # (one view per rank and step: the L1 sum goes straight into this iteration's slot of the loss curve)
             if dssim:                                                       # ... and the SSIM sum into the SSIM curve's
                 loss_sum, ssim_sum, dpix = gsr.loss.l1_dssim_loss_and_gradients(
@@ -468,6 +509,8 @@ def main():
                 aux_kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
             if args.lambda_alpha > 0.0:
                 aux_kw["dL_dalpha_image"] = gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], alpha_targets[v], None, args.lambda_alpha)[1]
+            if expo is not None:                                            # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
+                dpix, dE = gsr.exposure.exposure_backward(raw, expo.matrix(v), dpix, out=dpix)
             if aux:                                                         # the forward's depths: records re-packed with 1/depth
                 aux_kw["geom_buffer"] = {"depths": buf["depths"]}
             g = gsr.backward(background=bg, means3D=P["positions"], dL_dpixels=dpix, opacity=P["opacities"], shs=P["shs"], scales=P["scales"],
@@ -482,6 +525,8 @@ def main():
                     model.stats.update(buf["radii"], g, use_abs=args.absgrad)
                 else:                                                       # --capacity: only once the overflow check has passed
                     buf["_backward_out"] = g
+            if expo is not None:                                            # one single-wave launch; no read-back
+                expo.step(v, dE, gsr.scheduler.decayed_lr(args.exposure_lr_init, args.exposure_lr_final, it, args.iterations))
             if args.optimize_poses:                                         # 35 floats back: the wait this flag accepts
                 gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
                 pose_step(v, gsr.pose.pose_gradient(start_cams[v], pose_xi[v], gv.view(4, 4), gp.view(4, 4), gc))
@@ -581,6 +626,9 @@ def main():
         if rank == 0 and args.output and (it % args.save_interval == 0 or it == args.iterations - 1):
             gsr.point_cloud.save_ply(model.params, os.path.join(args.output, "point_cloud", f"iteration_{it}", "point_cloud.ply"), model.num_points,
                                     filter_3d=MODE_KW.get("filter_3d"))
+            if expo is not None:                                            # the matrices beside the PLY
+                with open(os.path.join(args.output, "point_cloud", f"iteration_{it}", "exposure.json"), "w") as f:
+                    json.dump(expo.state_dict(), f)
         if rank == 0 and (it % args.print_interval == 0 or it == args.iterations - 1):
             if dssim:                                                       # the combined loss (one read of both slots)
                 l1_v, ssim_v = torch.stack([loss_hist[it], ssim_hist[it]]).tolist()
@@ -605,7 +653,7 @@ def main():
                      "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses, filter_log, eval_scales)
+               poses, filter_log, eval_scales, expo)
 
 
 if __name__ == "__main__":
