@@ -199,6 +199,14 @@ EXPOSURE_BLOCK_PIXELS = 1024    # GSR_EXPOSURE_BLOCK_PIXELS
 EXPOSURE_MAX_BLOCKS = 1024      # GSR_EXPOSURE_MAX_BLOCKS
 EXPOSURE_RECORD_BYTES = 64      # GSR_EXPOSURE_RECORD_BYTES
 
+# include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
+# header, so its own table)
+DEBUG_LAYOUT_EXPORTS = {
+    "gsr_fwd_order_tables_offset": (C.c_int, [C.c_int64, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+}
+FWD_ORDER_MAX_TILES = 4096      # GSR_FWD_ORDER_MAX_TILES
+
+
 
 def check_rasterize_mode(mode):
     """The `rasterize_mode` keyword of render_gaussians() and backward(): refused before the library is touched."""
@@ -223,7 +231,8 @@ def lib():
         for name, (res, args) in (list(EXPORTS.items()) + list(CAPACITY_EXPORTS.items()) + list(LOSS_EXPORTS.items())
                                   + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
                                   + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
-                                  + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())):
+                                  + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
+                                  + list(DEBUG_LAYOUT_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -13,6 +13,7 @@
 #include "gsr_aux_grads.h"
 #include "gsr_camera_grads.h"
 #include "gsr_capacity.h"
+#include "gsr_debug_layout.h"
 #include "gsr_densify_stats.h"
 #include "gsr_internal.h"
 
@@ -375,6 +376,18 @@ size_t gsr_geom_workspace_bytes(int64_t N) { return gsr_carve_geom(nullptr, N < 
 size_t gsr_binning_workspace_bytes(int64_t, int64_t D, int32_t, int32_t) { return carve_bin(nullptr, D < 0 ? 0 : D).bytes; }
 size_t gsr_backward_workspace_bytes(int64_t N, int64_t, int32_t, int32_t) { return carve_bwd(nullptr, N < 0 ? 0 : N).bytes; }
 size_t gsr_backward_accumulators_offset(int64_t N) { return gsr_align((size_t)(N < 0 ? 0 : N) * sizeof(BlendRec)); } // carve_bwd: the records come first
+// (include/gsr_debug_layout.h) the two tile-order tables inside the geom workspace, from the carve itself
+int gsr_fwd_order_tables_offset(int64_t N, size_t *fwd_cost_offset, size_t *fwd_order_offset)
+{
+    static_assert(GSR_FWD_ORDER_MAX_TILES == GSR_FO_MAX_TILES, "the header's table size is the kernels'");
+    if (!fwd_cost_offset || !fwd_order_offset) return GSR_E_NULL;
+    if (N < 0 || N > 0x7FFFFFFFLL) return GSR_E_DIMS;
+    static char base[1]; // carved, never dereferenced
+    const GeomWs w = gsr_carve_geom(base, N);
+    *fwd_cost_offset = (size_t)((const char *)w.fwd_cost - base);
+    *fwd_order_offset = (size_t)((const char *)w.fwd_order - base);
+    return GSR_OK;
+}
 size_t gsr_block_order_ints(int32_t W, int32_t H)
 {
     if (W <= 0 || H <= 0) return 0;
