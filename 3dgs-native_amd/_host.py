@@ -1,6 +1,7 @@
 """Host-side plumbing shared by forward.py and backward.py: tensor conversion, camera struct packing,
 workspace caching.  PyTorch is only the owner of device memory and streams here."""
 import ctypes as C
+import weakref
 
 import numpy as np
 import torch
@@ -111,8 +112,7 @@ def raw_stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def stream_ptr(dev):
-    return raw_stream(dev)
+stream_ptr = raw_stream
 
 
 class on_device:
@@ -136,6 +136,19 @@ def version_of(t):
     """torch's in-place write counter of a tensor (None for anything else): tags that let backward() reuse state the forward
     derived from an array record it, so a caller's in-place write between the two calls is seen."""
     return t._version if isinstance(t, torch.Tensor) else None
+
+
+def stamp(t):
+    """The record of "this very tensor, unwritten": (weak reference, write counter) of a torch tensor, (None, None) for anything else.  Every tag
+    that carries forward state to backward() states its tensor conditions as stamps (views share their base's counter, so a write
+    through any view of a tensor, or into its base, is seen)."""
+    return (weakref.ref(t), t._version) if isinstance(t, torch.Tensor) else (None, None)
+
+
+def unwritten(stamp, given):
+    """True when `given` is the tensor the stamp was taken of and has not been written in place since."""
+    ref, version = stamp
+    return ref is not None and ref() is given and version_of(given) == version
 
 
 def written_in_place(*tensors):

@@ -11,8 +11,6 @@ RAW scales and opacity; both are exactly the substitution above around the uncha
 positions and the cameras (max and min do not depend on order): every rank of a data-parallel run computes the same bits, so no
 collective is needed.  It is recomputed when the point set changes, not every iteration (examples/train.py --filter-3d).
 """
-import weakref
-
 import numpy as np
 import torch
 
@@ -145,24 +143,21 @@ def _check_out(t, shape, dev, name):
 
 
 # ---- the keyword of render_gaussians() / backward(): the filtered tensors ride on the frame, as rho of the antialiased mode does ----
-def _identity_of(given, used):
-    """How backward() recognises the raw array a frame was rendered from: a torch tensor by identity and version counter, anything
-    else (it was copied to the device) by value against that copy."""
-    if isinstance(given, torch.Tensor):
-        return weakref.ref(given), given._version, None
-    return None, None, used
+def _raw(given, used):
+    """How backward() recognises the raw array a frame was rendered from: a torch tensor by its stamp, anything else (it was copied
+    to the device) by value against that copy."""
+    return _host.stamp(given), None if isinstance(given, torch.Tensor) else used
 
 
 def tag_frame(conic_opacity, filter_3d, raw_scales, sc, raw_opacity, op, sc_f, op_f):
-    """Called by render_gaussians(filter_3d=...): the filtered tensors (sc_f, op_f) the frame was rendered from, the filter tensor
-    (identity and version) and the raw arrays' identities ride on the frame's conic_opacity view."""
-    conic_opacity._gsr_filter_3d = (sc_f, op_f, weakref.ref(filter_3d), filter_3d._version, _identity_of(raw_scales, sc), _identity_of(raw_opacity, op),
-                                    conic_opacity._version)
+    """Called by render_gaussians(filter_3d=...): the filtered tensors (sc_f, op_f) the frame was rendered from ride on the frame's
+    conic_opacity view, with the stamps (_host.stamp) of the filter tensor, of the view itself and of the raw arrays."""
+    conic_opacity._gsr_filter_3d = (sc_f, op_f, _host.stamp(filter_3d), _host.stamp(conic_opacity), _raw(raw_scales, sc), _raw(raw_opacity, op))
 
 
-def _same(identity, given, dev, shape, what):
-    ref, ver, copy = identity
-    if ref is not None:      # (identity and version: frame_tag has checked them)
+def _same(raw, given, dev, shape, what):
+    stamp, copy = raw
+    if copy is None:      # (a tensor, unwritten: frame_tag has checked its stamp)
         return _host.to_dev(given, torch.float32, dev, shape)
     if isinstance(given, torch.Tensor) or not torch.equal(copy, _host.to_dev(given, torch.float32, dev, shape)):
         raise ValueError(f"backward(filter_3d=...): `{what}` is not the raw array this frame was rendered from")
@@ -181,15 +176,15 @@ def frame_tag(conic_opacity, filter_3d, scales, opacity):
     if tag is None:
         raise ValueError("backward(filter_3d=...) needs the conic_opacity view of a frame rendered with render_gaussians(filter_3d=...), "
                          "not a copy of it and not an unfiltered frame")
-    _, _, f_ref, f_ver, _, _, rec_ver = tag
-    if f_ref() is not filter_3d:
+    _, _, f_stamp, rec_stamp, raw_scales, raw_opacity = tag
+    if f_stamp[0]() is not filter_3d:
         raise ValueError("backward(filter_3d=...): this frame was rendered with another filter tensor")
-    if filter_3d._version != f_ver:
+    if not _host.unwritten(f_stamp, filter_3d):
         raise ValueError("backward(filter_3d=...): filter_3d was written in place since the render")
-    if conic_opacity._version != rec_ver:
+    if not _host.unwritten(rec_stamp, conic_opacity):
         raise ValueError("backward(filter_3d=...): the forward's records were written in place after the render")
-    for (ref, ver, _), given, what in ((tag[4], scales, "scales"), (tag[5], opacity, "opacity")):
-        if ref is not None and (ref() is not given or _host.version_of(given) != ver):
+    for (stamp, copy), given, what in ((raw_scales, scales, "scales"), (raw_opacity, opacity, "opacity")):
+        if copy is None and not _host.unwritten(stamp, given):
             raise ValueError(f"backward(filter_3d=...): `{what}` is not the raw tensor this frame was rendered from, or was written in place since")
     return tag
 

@@ -6,7 +6,6 @@ arrays come back as torch tensors on the GPU instead of wp.array (callers do `.c
 import ctypes as C
 import operator
 import os
-import weakref
 
 import torch
 
@@ -21,8 +20,6 @@ from .config import TILE_M, TILE_N
 # process never pays for it); the first training step's backward clears for itself.
 PRECLEAR_BACKWARD = not bool(int(os.environ.get("GSR_NO_PRECLEAR", "0")))
 _backward_seen = False          # set by backward.backward()
-_NO_RECORD_VIEWS = bool(int(os.environ.get("GSR_NO_RECORD_VIEWS", "0")))    # A/B switch: packed xy / conic_opacity / colors arrays beside the records
-_NO_COV_RECOMPUTE = bool(int(os.environ.get("GSR_NO_COV_RECOMPUTE", "0")))   # A/B switch: backward() always reads cov3Ds back
 
 
 def render_gaussians(background, means3D, colors=None, opacity=None, scales=None, rotations=None, scale_modifier=1.0,
@@ -83,24 +80,22 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
     # instead of twice.  `.cpu().numpy()`, indexing and arithmetic work on them as on any tensor; `.contiguous()` gives a packed copy.
     records = e((N, 16), f32)
     xy, conic_opacity, rgb = records[:, 0:2], records[:, 2:6], records[:, 6:9]
-    if _NO_RECORD_VIEWS:
-        xy, conic_opacity, rgb = e((N, 2), f32), e((N, 4), f32), e((N, 3), f32)
     depths, cov3Ds, clamped_state = e((N,), f32), e((N, 6), f32), e((N, 3), f32)
-    aa_scale = e((N,), f32) if antialiased else None      # rho per Gaussian (0 where culled): selects the _aa entry points
+    aa_scale = e((N,), f32) if antialiased else None      # rho per Gaussian (0 where culled); None is the classic mode
     # d(colour)/d(direction), nine floats per Gaussian: what the SH backward needs of the 48 coefficients (GsrGeom.sh_dir_grad).
     # Only worth its 36 bytes per Gaussian when the caller's SH / position tensors can be recognised again by backward(), i.e.
     # when they are device tensors used in place.
     in_place = lambda given, used: isinstance(given, torch.Tensor) and given.is_cuda and given.data_ptr() == used.data_ptr()
     sh_dir = e((N, 9), f32) if (N > 0 and in_place(sh, shs) and in_place(means3D, means)) else None
-    arr = (lambda t: _host.ptr(t)) if _NO_RECORD_VIEWS else (lambda t: None)
-    geom = _lib.GsrGeom(_host.ptr(radii), _host.ptr(tiles_touched), _host.ptr(point_offsets), arr(xy), _host.ptr(depths),
-                        _host.ptr(cov3Ds), arr(rgb), arr(conic_opacity), _host.ptr(clamped_state), _host.ptr(records), _host.ptr(sh_dir))
+    geom = _lib.GsrGeom(_host.ptr(radii), _host.ptr(tiles_touched), _host.ptr(point_offsets), None, _host.ptr(depths),
+                        _host.ptr(cov3Ds), None, None, _host.ptr(clamped_state), _host.ptr(records), _host.ptr(sh_dir))
     image, depth_image = e((H, W, 3), f32), e((H, W), f32)
     final_Ts, n_contrib = e((H, W), f32), e((H, W), i32)
     img = _lib.GsrImage(_host.ptr(image), _host.ptr(depth_image), _host.ptr(final_Ts), _host.ptr(n_contrib))
     ranges = e((gx * gy, 2), i32)
     stream = _host.raw_stream(dev)
 
+    # One entry point per stage: the _aa exports with aa_scale = NULL are the classic calls (csrc/api.hip).
     with _host.on_device(dev):
         gws = _host.workspace("geom", L.gsr_geom_workspace_bytes(N), dev, stream)
         if capacity is not None:
@@ -108,65 +103,47 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
                                                                             stream, capacity, capacity_hint, capacity_buffers or {}, aa_scale)
         else:
             D = C.c_int64(0)
-            if antialiased:
-                _lib.check(L.gsr_forward_count_aa(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
-                                                  C.byref(D), _host.ptr(aa_scale), stream))
-            else:
-                _lib.check(L.gsr_forward_count(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(),
-                                               C.byref(D), stream))
+            _lib.check(L.gsr_forward_count_aa(C.byref(scene), C.byref(cam), C.byref(geom), _host.ptr(gws), gws.numel(), C.byref(D),
+                                              _host.ptr(aa_scale), stream))
             D = D.value
             if debug:
                 print(f"gsr: {W}x{H}, N={N}, D={D}, SH degree {degree}")
-            point_list = e((D,), i32)
-            # per-entry 8x4-block hit masks: written by the forward blend, read by backward() (allocated with 16 spare bytes: the
-            # backward reads them 16 at a time)
-            block_masks = e((D + 16,), torch.uint8)[:D]
-            # the backward blend's blocks filed by cost, heaviest first (GsrBinning.block_order): filled by the forward blend from the masks
-            block_order = e((int(L.gsr_block_order_ints(W, H)),), i32)
-            # The backward's workspace, one per call: its accumulator records are what backward() returns dL_dcolor / dL_dmean2D /
-            # dL_dconic as views of, so it must not be shared between calls.  Handed to the forward, its records are cleared by the
-            # blend kernel's spare workgroups.
-            bwd_ws = None
-            if PRECLEAR_BACKWARD and _backward_seen and N > 0 and D > 0:
-                bwd_ws = e((int(L.gsr_backward_workspace_bytes(N, D, W, H)),), torch.uint8)
-            binning = _lib.GsrBinning(D, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(block_masks), _host.ptr(block_order),
-                                      _host.ptr(bwd_ws), 0)
+            point_list, block_masks, block_order, bwd_ws, binning = _binning_buffers(L, ranges, N, D, W, H, dev, {}, N > 0 and D > 0)
             bws = _host.workspace("bin", L.gsr_binning_workspace_bytes(N, D, W, H), dev, stream)
             _lib.check(L.gsr_forward_render(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img),
                                             _host.ptr(gws), gws.numel(), _host.ptr(bws), bws.numel(), stream))
-    # Let a following backward() use the records as they are: the tag rides on the means2D view (the reference's callers re-pack
-    # the dicts by hand, train.py:986-1000) and is honoured when backward() is handed these very three views, unwritten since
-    # (views share their base's version counter, so a write through any of them, or into the records, is seen).
+    # Let a following backward() use what this call derived.  Every tag rides on the tensor backward() is handed anyway (the
+    # reference's callers re-pack the dicts by hand, train.py:986-1000) and states "valid while these very tensors are unwritten"
+    # as _host.stamp()s, which backward() holds against what it is given with _host.unwritten() -- torch's version counters; the
+    # library's own in-place writers, Adam and the opacity reset, bump them too (_host.written_in_place).  Anything else a tag
+    # depends on is a plain field of it.
     if N > 0:
-        xy._gsr_records = (records, records._version, {"means2D": weakref.ref(xy), "conic_opacity": weakref.ref(conic_opacity), "rgb": weakref.ref(rgb)})
-        # likewise the block masks ride on the point_list tensor (their own allocation, alive as long as it is): a caller
-        # that hands backward() this very tensor gets the mask-driven compaction, anyone else the self-contained one
-        # -- and only together with the other buffers of this call (backward() checks identity): the masks describe these
-        # records, up to these n_contrib
+        stamp = _host.stamp
+        # the records stand in for the three arrays when backward() gets these very views (views share their base's counter, so a
+        # write through any of them, or into the records, is seen)
+        xy._gsr_records = (records, {"means2D": stamp(xy), "conic_opacity": stamp(conic_opacity), "rgb": stamp(rgb)})
         if sh_dir is not None:
             # the direction derivatives ride on clamped_state (which backward() receives as `clamped`), valid for these very
             # sh / means3D tensors, this camera position and this degree
-            # -- and only while neither has been written in place since (torch's version counters; the library's own in-place
-            # writers, Adam and the opacity reset, bump them too: _host.written_in_place)
-            clamped_state._gsr_sh_dir = (sh_dir, weakref.ref(sh), weakref.ref(means3D), tuple(cam.campos), int(degree),
-                                         sh._version, means3D._version)
+            clamped_state._gsr_sh_dir = (sh_dir, stamp(sh), stamp(means3D), tuple(cam.campos), int(degree))
         if antialiased:
-            # rho rides on the conic_opacity view, valid for this opacity (a device tensor used in place: by identity and version
-            # counter; anything else, which was copied to the device: by value against that copy) and while the view (column 5 of
-            # the records holds opacity * rho; views share their base's counter) has not been written:
+            # rho rides on the conic_opacity view (column 5 of the records holds opacity * rho), valid while that view is unwritten (the
+            # tensor a tag rides on needs no reference to itself: its version alone) and for this opacity: a device tensor used in
+            # place by its stamp; anything else, which was copied to the device, by value against that copy.
             # backward(rasterize_mode="antialiased") refuses anything else
-            if in_place(opacity, op):
-                conic_opacity._gsr_aa_scale = (aa_scale, weakref.ref(opacity), opacity._version, conic_opacity._version, None)
-            else:
-                conic_opacity._gsr_aa_scale = (aa_scale, None, None, conic_opacity._version, op)
+            by_value = None if in_place(opacity, op) else op
+            conic_opacity._gsr_aa_scale = (aa_scale, *stamp(opacity if by_value is None else None), conic_opacity._version, by_value)
         if filter_3d is not None:
             _filter3d.tag_frame(conic_opacity, filter_3d, *raw, scales, opacity)
-        if in_place(scales, sc) and in_place(rotations, rot) and not _NO_COV_RECOMPUTE:
-            # backward() need not read cov3Ds back when it is handed this very tensor, unwritten, with these very scales / rotations
-            # (unwritten too) and the same scale_modifier: the kernel recomputes Sigma3D with the forward's instructions (gsr.h GsrGeom.cov3D)
-            cov3Ds._gsr_sigma_of = (weakref.ref(scales), weakref.ref(rotations), scales._version, rotations._version, float(scale_modifier), cov3Ds._version)
+        if in_place(scales, sc) and in_place(rotations, rot):
+            # backward() need not read cov3Ds back when it is handed this very tensor with these very scales / rotations and the
+            # same scale_modifier: the kernel recomputes Sigma3D with the forward's instructions (gsr.h GsrGeom.cov3D)
+            cov3Ds._gsr_sigma_of = (stamp(cov3Ds), stamp(scales), stamp(rotations), float(scale_modifier))
+        # the block masks, and the block order derived from them, ride on the point_list tensor: they describe these records, up to
+        # these n_contrib, so a caller that hands backward() every one of this call's buffers gets the mask-driven compaction,
+        # anyone else the self-contained one
         owners = {"ranges": ranges, "n_contrib": n_contrib, "final_Ts": final_Ts, "means2D": xy, "conic_opacity": conic_opacity}
-        point_list._gsr_block_masks = (block_masks, {k: (weakref.ref(v), v._version) for k, v in owners.items()}, block_order)
+        point_list._gsr_block_masks = (block_masks, {k: stamp(v) for k, v in owners.items()}, block_order)
         if bwd_ws is not None:      # "a backward workspace with clean accumulators": the first backward() handed this point_list takes it
             point_list._gsr_cleared_ws = [bwd_ws, N]
     return image, depth_image, {
@@ -195,38 +172,47 @@ def _check_capacity(capacity, hint):
     return out[0], out[1]
 
 
-def _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev, stream, K, hint, bufs, aa_scale=None):
-    """gsr_forward_capacity: buffers for K pairs, no wait for D.  The count is copied (non-blocking) into pinned memory behind an
-    event; it rides on the point_list tensor (`_gsr_capacity`) for rendered_count() and backward()."""
+def _binning_buffers(L, ranges, N, D, W, H, dev, bufs, preclear):
+    """The binning buffers of one forward with room for D pairs, and their GsrBinning: point_list and block_masks (the caller's
+    `capacity_buffers`, else fresh), block order, and the pre-cleared backward workspace when `preclear` and the process trains."""
     e = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
     point_list = bufs.get("point_list")
     if point_list is None:
-        point_list = e((K,), torch.int32)
+        point_list = e((D,), torch.int32)
+    # per-entry 8x4-block hit masks: written by the forward blend, read by backward() (allocated with 16 spare bytes: the backward
+    # reads them 16 at a time)
     block_masks = bufs.get("block_masks")
     if block_masks is None:
-        block_masks = e((K + 16,), torch.uint8)[:K]
-    if point_list.numel() < K or block_masks.numel() < K:
+        block_masks = e((D + 16,), torch.uint8)[:D]
+    if point_list.numel() < D or block_masks.numel() < D:
         raise ValueError("capacity_buffers: point_list and block_masks need K entries")
+    # the backward blend's blocks filed by cost, heaviest first (GsrBinning.block_order): filled by the forward blend from the masks
     block_order = e((int(L.gsr_block_order_ints(W, H)),), torch.int32)
+    # The backward's workspace, one per call: its accumulator records are what backward() returns dL_dcolor / dL_dmean2D /
+    # dL_dconic as views of, so it must not be shared between calls.  Handed to the forward, its records are cleared by the
+    # blend kernel's spare workgroups.
     bwd_ws = None
-    if PRECLEAR_BACKWARD and _backward_seen and N > 0:      # (D is not known here: the clear is promised for an empty frame too)
-        bwd_ws = e((int(L.gsr_backward_workspace_bytes(N, K, W, H)),), torch.uint8)
+    if PRECLEAR_BACKWARD and _backward_seen and preclear:
+        bwd_ws = e((int(L.gsr_backward_workspace_bytes(N, D, W, H)),), torch.uint8)
+    binning = _lib.GsrBinning(D, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(block_masks), _host.ptr(block_order), _host.ptr(bwd_ws), 0)
+    return point_list, block_masks, block_order, bwd_ws, binning
+
+
+def _forward_capacity(L, scene, cam, geom, img, ranges, gws, point_offsets, N, W, H, dev, stream, K, hint, bufs, aa_scale=None):
+    """gsr_forward_capacity: buffers for K pairs, no wait for D.  The count is copied (non-blocking) into pinned memory behind an
+    event; it rides on the point_list tensor (`_gsr_capacity`) for rendered_count() and backward()."""
+    # (D is not known here: the clear is promised for an empty frame too)
+    point_list, block_masks, block_order, bwd_ws, binning = _binning_buffers(L, ranges, N, K, W, H, dev, bufs, N > 0)
     # the shape hint: the backward skips its blend for D = 0, so a frame that may hold pairs passes at least 1
-    hint = (K if hint is None else hint) if K > 0 else 0
-    hint = max(1, hint) if K > 0 else 0
-    binning = _lib.GsrBinning(K, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(block_masks), _host.ptr(block_order), _host.ptr(bwd_ws), 0)
+    hint = max(1, K if hint is None else hint) if K > 0 else 0
     need = int(L.gsr_binning_workspace_bytes(N, K, W, H))
     bws = bufs.get("binning_ws")
     if bws is None:
         bws = _host.workspace("bin", need, dev, stream)
     elif bws.numel() < need:
         raise ValueError(f"capacity_buffers: binning_ws needs {need} bytes")
-    if aa_scale is not None:      # antialiased mode (include/gsr_antialias.h)
-        _lib.check(L.gsr_forward_capacity_aa(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws),
-                                             gws.numel(), _host.ptr(bws), bws.numel(), hint, _host.ptr(aa_scale), stream))
-    else:
-        _lib.check(L.gsr_forward_capacity(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws), gws.numel(),
-                                          _host.ptr(bws), bws.numel(), hint, stream))
+    _lib.check(L.gsr_forward_capacity_aa(C.byref(scene), C.byref(cam), C.byref(geom), C.byref(binning), C.byref(img), _host.ptr(gws), gws.numel(),
+                                         _host.ptr(bws), bws.numel(), hint, _host.ptr(aa_scale), stream))
     count = torch.zeros((1,), dtype=torch.int32, pin_memory=True)
     if N > 0:
         count.copy_(point_offsets[N - 1:N], non_blocking=True)

@@ -1,6 +1,6 @@
 #!/bin/bash
 # usage (GPU box, repo root): bash tools/ab_env.sh "STAGE [STAGE...]" REPS "ENV=..." ["ENV=..." ...]
-# Like tools/ab.sh, but alternates ENVIRONMENT settings of the one product library (e.g. "X=0" "GSR_NO_COV_RECOMPUTE=1") instead of
+# Like tools/ab.sh, but alternates ENVIRONMENT settings of the one product library (e.g. "GSR_NO_PRECLEAR=0" "GSR_NO_PRECLEAR=1") instead of
 # builds: same box, same clocks, interleaved.  Prints ms_per_step, the median step and the named stage times per run, then
 # the per-setting minimum of each column.  Extra bench flags: AB_ARGS.
 set -o pipefail   # a failed bench run fails its line, and the first failure ends the script
