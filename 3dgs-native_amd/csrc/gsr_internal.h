@@ -276,7 +276,8 @@ size_t gsr_camera_scratch_bytes(int64_t N);
 hipError_t gsr_launch_camera_backward(const GsrScene &sc, const CamK &cam, const GsrGeom &g, const GradRec *acc, float *dL_dcamera, void *scratch,
                                       hipStream_t s, const float *aa_scale = nullptr /* the AA instantiation, as above */);
 // GSR_DEBUG (environment, read once by api.hip): every bit forces at any size a path that some frame size takes anyway, so the
-// oracle comparison covers it -- same results by other code paths (tests/test_gpu_alt_paths.py):
+// oracle comparison covers it -- same results by other code paths (tests/test_gpu_alt_paths.py; in capacity mode
+// tests/test_gpu_capacity_edges.py):
 //   bit  5 (32)    64-bit tile items (tile bits + id bits > 32)
 //   bit  6 (64)    the large-n radix chunks (N > 4 M)
 //   bit  7 (128)   the scanned super-block rows of many-block radix passes (radix_superscan_kernel; D > 8.4 M)

@@ -1,6 +1,8 @@
 """Capacity-mode forward (include/gsr_capacity.h) against the sized path on the same inputs: the same integer outputs and
 bit-identical images for every capacity K >= D, zeros for a frame without pairs, every write inside the K-sized buffers when
-D > K (guard tails), no host wait, and a trainer run that overflows on purpose and recovers."""
+D > K (guard tails), no host wait, and a trainer run that overflows on purpose and recovers.  These are the cases at the
+workload's own sizes and tiers; K and D at block edges, K alone crossing a tier, dirty buffers, frame sequences and the forced
+GSR_DEBUG paths on small frames are in tests/test_gpu_capacity_edges.py."""
 import json
 import os
 import re
