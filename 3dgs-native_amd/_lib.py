@@ -199,6 +199,15 @@ EXPOSURE_BLOCK_PIXELS = 1024    # GSR_EXPOSURE_BLOCK_PIXELS
 EXPOSURE_MAX_BLOCKS = 1024      # GSR_EXPOSURE_MAX_BLOCKS
 EXPOSURE_RECORD_BYTES = 64      # GSR_EXPOSURE_RECORD_BYTES
 
+# include/gsr_weighted_loss.h: the colour loss under per-pixel weights (its own header, so its own table)
+WEIGHTED_LOSS_EXPORTS = {
+    "gsr_weight_total_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_weight_total": (C.c_int, [vp, C.c_int32, C.c_int32, vp, vp, C.c_size_t, vp]),
+    "gsr_weighted_l1_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, C.c_size_t, vp]),
+    "gsr_weighted_dssim_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_weighted_l1_dssim_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, vp]),
+}
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -232,7 +241,7 @@ def lib():
                                   + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
                                   + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
                                   + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
-                                  + list(DEBUG_LAYOUT_EXPORTS.items())):
+                                  + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -6,15 +6,93 @@ reference (loss.py:243), and those two functions keep the reference's behaviour.
 The standard 3DGS loss (1 - lambda) L1 + lambda (1 - SSIM) with its full pixel gradient is
 `l1_dssim_loss_and_gradients` (include/gsr_loss.h).
 """
+import numpy as np
 import torch
 
 from . import _host, _lib
 
+_WS = {}         # (kind, device, stream, W, H) -> workspace of a loss call (one per stream: views in flight on several streams)
 
-def l1_loss_and_gradients(rendered, target, lambda_dssim=0.0, want_grad=True, loss_out=None):
+
+def _workspace(kind, nbytes, dev, stream, W, H):
+    key = (kind, dev, stream, W, H)
+    ws = _WS.get(key)
+    if ws is None:
+        ws = _WS[key] = torch.empty(max(16, int(nbytes)), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def _weight_image(weights, what):
+    """A weight image as given: a torch tensor or numpy array, float32, (H, W) with H, W >= 1 -- judged before the GPU is touched."""
+    if not isinstance(weights, (torch.Tensor, np.ndarray)):
+        raise ValueError(f"{what} must be a torch tensor or a numpy array, not {type(weights).__name__}")
+    if weights.dtype not in (torch.float32, np.float32):
+        raise ValueError(f"{what} must be float32, not {weights.dtype}")
+    if weights.ndim != 2 or weights.shape[0] < 1 or weights.shape[1] < 1:
+        raise ValueError(f"{what} must have shape (H, W), not {tuple(weights.shape)}")
+    return weights
+
+
+def _weight_total(w):
+    """The device float M = sum of the (H, W) device tensor w (gsr_weight_total: fixed order, the same bits every call)."""
+    L = _lib.lib()
+    H, W = int(w.shape[0]), int(w.shape[1])
+    total = torch.empty(1, dtype=torch.float32, device=w.device)
+    with _host.on_device(w.device):
+        stream = _host.stream_ptr(w.device)
+        ws = _workspace("sum", L.gsr_weight_total_workspace_bytes(W, H), w.device, stream, W, H)
+        _lib.check(L.gsr_weight_total(_host.ptr(w), W, H, _host.ptr(total), _host.ptr(ws), ws.numel(), stream))
+    return total
+
+
+class PixelWeights:
+    """Per-pixel weights of the colour loss (include/gsr_weighted_loss.h): `.weights`, the (H, W) float32 device tensor, and
+    `.total`, their sum M as a 1-element device tensor, computed once here so that a loss call adds no launch for it.
+    Weights are >= 0 and finite (0 = the pixel does not count); nothing checks that.
+    dilate=r first takes the minimum over each (2r+1) x (2r+1) neighbourhood (clipped to the image), which grows the ignored
+    region by r pixels.  The SSIM term reaches 5 pixels, so a region is excluded bit for bit only by a mask grown by 5."""
+
+    def __init__(self, weights, dilate=0):
+        w = _weight_image(weights, "PixelWeights: weights")
+        if not (isinstance(dilate, int) and dilate >= 0):
+            raise ValueError(f"PixelWeights: dilate must be an integer >= 0, not {dilate!r}")
+        dev = _host.device_of(w)
+        w = _host.to_dev(w, torch.float32, dev)
+        if dilate:
+            w = (-torch.nn.functional.max_pool2d(-w[None, None], 2 * dilate + 1, stride=1, padding=dilate))[0, 0].contiguous()
+        self.weights, self.total = w, _weight_total(w)
+
+
+def _checked_weights(weights, rendered, target, who):
+    """The `weights` keyword before anything touches the GPU: a PixelWeights or a bare weight image whose shape is the images' and
+    which lies on their device."""
+    w = weights.weights if isinstance(weights, PixelWeights) else _weight_image(weights, f"{who}: weights")
+    hw = tuple(np.shape(rendered)[:2])
+    if tuple(w.shape) != hw:
+        raise ValueError(f"{who}: weights have shape {tuple(w.shape)} for a {hw} image")
+    for img in (rendered, target):
+        if isinstance(w, torch.Tensor) and w.is_cuda and isinstance(img, torch.Tensor) and img.is_cuda and img.device != w.device:
+            raise ValueError(f"{who}: weights on {w.device}, image on {img.device}")
+    return weights
+
+
+def _device_weights(weights, dev):
+    """(weight image, total) on `dev`; a bare image's total is computed here, in the call."""
+    if isinstance(weights, PixelWeights):
+        return weights.weights, weights.total
+    w = _host.to_dev(weights, torch.float32, dev)
+    return w, _weight_total(w)
+
+
+def l1_loss_and_gradients(rendered, target, lambda_dssim=0.0, want_grad=True, loss_out=None, weights=None):
     """One kernel: returns (loss_sum device tensor [1] = sum |rendered - target|, pixel_grad (H,W,3) or None).
     mean L1 = loss_sum / (H*W*3); pixel_grad = (1-lambda_dssim)/(H*W*3) * sign(rendered - target).
-    `loss_out`: a 1-element float32 device tensor (e.g. a slot of a trainer's loss curve) to receive the sum instead of a fresh one."""
+    `loss_out`: a 1-element float32 device tensor (e.g. a slot of a trainer's loss curve) to receive the sum instead of a fresh one.
+    `weights`: a PixelWeights, or a bare (H, W) float32 weight image m whose total M is computed in the call
+    (include/gsr_weighted_loss.h).  Then loss_sum = sum m |rendered - target|, mean L1 = loss_sum / (3 M) and
+    pixel_grad = (1-lambda_dssim)/(3 M) * m * sign(rendered - target); the sum is reduced in a fixed order."""
+    if weights is not None:
+        _checked_weights(weights, rendered, target, "l1_loss_and_gradients")
     L = _lib.lib()
     dev = _host.device_of(rendered, target)
     r = _host.to_dev(rendered, torch.float32, dev)
@@ -25,6 +103,14 @@ def l1_loss_and_gradients(rendered, target, lambda_dssim=0.0, want_grad=True, lo
     if loss_out is not None and not (isinstance(loss_out, torch.Tensor) and loss_out.is_cuda and loss_out.dtype == torch.float32 and loss_out.numel() == 1):
         raise ValueError("l1_loss_and_gradients: loss_out must be a 1-element float32 device tensor")
     loss_sum = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
+    if weights is not None:
+        m, total = _device_weights(weights, dev)
+        with _host.on_device(dev):
+            stream = _host.stream_ptr(dev)
+            ws = _workspace("sum", L.gsr_weight_total_workspace_bytes(W, H), dev, stream, W, H)
+            _lib.check(L.gsr_weighted_l1_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(total), _host.ptr(grad), _host.ptr(loss_sum),
+                                                   W, H, 1.0 - float(lambda_dssim), _host.ptr(ws), ws.numel(), stream))
+        return loss_sum, grad
     l1_weight = (1.0 - float(lambda_dssim)) / (H * W * 3.0)
     with _host.on_device(dev):
         _lib.check(L.gsr_l1_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(grad), _host.ptr(loss_sum), W, H, l1_weight,
@@ -44,22 +130,23 @@ def compute_image_gradients(rendered, target, lambda_dssim=0.2):
     return l1_loss_and_gradients(rendered, target, lambda_dssim)[1]
 
 
-_DSSIM_WS = {}   # (device, stream, W, H) -> workspace of gsr_l1_dssim_loss_grad (one per stream: views in flight on several streams)
-
-
 def _slot(t, name):
     if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
         raise ValueError(f"l1_dssim_loss_and_gradients: {name} must be a 1-element float32 device tensor")
     return t
 
 
-def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaussian", want_grad=True, loss_out=None, ssim_out=None):
+def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaussian", want_grad=True, loss_out=None, ssim_out=None,
+                                weights=None):
     """L = (1 - lambda) L1 + lambda (1 - SSIM) in one call (include/gsr_loss.h), with no host sync.
     Returns (l1_sum, ssim_sum, pixel_grad): device tensors [1] with l1_sum = sum |rendered - target| (mean L1 = l1_sum / (3HW))
     and ssim_sum = sum over pixels of the channel-mean SSIM (SSIM = ssim_sum / (HW)), and pixel_grad = dL/drendered (H, W, 3),
     or None without want_grad.  window: "gaussian" (centred sigma = 1.5, standard 3DGS) or "reference" (gsr_ssim's weights),
     both clipped to the image and renormalised at the border.  `loss_out` / `ssim_out`: 1-element float32 device tensors (e.g.
-    slots of a trainer's curves) that receive the sums instead of fresh ones."""
+    slots of a trainer's curves) that receive the sums instead of fresh ones.
+    `weights`: a PixelWeights, or a bare (H, W) float32 weight image m whose total M is computed in the call
+    (include/gsr_weighted_loss.h).  The same tuple comes back, of the weighted loss: l1_sum = sum m |rendered - target| (mean L1 =
+    l1_sum / (3 M)), ssim_sum = sum of m times the channel-mean SSIM (SSIM = ssim_sum / M)."""
     if window not in _lib.SSIM_WINDOWS:
         raise ValueError(f"window must be one of {sorted(_lib.SSIM_WINDOWS)}, not {window!r}")
     lam = float(lambda_dssim)
@@ -67,6 +154,8 @@ def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaus
         raise ValueError(f"lambda_dssim must be in [0, 1], not {lambda_dssim}")
     _slot(loss_out, "loss_out")
     _slot(ssim_out, "ssim_out")
+    if weights is not None:
+        _checked_weights(weights, rendered, target, "l1_dssim_loss_and_gradients")
     L = _lib.lib()
     dev = _host.device_of(rendered, target)
     r = _host.to_dev(rendered, torch.float32, dev)
@@ -76,12 +165,18 @@ def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaus
     grad = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_grad else None
     l1_sum = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
     ssim_sum = torch.empty(1, dtype=torch.float32, device=dev) if ssim_out is None else ssim_out
+    if weights is not None:
+        m, total = _device_weights(weights, dev)
+        with _host.on_device(dev):
+            stream = _host.stream_ptr(dev)
+            ws = _workspace("weighted_dssim", L.gsr_weighted_dssim_workspace_bytes(W, H), dev, stream, W, H)
+            _lib.check(L.gsr_weighted_l1_dssim_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(total), _host.ptr(grad),
+                                                         _host.ptr(l1_sum), _host.ptr(ssim_sum), W, H, lam, _lib.SSIM_WINDOWS[window],
+                                                         _host.ptr(ws), ws.numel(), stream))
+        return l1_sum, ssim_sum, grad
     with _host.on_device(dev):
         stream = _host.stream_ptr(dev)
-        key = (dev, stream, W, H)
-        ws = _DSSIM_WS.get(key)
-        if ws is None:
-            ws = _DSSIM_WS[key] = torch.empty(max(16, int(L.gsr_dssim_workspace_bytes(W, H))), dtype=torch.uint8, device=dev)
+        ws = _workspace("dssim", L.gsr_dssim_workspace_bytes(W, H), dev, stream, W, H)
         _lib.check(L.gsr_l1_dssim_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(grad), _host.ptr(l1_sum), _host.ptr(ssim_sum), W, H,
                                             lam, _lib.SSIM_WINDOWS[window], _host.ptr(ws), ws.numel(), stream))
     return l1_sum, ssim_sum, grad

@@ -39,6 +39,15 @@ view (12 numbers, c' = c A + b) and trains it with Adam (--exposure-lr-init -> -
 the corrected render, and the step stays free of host waits.  --exposure-noise S (seed --exposure-seed) perturbs every training target
 once at load, for experiments.  Training views are then scored through their learned E_v, held-out views with the identity; the
 matrices go to the summary and to exposure.json beside each PLY.  One GPU only, and not with --capacity.
+
+Per-pixel loss weights (include/gsr_weighted_loss.h, loss.PixelWeights): --mask-dir DIR reads <DIR>/<basename of file_path>.png
+per training view, first channel / 255 = the weight of that pixel in the colour loss (0 = ignore: a passer-by, a shadow, sky), for
+L1 alone and with --lambda-dssim, also under --optimize-exposure.  --mask-dilate R (default 5, the SSIM window's radius) first grows
+the ignored region by R pixels: only then is what it covers invisible to the SSIM term too.  The loss curve is normalised per view
+by 3 M_v, M_v the view's weight total; the summary adds the weighted L1 / PSNR / SSIM beside the plain ones.  For experiments,
+--occluders K (--occluder-seed, --occluder-size F) pastes K opaque saturated rectangles of side up to F of the image's into every
+training target at load, elsewhere in every view; --mask-occluders trains with the masks of exactly those rectangles, dilated, and
+the summary then also scores every view against the clean targets (clean_psnr_mean, clean_ssim_mean, clean_l1_mean).
 """
 import argparse
 import importlib
@@ -104,6 +113,46 @@ def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
     return out
 
 
+def load_masks(path, mask_dir, max_views, shapes, split="train"):
+    """The weight images of --mask-dir: <mask_dir>/<basename of file_path>.png per frame, first channel / 255, (H, W) float32; its
+    shape must be its image's."""
+    from PIL import Image
+    with open(os.path.join(path, f"transforms_{split}.json")) as f:
+        tf = json.load(f)
+    masks = []
+    for fr, shape in zip(tf["frames"][:max_views], shapes):
+        png = np.asarray(Image.open(os.path.join(mask_dir, os.path.basename(fr["file_path"]) + ".png")))
+        m = (png if png.ndim == 2 else png[:, :, 0]).astype(np.float32) / 255.0
+        if m.shape != tuple(shape):
+            raise ValueError(f"{fr['file_path']}: mask {m.shape} for a {tuple(shape)} image")
+        masks.append(np.ascontiguousarray(m))
+    return masks
+
+
+def occluder_rects(H, W, count, size, seed, view):
+    """--occluders: `count` rectangles (y0, y1, x0, x1, rgb) for one view -- sides between 0.3 and 1 times `size` of the image's
+    side, anywhere inside the image, a saturated colour each (one channel 1, one 0, one random); seeded by (seed, view)."""
+    rng = np.random.default_rng([seed, view])
+    rects = []
+    for _ in range(count):
+        h, w = (max(1, int(rng.uniform(0.3, 1.0) * size * n)) for n in (H, W))
+        y0, x0 = int(rng.integers(0, H - h + 1)), int(rng.integers(0, W - w + 1))
+        rgb = np.zeros(3, np.float32)
+        hi, lo, mid = rng.permutation(3)
+        rgb[hi], rgb[mid] = 1.0, rng.random()
+        rects.append((y0, y0 + h, x0, x0 + w, rgb))
+    return rects
+
+
+def paste_occluders(target, rects):
+    """(the (H, W, 3) numpy target with the rectangles pasted, their mask: 0 on a rectangle, 1 elsewhere)"""
+    out, mask = target.copy(), np.ones(target.shape[:2], np.float32)
+    for y0, y1, x0, x1, rgb in rects:
+        out[y0:y1, x0:x1] = rgb
+        mask[y0:y1, x0:x1] = 0.0
+    return out, mask
+
+
 MODE_KW = {}     # --rasterize-mode antialiased: {"rasterize_mode": "antialiased"} for every render and backward of the run;
                  # --filter-3d: also {"filter_3d": the current filter}, replaced at every recomputation
 
@@ -156,6 +205,16 @@ def score_views(P, cams, targets, bg, exposure=None):
     return rows, images
 
 
+def weighted_scores(img, t, w):
+    """score_views' three numbers under a PixelWeights w: sum m |d| / (3 M), PSNR of sum m d^2 / (3 M), and ssim_sum / M"""
+    M = float(w.total.item())
+    l1_sum, ssim_sum, _ = gsr.loss.l1_dssim_loss_and_gradients(img, t, 0.0, window="gaussian", want_grad=False, weights=w)
+    d = img - t
+    mse = float((w.weights[..., None] * d * d).sum().item()) / (3.0 * M)
+    return {"l1": float(l1_sum.item()) / (3.0 * M), "psnr": (10.0 * np.log10(1.0 / mse)) if mse > 0 else float("inf"),
+            "ssim": float(ssim_sum.item()) / M}
+
+
 def aux_scores(P, cams, depth_targets, alpha_targets, bg):
     """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets."""
     dl, al = [], []
@@ -174,7 +233,7 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg):
 
 
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
-           alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None):
+           alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None, weights=None, clean_targets=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -186,6 +245,15 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
                "train_psnr_mean": float(np.mean([r["psnr"] for r in rows])), "train_ssim_mean": float(np.mean([r["ssim"] for r in rows]))}
     if args.capacity:
         summary["capacity_retries"] = len(capacity_log)
+    if weights is not None:                                                 # the same three scores under each view's weights
+        wrows = [weighted_scores(img, t.reshape(img.shape), w) for img, t, w in zip(images, targets, weights)]
+        summary.update({"train_views_weighted": wrows, "train_weighted_l1_mean": float(np.mean([r["l1"] for r in wrows])),
+                        "train_weighted_psnr_mean": float(np.mean([r["psnr"] for r in wrows])),
+                        "train_weighted_ssim_mean": float(np.mean([r["ssim"] for r in wrows]))})
+    if clean_targets is not None:                                           # --occluders: against the targets before the rectangles
+        crows, _ = score_views(P, cams, clean_targets, bg, exposure)
+        summary.update({"clean_views": crows, "clean_l1_mean": float(np.mean([r["l1"] for r in crows])),
+                        "clean_psnr_mean": float(np.mean([r["psnr"] for r in crows])), "clean_ssim_mean": float(np.mean([r["ssim"] for r in crows]))})
     if poses is not None:                                                   # --pose-noise-* / --optimize-poses: error vs the dataset poses
         summary.update(poses)
     if exposure is not None:                                                # --optimize-exposure: which rows went through a matrix, and the matrices
@@ -331,7 +399,24 @@ def main():
                     "clamp(t A_v + b_v, 0, 1): A_v = diag(exp(u_v + w_v)), u_v ~ N(0, S^2) per channel, w_v ~ N(0, S^2) shared, "
                     "b_v ~ N(0, (S/4)^2) per channel (exposure.random_exposures)")
     ap.add_argument("--exposure-seed", type=int, default=0, help="seed of the exposure perturbation")
+    ap.add_argument("--mask-dir", default=None, help="with --dataset: per-pixel weights of the colour loss (include/gsr_weighted_loss.h), "
+                    "<DIR>/<basename of file_path>.png per training view, first channel / 255 (0 = the pixel does not count); the shape "
+                    "must be the image's")
+    ap.add_argument("--mask-dilate", type=int, default=5, metavar="R", help="grow the ignored region of every mask by R pixels first "
+                    "(the minimum over each (2R+1)^2 neighbourhood).  5 is the SSIM window's radius: what the grown mask covers is then "
+                    "invisible to the D-SSIM term too")
+    ap.add_argument("--occluders", type=int, default=0, metavar="K", help="paste K opaque rectangles of a random saturated colour into "
+                    "every training target once, at load, elsewhere in every view; the summary also scores against the clean targets")
+    ap.add_argument("--occluder-seed", type=int, default=0, help="seed of the rectangles")
+    ap.add_argument("--occluder-size", type=float, default=0.25, metavar="F", help="largest side of a rectangle, as a fraction of the image's")
+    ap.add_argument("--mask-occluders", action="store_true", help="train with the masks of exactly those rectangles (dilated by --mask-dilate)")
     args = ap.parse_args()
+    if args.mask_dilate < 0 or args.occluders < 0 or not 0.0 < args.occluder_size <= 1.0:
+        raise SystemExit("--mask-dilate and --occluders must be >= 0, --occluder-size in (0, 1]")
+    if args.mask_dir and not args.dataset:
+        raise SystemExit("--mask-dir needs --dataset (the masks are named after its frames)")
+    if args.mask_occluders and args.occluders == 0:
+        raise SystemExit("--mask-occluders needs --occluders K")
     if not (args.exposure_lr_init > 0.0 and args.exposure_lr_final > 0.0 and np.isfinite(args.exposure_lr_init + args.exposure_lr_final)):
         raise SystemExit("--exposure-lr-init and --exposure-lr-final must be positive and finite")
     if not (args.exposure_noise >= 0.0 and np.isfinite(args.exposure_noise)):
@@ -400,6 +485,30 @@ def main():
     if args.exposure_noise > 0.0:                                            # every target as a camera with that exposure error stored it
         noise = gsr.exposure.random_exposures(len(targets), args.exposure_noise, args.exposure_seed)
         targets = [gsr.exposure.perturbed_target(t.reshape(c["height"], c["width"], 3), e) for t, c, e in zip(targets, cams, noise)]
+    masks = None                                                            # per view: the (H, W) weights as given, on the host
+    if args.mask_dir:
+        try:
+            masks = load_masks(args.dataset, args.mask_dir, args.views, [(c["height"], c["width"]) for c in cams])
+        except (ValueError, OSError) as e:
+            raise SystemExit(f"--mask-dir: {e}") from None
+    clean_targets = None
+    if args.occluders > 0:                                                  # every target as a capture with things in the way stored it
+        clean_targets, pasted = targets, []
+        if args.mask_occluders and masks is None:
+            masks = [np.ones((c["height"], c["width"]), np.float32) for c in cams]
+        for v, (t, c) in enumerate(zip(targets, cams)):
+            rects = occluder_rects(c["height"], c["width"], args.occluders, args.occluder_size, args.occluder_seed, v)
+            img, hole = paste_occluders(t.reshape(c["height"], c["width"], 3).cpu().numpy(), rects)
+            pasted.append(torch.as_tensor(img).to(dev))
+            if args.mask_occluders:
+                masks[v] = masks[v] * hole
+        targets = pasted
+    pix_w = None                                                            # per view: loss.PixelWeights (the grown mask and its total M_v)
+    if masks is not None:
+        pix_w = [gsr.loss.PixelWeights(torch.as_tensor(m).to(dev), dilate=args.mask_dilate) for m in masks]
+        w_total = [float(p.total.item()) for p in pix_w]
+        if min(w_total) <= 0.0:
+            raise SystemExit(f"the mask of view {int(np.argmin(w_total))} leaves no pixel with weight (after --mask-dilate {args.mask_dilate})")
     expo = gsr.exposure.ExposureModel(len(cams), dev) if args.optimize_exposure else None
     # --pose-noise-*: the poses the trainer starts from; the dataset's stay in true_cams for the pose error (the targets are the
     # dataset's images, or renders of the hidden scene from the dataset poses)
@@ -438,6 +547,7 @@ def main():
     ssim_of = {}                                                            # (several views per rank: each view's mean SSIM)
     per_rank_views = -(-args.views_per_step // world)
     sum_scale = float(cams[0]["height"] * cams[0]["width"] * 3)             # an L1 sum -> mean (all views of a dataset share one size)
+    view_of = []                                                            # with weights the scale is the view's: 3 M_v (one view per rank and step)
     streams_few, streams_many = gsr.dist.ViewStreams(1, dev), gsr.dist.ViewStreams(min(per_rank_views, args.view_streams or 3), dev)
     density_log = [{"iteration": -1, "points": model.num_points}]
     # --capacity: K (None = render sized), the point count K was last confirmed for, the largest D seen, and each view's last D (its
@@ -497,13 +607,16 @@ def main():
                 raw = img.reshape(c["height"], c["width"], 3)
                 img = gsr.exposure.apply_exposure(raw, expo.matrix(v))
             # (one view per rank and step: the L1 sum goes straight into this iteration's slot of the loss curve)
+            w_v = pix_w[v] if pix_w is not None else None                   # the colour loss under this view's weights (None: today's call)
+            mean_of = (3.0 * w_v.total) if w_v is not None else (c["height"] * c["width"] * 3)   # an L1 sum -> this view's mean
             if dssim:                                                       # ... and the SSIM sum into the SSIM curve's
                 loss_sum, ssim_sum, dpix = gsr.loss.l1_dssim_loss_and_gradients(
                     img, targets[v], args.lambda_dssim, args.ssim_window, loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None,
-                    ssim_out=ssim_hist[it:it + 1] if len(mine) == 1 else None)
-                ssim_of[v] = ssim_sum / (c["height"] * c["width"])          # (a re-run of an overflowed view replaces its entry)
+                    ssim_out=ssim_hist[it:it + 1] if len(mine) == 1 else None, weights=w_v)
+                ssim_of[v] = ssim_sum / (mean_of / 3.0)                     # (a re-run of an overflowed view replaces its entry)
             else:
-                loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None)
+                loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None,
+                                                                weights=w_v)
             aux_kw = {}
             if args.lambda_depth > 0.0:                                     # (the curve keeps the colour loss: the terms are in the summary)
                 aux_kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
@@ -531,8 +644,8 @@ def main():
                 gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
                 pose_step(v, gsr.pose.pose_gradient(start_cams[v], pose_xi[v], gv.view(4, 4), gp.view(4, 4), gc))
             if capacity is not None:
-                return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"], buf
-            return (loss_sum if len(mine) == 1 else loss_sum / (c["height"] * c["width"] * 3)), g["_arena"], g["_view_payload"]
+                return (loss_sum if len(mine) == 1 else loss_sum / mean_of), g["_arena"], g["_view_payload"], buf
+            return (loss_sum if len(mine) == 1 else loss_sum / mean_of), g["_arena"], g["_view_payload"]
 
         def capacity_views():
             """--capacity: every view enqueued without a wait for D; then, with the backward enqueued and before Adam, each view's count
@@ -605,7 +718,7 @@ def main():
             if dssim:
                 ssim_hist[it] = sum(ssim_of[v] for v in mine)[0] / len(mine)
         elif len(mine) == 1:
-            pass                                                            # written by the loss kernel as a SUM: scaled once, at the end
+            view_of.append(mine[0])                                         # written by the loss kernel as a SUM: scaled once, at the end
         if (screen_stats and world > 1 and it > args.densify_from and it < args.densify_until and it % args.densify_interval == 0):
             gsr.dist.reduce_densify_stats(model.stats, world)               # once per density-control call: every rank marks the same rows
         log = model.densification_and_pruning(it)                           # train.py:1060
@@ -632,17 +745,21 @@ def main():
         if rank == 0 and (it % args.print_interval == 0 or it == args.iterations - 1):
             if dssim:                                                       # the combined loss (one read of both slots)
                 l1_v, ssim_v = torch.stack([loss_hist[it], ssim_hist[it]]).tolist()
-                l1_v, ssim_v = (l1_v / sum_scale, ssim_v * 3.0 / sum_scale) if len(mine) == 1 else (l1_v, ssim_v)
+                scale = 3.0 * w_total[mine[0]] if pix_w is not None and len(mine) == 1 else sum_scale
+                l1_v, ssim_v = (l1_v / scale, ssim_v * 3.0 / scale) if len(mine) == 1 else (l1_v, ssim_v)
                 shown = (1.0 - args.lambda_dssim) * l1_v + args.lambda_dssim * (1.0 - ssim_v)
             else:
-                shown = float(loss_hist[it].item()) / (sum_scale if len(mine) == 1 else 1.0)
+                shown = float(loss_hist[it].item()) / ((3.0 * w_total[mine[0]] if pix_w is not None else sum_scale) if len(mine) == 1 else 1.0)
             print(f"iter {it:5d}  loss {shown:.6f}", flush=True)
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t_start
     if per_rank_views == 1:
-        loss_hist /= sum_scale                                              # slots hold sums of |difference|: one division for the whole curve
+        scale = sum_scale                                                   # slots hold sums of |difference|: one division for the whole curve
+        if pix_w is not None and len(view_of) == loss_hist.numel():         # ... weighted sums: each iteration by its view's 3 M_v
+            scale = 3.0 * torch.tensor(w_total, device=dev)[torch.tensor(view_of, device=dev)]
+        loss_hist /= scale
         if dssim:
-            ssim_hist /= sum_scale / 3.0                                    # ... and sums of per-pixel SSIM
+            ssim_hist /= scale / 3.0                                        # ... and sums of per-pixel SSIM
     if rank == 0:
         poses = None
         if true_cams is not start_cams or args.optimize_poses:
@@ -653,7 +770,7 @@ def main():
                      "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses, filter_log, eval_scales, expo)
+               poses, filter_log, eval_scales, expo, pix_w, clean_targets)
 
 
 if __name__ == "__main__":
