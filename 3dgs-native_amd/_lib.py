@@ -208,6 +208,18 @@ WEIGHTED_LOSS_EXPORTS = {
     "gsr_weighted_l1_dssim_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_int32, vp, C.c_size_t, vp]),
 }
 
+# include/gsr_depth_corr.h: the Pearson-correlation depth loss, 1 - rho(rendered inverse depth, target), for depth priors known up to
+# a scale and a shift per image (its own header, so its own table)
+DEPTH_CORR_EXPORTS = {
+    "gsr_depth_corr_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_depth_corr_loss_grad": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, C.c_size_t, vp]),
+}
+DEPTH_CORR_FIT_FLOATS = 4           # GSR_DEPTH_CORR_FIT_FLOATS: (rho, s, b, M)
+DEPTH_CORR_BLOCK_PIXELS = 1024      # GSR_DEPTH_CORR_BLOCK_PIXELS
+DEPTH_CORR_MAX_BLOCKS = 1024        # GSR_DEPTH_CORR_MAX_BLOCKS
+DEPTH_CORR_RECORD_BYTES = 64        # GSR_DEPTH_CORR_RECORD_BYTES
+DEPTH_CORR_MIN_REL_VAR = 1e-12      # GSR_DEPTH_CORR_MIN_REL_VAR
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -241,7 +253,8 @@ def lib():
                                   + list(AUX_EXPORTS.items()) + list(CAMERA_EXPORTS.items())
                                   + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
                                   + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
-                                  + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())):
+                                  + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
+                                  + list(DEPTH_CORR_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -247,3 +247,55 @@ def alpha_loss_and_gradients(final_Ts, target_alpha, mask=None, weight=1.0, want
     depth_loss_and_gradients (normalised by W H).  final_Ts is the forward's img_buffer["final_Ts"]; the gradient goes to
     backward(dL_dalpha_image=...)."""
     return _aux_l1("gsr_alpha_loss_grad", final_Ts, target_alpha, mask, weight, want_grad, loss_out)
+
+
+def _depth_image(x, what, hw=None):
+    """An inverse-depth image, target or weight image as given: (H, W) or (H, W, 1) with H, W >= 1, of the shape `hw` when that is
+    known -- judged before the GPU is touched.  Returns (H, W)."""
+    shape = tuple(np.shape(x))
+    if len(shape) == 3 and shape[2] == 1:
+        shape = shape[:2]
+    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
+        raise ValueError(f"depth_corr_loss_and_gradients: {what} must have shape (H, W), not {tuple(np.shape(x))}")
+    if hw is not None and shape != hw:
+        raise ValueError(f"depth_corr_loss_and_gradients: {what} has shape {shape} for a {hw} render")
+    return shape
+
+
+def depth_corr_loss_and_gradients(rendered, target, mask=None, weight=1.0, want_grad=True, loss_out=None, fit_out=None):
+    """1 - Pearson correlation between the rendered inverse depth and a relative depth target, with its exact gradient, three
+    launches, no host sync (include/gsr_depth_corr.h).  A relative target is one known only up to t -> a t + b per image (a > 0), as
+    a monocular depth network gives it: the loss and the gradient do not change under that map.
+    Returns (loss, grad, fit): loss a device tensor [1] = 1 - rho, rho the correlation under the weights `mask` (None: all ones);
+    grad (H, W) = weight * dloss/drendered, or None without want_grad; fit a device tensor [4] = (rho, s, b, M) with
+    rendered ~ s * target + b in the least-squares sense and M the weight total.  A frame without variance (M = 0, a constant
+    render or target) gives loss 1, a zero gradient and fit (0, 0, 0, M).  The loss is O(1) whatever the image size: there is no
+    1 / (W H) in `weight`.  `loss_out`: a 1-element float32 device tensor that receives the loss instead of a fresh one; `fit_out`:
+    the same for the 4 floats of the fit (a row of a (V, 4) tensor).  The gradient goes to backward(dL_ddepth_image=...)."""
+    hw = _depth_image(rendered, "rendered")
+    _depth_image(target, "target", hw)
+    if mask is not None:
+        _depth_image(mask, "mask", hw)
+    weight = float(weight)
+    if not np.isfinite(weight):
+        raise ValueError(f"depth_corr_loss_and_gradients: weight must be finite, not {weight}")
+    _slot(loss_out, "loss_out")
+    if fit_out is not None and not (isinstance(fit_out, torch.Tensor) and fit_out.is_cuda and fit_out.dtype == torch.float32
+                                    and fit_out.numel() == _lib.DEPTH_CORR_FIT_FLOATS and fit_out.is_contiguous()):
+        raise ValueError("depth_corr_loss_and_gradients: fit_out must be a contiguous 4-element float32 device tensor")
+    L = _lib.lib()
+    dev = _host.device_of(rendered, target, mask)
+    H, W = hw
+    r = _host.to_dev(rendered, torch.float32, dev, (H, W))
+    t = _host.to_dev(target, torch.float32, dev, (H, W))
+    m = _host.to_dev(mask, torch.float32, dev, (H, W)) if mask is not None else None
+    grad = torch.empty((H, W), dtype=torch.float32, device=dev) if want_grad else None
+    loss = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
+    fit = torch.empty(_lib.DEPTH_CORR_FIT_FLOATS, dtype=torch.float32, device=dev) if fit_out is None else fit_out
+    with _host.on_device(dev):
+        stream = _host.stream_ptr(dev)
+        ws = _workspace("depth_corr", L.gsr_depth_corr_workspace_bytes(W, H), dev, stream, W, H)
+        _lib.check(L.gsr_depth_corr_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(grad), _host.ptr(loss), _host.ptr(fit), W, H,
+                                              weight, _host.ptr(ws), ws.numel(), stream))
+    _host.written_in_place(loss_out, fit_out)
+    return loss, grad, fit

@@ -16,7 +16,13 @@ train.py:323-334) is used; without it, targets are renders of a hidden seeded sc
 Depth and alpha supervision (include/gsr_aux_grads.h): --lambda-depth adds lambda_d times the masked L1 of the rendered inverse
 depth (targets: --depth-dir with --dataset, one float32 (H, W) .npy per frame named after its file_path; else the hidden scene's own
 inverse depth; mask = target > 0), --lambda-alpha lambda_a times the L1 of the alpha image 1 - final_T (targets: the PNG alpha,
-or the hidden scene's).  Both terms are normalised by W H, as the reference's depth_loss.
+or the hidden scene's).  Both terms are normalised by W H, as the reference's depth_loss.  That L1 needs targets in the scene's own
+units.  --depth-loss pearson (include/gsr_depth_corr.h) is for relative targets instead -- inverse depth known only up to an unknown
+scale a > 0 and shift b per image, t -> a t + b, as a monocular depth network gives it: the depth term is then lambda_d times
+1 - the Pearson correlation of the rendered inverse depth with the target over the same mask, which no such a and b change (it is
+O(1) already: no W H).  For experiments, --depth-noise S (seed --depth-seed) stores every view's depth target as a_v t + b_v on its
+masked pixels, a_v = exp(U(-S, S)), b_v = U(0, S) times the view's mean target; the summary then scores the depth against the
+clean targets too (train_depth_l1_clean_mean), and always reports the mean correlation and each view's fitted (s, b).
 
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
@@ -215,9 +221,26 @@ def weighted_scores(img, t, w):
             "ssim": float(ssim_sum.item()) / M}
 
 
-def aux_scores(P, cams, depth_targets, alpha_targets, bg):
-    """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets."""
-    dl, al = [], []
+def perturb_depth_targets(depth_targets, noise, seed):
+    """--depth-noise S: every view's target as a relative depth source would store it, a_v t + b_v on the masked pixels (t > 0, taken
+    from the clean target: a_v > 0 and b_v >= 0 keep it) with a_v = exp(U(-S, S)) and b_v = U(0, S) * mean(t over the mask)."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for t in depth_targets:
+        a, u = float(np.exp(rng.uniform(-noise, noise))), float(rng.uniform(0.0, noise))
+        mask = t > 0
+        b = u * float(t[mask].mean().item()) if bool(mask.any().item()) else 0.0
+        out.append(torch.where(mask, a * t + b, t).contiguous())
+    return out
+
+
+def aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets=None):
+    """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets.
+    Third: with depth targets, {"train_depth_corr_mean": the mean Pearson correlation rho of the rendered inverse depth with the
+    targets as given, "train_depth_fit": each view's (s, b) of render ~ s target + b (include/gsr_depth_corr.h)}, and with
+    clean_depth_targets (--depth-noise) "train_depth_l1_clean_mean", the first score against the unperturbed targets."""
+    dl, al, dc = [], [], []
+    fits = torch.zeros((len(cams), 4), device=P["positions"].device) if depth_targets is not None else None
     for k, c in enumerate(cams):
         _, dep, buf = gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
                                            rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
@@ -226,14 +249,25 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg):
         if depth_targets is not None:
             t = depth_targets[k]
             dl.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
+            gsr.loss.depth_corr_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False, fit_out=fits[k])
+            if clean_depth_targets is not None:
+                t = clean_depth_targets[k]
+                dc.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
         if alpha_targets is not None:
             t = alpha_targets[k]
             al.append(float(gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], t, want_grad=False)[0].item()) / t.numel())
-    return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None)
+    extra = {}
+    if fits is not None:
+        f = fits.cpu().numpy().astype(np.float64)
+        extra = {"train_depth_corr_mean": float(f[:, 0].mean()), "train_depth_fit": [[float(s), float(b)] for s, b in f[:, 1:3]]}
+        if dc:
+            extra["train_depth_l1_clean_mean"] = float(np.mean(dc))
+    return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None), extra
 
 
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
-           alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None, weights=None, clean_targets=None):
+           alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None, weights=None, clean_targets=None,
+           clean_depth_targets=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -260,9 +294,10 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
         summary["exposure_applied"] = {"train_views": True, "train_eval_scales": True, "holdout_views": False, "holdout_eval_scales": False}
         summary["exposure_final"] = exposure.state_dict()["E"]
         summary["exposure_steps"] = list(exposure.steps)
-    d_l1, a_l1 = aux_scores(P, cams, depth_targets, alpha_targets, bg)
+    d_l1, a_l1, d_extra = aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets)
     if d_l1 is not None:
         summary["train_depth_l1_mean"] = d_l1
+    summary.update(d_extra)
     if a_l1 is not None:
         summary["train_alpha_l1_mean"] = a_l1
     if args.holdout and args.dataset:
@@ -354,7 +389,16 @@ def main():
                     "standard 3DGS uses 0.2).  0 = L1 alone, the reference trainer's loss")
     ap.add_argument("--ssim-window", default="gaussian", choices=["gaussian", "reference"], help="SSIM window of the D-SSIM term: the "
                     "centred sigma = 1.5 Gaussian of standard 3DGS, or the reference's distance-indexed weights (gsr_ssim)")
-    ap.add_argument("--lambda-depth", type=float, default=0.0, help="weight of the masked inverse-depth L1 (include/gsr_aux_grads.h)")
+    ap.add_argument("--lambda-depth", type=float, default=0.0, help="weight of the depth term: the masked inverse-depth L1 "
+                    "(include/gsr_aux_grads.h), or what --depth-loss selects")
+    ap.add_argument("--depth-loss", default="l1", choices=["l1", "pearson"], help="l1: the masked L1 against inverse depth in the scene's "
+                    "own units.  pearson: 1 - the Pearson correlation of the rendered inverse depth with the target over the mask "
+                    "(include/gsr_depth_corr.h), for relative targets: inverse depth known only up to an unknown scale a > 0 and shift b "
+                    "per image (t -> a t + b), as monocular depth networks give it.  Needs --lambda-depth > 0; not divided by W H")
+    ap.add_argument("--depth-noise", type=float, default=0.0, metavar="S", help="make every depth target relative once, at load: "
+                    "a_v t + b_v on its masked pixels, a_v = exp(U(-S, S)), b_v = U(0, S) * mean(t over the mask) per view; the summary "
+                    "then also scores the depth against the clean targets (train_depth_l1_clean_mean)")
+    ap.add_argument("--depth-seed", type=int, default=0, help="seed of the depth perturbation")
     ap.add_argument("--depth-dir", default=None, help="with --dataset: one float32 (H, W) inverse-depth .npy per frame, named after its "
                     "file_path (without --dataset the hidden scene's own inverse depth is the target)")
     ap.add_argument("--lambda-alpha", type=float, default=0.0, help="weight of the L1 of the alpha image 1 - final_T against the PNG "
@@ -437,6 +481,12 @@ def main():
         raise SystemExit("--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0")
     if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
         raise SystemExit("--lambda-depth and --lambda-alpha must be >= 0")
+    if args.depth_loss == "pearson" and not args.lambda_depth > 0.0:
+        raise SystemExit("--depth-loss pearson needs --lambda-depth > 0 (its weight)")
+    if not (args.depth_noise >= 0.0 and np.isfinite(args.depth_noise)):
+        raise SystemExit("--depth-noise must be >= 0 and finite")
+    if args.depth_noise > 0.0 and args.dataset and not args.depth_dir:
+        raise SystemExit("--depth-noise with --dataset needs --depth-dir (there is no depth target to perturb)")
     if args.lambda_depth > 0.0 and args.dataset and not args.depth_dir:
         raise SystemExit("--lambda-depth with --dataset needs --depth-dir (inverse-depth targets)")
     if not 0.0 <= args.lambda_dssim <= 1.0:
@@ -519,7 +569,10 @@ def main():
     start_cams = cams
     pose_xi = [np.zeros(6) for _ in cams]                                    # --optimize-poses: each view's correction, its Adam state
     pose_m, pose_v, pose_t = [np.zeros(6) for _ in cams], [np.zeros(6) for _ in cams], [0] * len(cams)
-    depth_masks = [(t > 0).float() for t in depth_targets] if depth_targets is not None else None
+    depth_masks = [(t > 0).float() for t in depth_targets] if depth_targets is not None else None   # (from the clean targets)
+    clean_depth_targets = None
+    if args.depth_noise > 0.0:                                              # every depth target as a relative depth source stored it
+        clean_depth_targets, depth_targets = depth_targets, perturb_depth_targets(depth_targets, args.depth_noise, args.depth_seed)
     aux = args.lambda_depth > 0.0 or args.lambda_alpha > 0.0
 
     n = args.gaussians
@@ -618,7 +671,9 @@ def main():
                 loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None,
                                                                 weights=w_v)
             aux_kw = {}
-            if args.lambda_depth > 0.0:                                     # (the curve keeps the colour loss: the terms are in the summary)
+            if args.lambda_depth > 0.0 and args.depth_loss == "pearson":    # lambda_d (1 - rho): blind to the target's scale and shift
+                aux_kw["dL_ddepth_image"] = gsr.loss.depth_corr_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
+            elif args.lambda_depth > 0.0:                                   # (the curve keeps the colour loss: the terms are in the summary)
                 aux_kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
             if args.lambda_alpha > 0.0:
                 aux_kw["dL_dalpha_image"] = gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], alpha_targets[v], None, args.lambda_alpha)[1]
@@ -770,7 +825,7 @@ def main():
                      "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses, filter_log, eval_scales, expo, pix_w, clean_targets)
+               poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets)
 
 
 if __name__ == "__main__":
