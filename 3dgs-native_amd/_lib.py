@@ -220,6 +220,16 @@ DEPTH_CORR_MAX_BLOCKS = 1024        # GSR_DEPTH_CORR_MAX_BLOCKS
 DEPTH_CORR_RECORD_BYTES = 64        # GSR_DEPTH_CORR_RECORD_BYTES
 DEPTH_CORR_MIN_REL_VAR = 1e-12      # GSR_DEPTH_CORR_MIN_REL_VAR
 
+# include/gsr_knn.h: exact 3-nearest-neighbour distances of a point cloud, the start of a run from SfM or random points (its own
+# header, so its own table)
+KNN_EXPORTS = {
+    "gsr_knn_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_knn": (C.c_int, [C.c_int64, vp, vp, vp, vp, C.c_size_t, vp]),
+}
+KNN_K = 3                           # GSR_KNN_K
+KNN_BLOCK_POINTS = 256              # GSR_KNN_BLOCK_POINTS
+KNN_MAX_POINTS = 1 << 27            # GSR_KNN_MAX_POINTS
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -254,7 +264,7 @@ def lib():
                                   + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
                                   + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
                                   + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
-                                  + list(DEPTH_CORR_EXPORTS.items())):
+                                  + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -5,6 +5,10 @@ called from train.py:796-803.  Same vertex layout, field names and byte order as
 f_dc_0..2, f_rest_0..44.  Host I/O only -- the arrays are copied off the device once and packed with numpy, there is
 no per-vertex Python loop.  `load_ply` reads such a file back (the reference has no reader; this one exists for
 round-trip tests and for resuming from a checkpoint).
+
+`load_points` reads a plain point cloud (x y z and optional uchar colours: what COLMAP and every point-cloud tool write), and
+`gaussians_from_points` turns one into the trainer's five arrays with the original's start: isotropic scales from the three nearest
+neighbours (knn.init_scales), opacity 0.1, the colour in the SH DC term.
 """
 import os
 
@@ -114,3 +118,100 @@ def load_ply(filepath):
     return {"positions": np.stack([v["x"], v["y"], v["z"]], axis=1), "scales": np.stack([v["scale_0"], v["scale_1"], v["scale_2"]], axis=1),
             "rotations": np.stack([v["rot_x"], v["rot_y"], v["rot_z"], v["rot_w"]], axis=1), "opacities": np.array(v["opacity"]),
             "shs": shs.reshape(n * 16, 3), "colors": np.stack([v["red"], v["green"], v["blue"]], axis=1)}
+
+
+SH_C0 = 0.28209479177387814
+_PLY_SCALARS = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "<i2", "int16": "<i2", "ushort": "<u2", "uint16": "<u2",
+                "int": "<i4", "int32": "<i4", "uint": "<u4", "uint32": "<u4", "float": "<f4", "float32": "<f4", "double": "<f8", "float64": "<f8"}
+
+
+def load_points(filepath):
+    """A binary little-endian PLY point cloud: (xyz float32 (N, 3), rgb float32 (N, 3) in [0, 1] or None).  The vertex element needs
+    x, y, z; uchar red, green, blue are the colours when all three are there; every other scalar property is skipped by its declared
+    size.  Elements behind the vertices (faces) are not read.  ASCII files, list properties in the vertex element and truncated
+    files are refused with ValueError."""
+    with open(filepath, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("not a PLY file")
+        n, fields, fmt, element = None, [], None, None
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("PLY header not terminated")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                element = tok[1]
+                if element == "vertex":
+                    if n is not None or fields:
+                        raise ValueError("the vertex element must be the first element of the file, once")
+                    n = int(tok[2])
+                elif n is None:
+                    raise ValueError("the vertex element must be the first element of the file, once")
+            elif tok[0] == "property" and element == "vertex":
+                if tok[1] == "list" or tok[1] not in _PLY_SCALARS:
+                    raise ValueError(f"vertex property {tok[-1]!r}: only scalar properties are supported (got {tok[1]!r})")
+                fields.append((tok[2], _PLY_SCALARS[tok[1]]))
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"expected a binary_little_endian PLY (got {fmt!r}): convert ASCII or big-endian files first")
+        names = [k for k, _ in fields]
+        if n is None or len(set(names)) != len(names) or not all(k in names for k in "xyz"):
+            raise ValueError("expected a vertex element with properties x, y, z")
+        v = np.fromfile(f, dtype=np.dtype(fields), count=n)
+    if len(v) != n:
+        raise ValueError("PLY file is truncated")
+    xyz = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32)
+    rgb = None
+    if all(k in names and v.dtype[k] == np.uint8 for k in ("red", "green", "blue")):
+        rgb = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.float32) / np.float32(255)
+    return xyz, rgb
+
+
+def check_points(xyz, rgb=None, opacity=0.1):
+    """The arguments of gaussians_from_points, refused with ValueError before the library or the device is touched: xyz (N, 3) with
+    N >= 1 and finite, rgb None or (N, 3), opacity in (0, 1).  Returns them as float32 host arrays."""
+    if hasattr(xyz, "detach"):
+        xyz = xyz.detach().cpu().numpy()
+    xyz = np.asarray(xyz)
+    if xyz.ndim != 2 or xyz.shape[1] != 3 or xyz.shape[0] < 1:
+        raise ValueError(f"xyz must have shape (N, 3) with N >= 1 (got {xyz.shape})")
+    xyz = np.ascontiguousarray(xyz, np.float32)
+    if not np.isfinite(xyz).all():
+        raise ValueError("xyz must be finite")
+    if rgb is not None:
+        if hasattr(rgb, "detach"):
+            rgb = rgb.detach().cpu().numpy()
+        rgb = np.asarray(rgb)
+        if rgb.shape != xyz.shape:
+            raise ValueError(f"rgb must have shape {xyz.shape}, one colour per point (got {rgb.shape})")
+        rgb = np.ascontiguousarray(rgb, np.float32)
+    opacity = float(opacity)
+    if not 0.0 < opacity < 1.0:
+        raise ValueError(f"opacity must be in (0, 1) (got {opacity})")
+    return xyz, rgb, opacity
+
+
+def gaussians_from_points(xyz, rgb=None, opacity=0.1, device="cuda"):
+    """The trainer's five-array `params` dict for Gaussians at the points `xyz` (N, 3): scales from the three nearest neighbours
+    (knn.init_scales), rotations as densify.init_gaussian_params stores them, `opacity` everywhere, SH DC = (rgb - 0.5) / C0 (0
+    without colours), zeros above DC."""
+    import torch
+    from . import densify, knn
+    xyz, rgb, opacity = check_points(xyz, rgb, opacity)
+    dev = torch.device(device)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    n = xyz.shape[0]
+    P = densify.alloc_params(n, dev)
+    P["positions"].copy_(torch.from_numpy(xyz))
+    P["scales"].copy_(knn.init_scales(P["positions"]))
+    P["rotations"][:, 0] = 1.0                                  # (1, 0, 0, 0) as stored, as gsr_init_gaussians leaves it
+    P["opacities"].fill_(opacity)
+    if rgb is not None:
+        P["shs"].view(n, 16, 3)[:, 0, :] = torch.from_numpy((rgb - np.float32(0.5)) / np.float32(SH_C0)).to(dev)
+    return P

@@ -54,6 +54,12 @@ by 3 M_v, M_v the view's weight total; the summary adds the weighted L1 / PSNR /
 --occluders K (--occluder-seed, --occluder-size F) pastes K opaque saturated rectangles of side up to F of the image's into every
 training target at load, elsewhere in every view; --mask-occluders trains with the masks of exactly those rectangles, dilated, and
 the summary then also scores every view against the clean targets (clean_psnr_mean, clean_ssim_mean, clean_l1_mean).
+
+Starting from a point cloud (include/gsr_knn.h, knn.py): --init knn keeps the reference start's positions and gives every Gaussian
+the isotropic scale the original 3DGS starts with, the root of the mean squared distance to its three nearest neighbours, instead
+of the constant 0.1; --init-points FILE.ply starts from the points (and uchar colours) of a binary PLY the same way
+(point_cloud.gaussians_from_points) and takes the point count from the file.  The --log header records `init`, the smallest, median and
+largest initial scale, and `first_iteration_pairs`, the (tile, Gaussian) pair count D of the run's first frame.
 """
 import argparse
 import importlib
@@ -267,7 +273,7 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets=No
 
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
            alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None, weights=None, clean_targets=None,
-           clean_depth_targets=None):
+           clean_depth_targets=None, init_info=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -324,7 +330,7 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
         curve = loss_hist[:args.iterations].cpu().numpy()
         scurve = ssim_hist[:args.iterations].cpu().numpy() if ssim_hist is not None else None
         with open(args.log, "w") as f:
-            f.write(json.dumps({"record": "arguments", **{k: v for k, v in vars(args).items()}}) + "\n")
+            f.write(json.dumps({"record": "arguments", **{k: v for k, v in vars(args).items()}, **(init_info or {})}) + "\n")
             for d in density_log:
                 f.write(json.dumps({"record": "density_control", **d}) + "\n")
             for d in capacity_log:
@@ -366,8 +372,12 @@ def main():
     ap.add_argument("--densify-interval", type=int, default=100)
     ap.add_argument("--opacity-reset-interval", type=int, default=3000)
     ap.add_argument("--save-interval", type=int, default=500)   # config.py:32
-    ap.add_argument("--init", default="reference", choices=["reference", "random"], help="initial Gaussians: the reference's "
-                    "init_gaussian_params, or a seeded random scene")
+    ap.add_argument("--init", default=None, choices=["reference", "random", "knn"], help="initial Gaussians: the reference's "
+                    "init_gaussian_params (the default), a seeded random scene, or knn: the reference's positions with the scale of "
+                    "each set from its three nearest neighbours (include/gsr_knn.h), the original 3DGS start from random points")
+    ap.add_argument("--init-points", default=None, metavar="FILE.ply", help="start from the points of a binary little-endian PLY "
+                    "(x y z, optional uchar red green blue): kNN scales, opacity 0.1, the colours in the SH DC term.  The point "
+                    "count comes from the file (--gaussians is overridden); not with an explicit --init reference or --init random")
     ap.add_argument("--backend", default=None, help="collective backend (default: nccl = RCCL); gloo + --single-device rehearses N ranks on one GPU")
     ap.add_argument("--single-device", action="store_true")
     ap.add_argument("--dense-sh", action="store_true", help="materialise the 48-float SH gradient (backward's dense return, one "
@@ -455,6 +465,19 @@ def main():
     ap.add_argument("--occluder-size", type=float, default=0.25, metavar="F", help="largest side of a rectangle, as a fraction of the image's")
     ap.add_argument("--mask-occluders", action="store_true", help="train with the masks of exactly those rectangles (dilated by --mask-dilate)")
     args = ap.parse_args()
+    if args.init_points and args.init in ("reference", "random"):
+        raise SystemExit(f"--init-points starts from the file's points: it cannot be combined with --init {args.init}")
+    init_cloud = None
+    if args.init_points:
+        try:
+            init_cloud = gsr.point_cloud.load_points(args.init_points)
+        except (ValueError, OSError) as e:
+            raise SystemExit(f"--init-points: {e}") from None
+        if len(init_cloud[0]) < 1:
+            raise SystemExit("--init-points: the file holds no points")
+        print(f"--init-points: {len(init_cloud[0])} points from {args.init_points} (--gaussians {args.gaussians} is overridden)", flush=True)
+        args.gaussians, args.init = len(init_cloud[0]), "points"
+    args.init = args.init or "reference"
     if args.mask_dilate < 0 or args.occluders < 0 or not 0.0 < args.occluder_size <= 1.0:
         raise SystemExit("--mask-dilate and --occluders must be >= 0, --occluder-size in (0, 1]")
     if args.mask_dir and not args.dataset:
@@ -579,11 +602,24 @@ def main():
     if args.init == "reference":
         # the reference trainer's start (train.py:37-92, 193-214): randf-hashed positions in (-1.3, 1.3)^3, scale 0.1, opacity 0.1
         P = gsr.densify.init_gaussian_params(n, 0.1, dev)
+    elif args.init == "knn":
+        # the same positions, every scale from the point's three nearest neighbours: the original's start from random points
+        P = gsr.densify.init_gaussian_params(n, 0.1, dev)
+        P["scales"].copy_(gsr.knn.init_scales(P["positions"]))
+    elif args.init == "points":
+        P = gsr.point_cloud.gaussians_from_points(init_cloud[0], init_cloud[1], device=dev)
     else:
         init = gsr.scenes.synthetic_scene(n, 0.05, 0.5, seed=8)             # same on every rank (replicated parameters)
         t = lambda a, shape: torch.as_tensor(np.ascontiguousarray(a, np.float32)).reshape(shape).to(dev)
         P = {"positions": t(init["means"], (n, 3)), "scales": t(init["scales"], (n, 3)), "rotations": t(init["rotations"], (n, 4)),
              "opacities": t(init["opacities"], (n,)), "shs": t(init["shs"], (n * 16, 3))}
+    init_info = {"init": args.init}
+    if args.init in ("knn", "points"):
+        s0 = P["scales"][:, 0]
+        init_info.update({"init_scale_min": float(s0.min().item()), "init_scale_median": float(s0.median().item()),
+                          "init_scale_max": float(s0.max().item())})
+        print(f"--init {args.init}: {n} Gaussians, initial scale min {init_info['init_scale_min']:.4g} median "
+              f"{init_info['init_scale_median']:.4g} max {init_info['init_scale_max']:.4g}", flush=True)
     model = gsr.densify.GaussianModel(
         P, scene_extent=gsr.densify.calculate_scene_extent([c["camera_center"] for c in cams]),
         config={"densify_from_iter": args.densify_from, "densify_until_iter": args.densify_until, "densification_interval": args.densify_interval,
@@ -651,6 +687,7 @@ def main():
                       image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"], **MODE_KW)
             if capacity is None:
                 img, dep, buf = gsr.render_gaussians(**kw)
+                init_info.setdefault("first_iteration_pairs", int(buf["point_list"].shape[0]))   # D of the run's first frame (sized: the host has it)
                 if args.capacity:
                     sized_D.append(int(buf["point_list"].shape[0]))        # (the sized path's D: what --capacity learns K from)
             else:
@@ -825,7 +862,7 @@ def main():
                      "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets)
+               poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets, init_info)
 
 
 if __name__ == "__main__":
