@@ -13,10 +13,11 @@
 // Culled Gaussians add nothing; radii, rectangles and the sort order are piecewise constant.
 //
 // The sum over Gaussians is bitwise reproducible (no float atomics): camera_partials_kernel runs a fixed grid (a function of N
-// alone), each lane sums its grid-stride Gaussians in float32, the wave reduces by shuffles and the workgroup its four waves
-// in float64 into one row of partials (plain vector stores); camera_finish_kernel, one workgroup, sums the rows in a fixed
-// order in float64 and rounds once.  A standalone pair of launches after the blend half: geom_backward_kernel is not touched.
-#include "gsr_internal.h"
+// alone), each lane sums its grid-stride Gaussians in float32, and the rest is a fixed-order sum ("The fixed-order
+// sum"; fixed_sum.h) with serial wave sums: float32 butterflies and float64 wave sums into one row of partials (plain vector
+// stores); camera_finish_kernel, one workgroup, walks the rows and sums them in float64 and rounds once.  A standalone pair of
+// launches after the blend half: geom_backward_kernel is not touched.
+#include "fixed_sum.h"
 #include "sh_stage.h"
 #include "sigma3d.h"
 
@@ -206,7 +207,7 @@ __global__ __launch_bounds__(256) void camera_partials_kernel(int64_t N, const f
                                                               double *__restrict__ partials, AaIn... aa_in)
 {
     static_assert(sizeof...(AaIn) == (AA ? 2 : 0), "opacity and aa_scale, in the AA kernel only");
-    __shared__ double s_wave[4][kSlots];
+    __shared__ double s_wave[GSR_SUM_WAVES][kSlots];
     float acc[kSlots];
 #pragma unroll
     for (int k = 0; k < kSlots; ++k) acc[k] = 0.0f;
@@ -214,59 +215,24 @@ __global__ __launch_bounds__(256) void camera_partials_kernel(int64_t N, const f
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride)
         if (radii[i] > 0)
             camera_term<AA>(i, means, scales, rots, shs, degree, scale_mod, cam, cov3Ds, clamped_state, accs, sh_dir_grad, acc, aa_in...);
-    // the wave's sums (butterfly: every lane ends with the same bits), then the four waves in float64, in wave order
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) {
-        float v = acc[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        acc[k] = v;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kSlots; ++k) s_wave[wv][k] = (double)acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < kRow) {
-        double s = 0.0;
-        if (threadIdx.x < kSlots) s = ((s_wave[0][threadIdx.x] + s_wave[1][threadIdx.x]) + s_wave[2][threadIdx.x]) + s_wave[3][threadIdx.x];
-        partials[(size_t)blockIdx.x * kRow + threadIdx.x] = s;
-    }
+    // the wave's sums in float32, then the four waves in float64, in wave order
+    const GsrBlockSums<double, kSlots> b = gsr_block_sums<256, true>(acc, s_wave);
+    if (threadIdx.x < kRow) partials[(size_t)blockIdx.x * kRow + threadIdx.x] = threadIdx.x < kSlots ? b.serial(threadIdx.x) : 0.0;
 }
 
-// one workgroup: lane t sums rows t, t + 256, ... (at most four: the grid is capped at GSR_CAMERA_MAX_BLOCKS) in float64, the
-// waves reduce by the same butterfly as above and the four wave sums are added in wave order: a fixed order throughout
+// one workgroup: the record walk over the rows (at most four per lane: the grid is capped at GSR_CAMERA_MAX_BLOCKS) and the
+// same tree, all in float64, the four wave sums again in wave order
 __global__ __launch_bounds__(256) void camera_finish_kernel(int nblk, const double *__restrict__ partials, float *__restrict__ out)
 {
-    __shared__ double s_wave[4][kSlots];
-    double acc[kSlots];
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) acc[k] = 0.0;
-    for (int b = threadIdx.x; b < nblk; b += 256) {
-        const double *row = partials + (size_t)b * kRow;
-#pragma unroll
-        for (int k = 0; k < kSlots; ++k) acc[k] += row[k];
-    }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < kSlots; ++k) {
-        double v = acc[k];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        acc[k] = v;
-    }
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kSlots; ++k) s_wave[wv][k] = acc[k];
-    }
-    __syncthreads();
+    __shared__ double s_wave[GSR_SUM_WAVES][kSlots];
+    GsrLaneSums<double, kSlots> acc = gsr_record_walk<kSlots, kRow>(partials, nblk);
+    const GsrBlockSums<double, kSlots> b = gsr_block_sums<256, true>(acc.v, s_wave);
     if (threadIdx.x < 36) {
         int k = -1;
 #pragma unroll
         for (int j = 0; j < kSlots; ++j)
             if (kOut[j] == (int)threadIdx.x) k = j;
-        const double v = k >= 0 ? ((s_wave[0][k] + s_wave[1][k]) + s_wave[2][k]) + s_wave[3][k] : 0.0;
+        const double v = k >= 0 ? b.serial(k) : 0.0;
         out[threadIdx.x] = (float)v;
     }
 }

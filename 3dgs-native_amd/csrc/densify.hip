@@ -177,7 +177,6 @@ __global__ __launch_bounds__(256) void fill_kernel(int64_t N, float v, float *__
 }
 
 bool params_ok(const GsrParams *p) { return p && (p->N == 0 || (p->positions && p->scales && p->rotations && p->opacities && p->shs)); }
-int done() { return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP; }
 unsigned blocks_for(int64_t threads) { return (unsigned)gsr_div_up(threads, 256); }
 constexpr int64_t MAX_ROWS = (int64_t)1 << 27; // 16 lanes per row must fit a 32-bit grid; row*3 must fit the int32 the generator is seeded with
 
@@ -195,7 +194,7 @@ int gsr_densify_mark(const GsrParams *p, const float *pos_grad, int64_t n_grad, 
     const float scale_threshold = percent_dense * scene_extent; // float32 product, as in the kernels (optimizer.py:199, 232)
     hipLaunchKernelGGL(mark_kernel, dim3(blocks_for(p->N)), dim3(256), 0, (hipStream_t)stream, *p, pos_grad, n_grad, grad_threshold,
                        scale_threshold, mode, mask);
-    return done();
+    return gsr_done();
 }
 
 int gsr_prune_mark(const GsrParams *p, float opacity_threshold, int32_t *valid, void *stream)
@@ -205,7 +204,7 @@ int gsr_prune_mark(const GsrParams *p, float opacity_threshold, int32_t *valid, 
     if (p->N == 0) return GSR_OK;
     if (!p->opacities || !valid) return GSR_E_NULL;
     hipLaunchKernelGGL(prune_mark_kernel, dim3(blocks_for(p->N)), dim3(256), 0, (hipStream_t)stream, p->N, p->opacities, opacity_threshold, valid);
-    return done();
+    return gsr_done();
 }
 
 int gsr_split_removal_mask(int64_t n_total, int64_t offset, const int32_t *split_mask, int32_t *valid, void *stream)
@@ -214,7 +213,7 @@ int gsr_split_removal_mask(int64_t n_total, int64_t offset, const int32_t *split
     if (n_total == 0) return GSR_OK;
     if (!valid || (offset > 0 && !split_mask)) return GSR_E_NULL;
     hipLaunchKernelGGL(split_removal_kernel, dim3(blocks_for(n_total)), dim3(256), 0, (hipStream_t)stream, n_total, offset, split_mask, valid);
-    return done();
+    return gsr_done();
 }
 
 size_t gsr_mask_scan_workspace_bytes(int64_t N) { return N <= 0 ? 256 : gsr_align(((size_t)gsr_div_up(N, GSR_SCAN_WAVE_ITEMS) + 4) * sizeof(int32_t)); } // + 4: read as int4
@@ -242,7 +241,7 @@ int gsr_clone_gaussians(const GsrParams *in, const int32_t *mask, const int32_t 
     if (in->N == 0) return GSR_OK;
     if (!mask || !prefix) return GSR_E_NULL;
     hipLaunchKernelGGL(clone_kernel, dim3(blocks_for(in->N * 16)), dim3(256), 0, (hipStream_t)stream, *in, mask, prefix, noise_scale, *out);
-    return done();
+    return gsr_done();
 }
 
 int gsr_split_gaussians(const GsrParams *in, const int32_t *mask, const int32_t *prefix, int32_t n_split, float scale_factor, const GsrParams *out,
@@ -254,7 +253,7 @@ int gsr_split_gaussians(const GsrParams *in, const int32_t *mask, const int32_t 
     if (!mask || !prefix) return GSR_E_NULL;
     hipLaunchKernelGGL(split_kernel, dim3(blocks_for(in->N * 16)), dim3(256), 0, (hipStream_t)stream, *in, mask, prefix, (int)n_split, scale_factor,
                        *out);
-    return done();
+    return gsr_done();
 }
 
 int gsr_compact_gaussians(const GsrParams *in, const int32_t *valid, const int32_t *prefix, const GsrParams *out, void *stream)
@@ -264,7 +263,7 @@ int gsr_compact_gaussians(const GsrParams *in, const int32_t *valid, const int32
     if (in->N == 0 || out->N == 0) return GSR_OK;
     if (!valid || !prefix) return GSR_E_NULL;
     hipLaunchKernelGGL(compact_kernel, dim3(blocks_for(in->N * 16)), dim3(256), 0, (hipStream_t)stream, *in, valid, prefix, *out);
-    return done();
+    return gsr_done();
 }
 
 int gsr_init_gaussians(const GsrParams *out, float init_scale, void *stream)
@@ -273,7 +272,7 @@ int gsr_init_gaussians(const GsrParams *out, float init_scale, void *stream)
     if (out->N < 0 || out->N > MAX_ROWS) return GSR_E_DIMS;
     if (out->N == 0) return GSR_OK;
     hipLaunchKernelGGL(init_kernel, dim3(blocks_for(out->N * 16)), dim3(256), 0, (hipStream_t)stream, *out, init_scale);
-    return done();
+    return gsr_done();
 }
 
 int gsr_reset_opacities(int64_t N, float max_opacity, float *opacities, void *stream)
@@ -282,7 +281,7 @@ int gsr_reset_opacities(int64_t N, float max_opacity, float *opacities, void *st
     if (N == 0) return GSR_OK;
     if (!opacities) return GSR_E_NULL;
     hipLaunchKernelGGL(fill_kernel, dim3(blocks_for(N)), dim3(256), 0, (hipStream_t)stream, N, max_opacity, opacities);
-    return done();
+    return gsr_done();
 }
 
 } // extern "C"

@@ -68,7 +68,6 @@ __global__ __launch_bounds__(256) void prune_mark_stats_kernel(int64_t N, const 
     valid[i] = keep ? 1 : 0;
 }
 
-int done() { return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP; }
 unsigned blocks_for(int64_t threads) { return (unsigned)gsr_div_up(threads, 256); }
 constexpr int64_t MAX_ROWS = (int64_t)1 << 27; // densify.hip's row limit
 
@@ -98,7 +97,7 @@ int gsr_densify_stats_update(const GsrDensifyStats *stats, const int32_t *radii,
     const int col = use_abs ? gsr_gradrec_slot(10) : gsr_gradrec_slot(3); // columns 12-13 or 3-4
     hipLaunchKernelGGL(densify_stats_update_kernel, dim3(blocks_for(N)), dim3(256), 0, (hipStream_t)stream, N, radii, acc, col, stats->grad_accum,
                        stats->vis_count, stats->max_radii);
-    return done();
+    return gsr_done();
 }
 
 int gsr_densify_mark_stats(const GsrParams *params, const GsrDensifyStats *stats, float grad_threshold, float scene_extent, float percent_dense,
@@ -112,7 +111,7 @@ int gsr_densify_mark_stats(const GsrParams *params, const GsrDensifyStats *stats
     const float scale_threshold = percent_dense * scene_extent; // float32 product, as gsr_densify_mark's
     hipLaunchKernelGGL(densify_mark_stats_kernel, dim3(blocks_for(params->N)), dim3(256), 0, (hipStream_t)stream, params->N, params->scales, stats->N,
                        stats->grad_accum, stats->vis_count, grad_threshold, scale_threshold, mode, mask);
-    return done();
+    return gsr_done();
 }
 
 int gsr_prune_mark_stats(const GsrParams *params, const GsrDensifyStats *stats, float opacity_threshold, float max_screen_radius,
@@ -125,7 +124,7 @@ int gsr_prune_mark_stats(const GsrParams *params, const GsrDensifyStats *stats, 
     if (!params->opacities || !params->scales || !valid) return GSR_E_NULL;
     hipLaunchKernelGGL(prune_mark_stats_kernel, dim3(blocks_for(params->N)), dim3(256), 0, (hipStream_t)stream, params->N, params->opacities,
                        params->scales, stats->N, stats->max_radii, opacity_threshold, max_screen_radius, max_world_scale, valid);
-    return done();
+    return gsr_done();
 }
 
 } // extern "C"

@@ -5,7 +5,7 @@
 // existing kernel touched.  Three launches on the caller's stream, no host wait, no float atomics:
 //   depth_corr_sums_kernel    a fixed grid of at most GSR_DEPTH_CORR_MAX_BLOCKS workgroups walks the image, 4 consecutive pixels per lane
 //                             and round as one 16-byte load per image, and leaves the six float64 sums of its pixels in one 64-byte
-//                             record (registers, a 64-lane butterfly, the 4 waves through LDS -- exposure.hip's tree, in float64).
+//                             record (a fixed-order sum in float64 with pairwise wave sums: DESIGN.md, "The fixed-order sum"; fixed_sum.h).
 //   depth_corr_finish_kernel  one workgroup adds the records in a fixed order, forms the moments, the degeneracy test, rho, loss and
 //                             fit in float64, and leaves (mu_r, mu_t, k1, k2, degenerate) in the record behind the partial ones.
 //   depth_corr_grad_kernel    one 4-pixel group per lane: grad = float(k1 m ((t - mu_t) - k2 (r - mu_r))), the centring in float64.
@@ -22,8 +22,8 @@
 // in the step; grad is stored with the default policy, the backward blend reads it next.
 #include <math.h>
 
+#include "fixed_sum.h"
 #include "gsr_depth_corr.h"
-#include "gsr_internal.h"
 #include "sh_stage.h"
 
 namespace {
@@ -50,31 +50,12 @@ __device__ __forceinline__ void add_pixel(float rf, float tf, float mf, double s
     s[5] += mr * t;
 }
 
-// The workgroup's sums: a butterfly over each wave, then the 4 waves through LDS.  After the call (it ends in a barrier) every thread
-// may read total(k); the order of the additions is fixed.
-struct BlockSums {
-    double (*red)[NS];
-    __device__ __forceinline__ double total(int k) const { return (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]); }
-};
-__device__ __forceinline__ BlockSums block_sums(double s[NS])
-{
-    __shared__ double s_red[NT / GSR_WAVE][NS];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < NS; ++k) s[k] += __shfl_xor(s[k], d, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < NS; ++k) s_red[threadIdx.x >> 6][k] = s[k];
-    __syncthreads();
-    return BlockSums{s_red};
-}
-
 // workgroup k leaves its six sums in part[REC * k]; `groups` = ceil(P / 4)
 template <bool MASK>
 __global__ __launch_bounds__(NT) void depth_corr_sums_kernel(int64_t P, int64_t groups, const float *__restrict__ rendered, const float *__restrict__ target,
                                                              const float *__restrict__ mask, double *__restrict__ part)
 {
+    __shared__ double s_red[GSR_SUM_WAVES][NS];
     double s[NS] = {};
     const int64_t stride = (int64_t)gridDim.x * NT;
     for (int64_t q = (int64_t)blockIdx.x * NT + threadIdx.x; q < groups; q += stride) {
@@ -89,29 +70,25 @@ __global__ __launch_bounds__(NT) void depth_corr_sums_kernel(int64_t P, int64_t 
         }
         for (int64_t i = GROUP * q; i < P; ++i) add_pixel(rendered[i], target[i], MASK ? mask[i] : 1.0f, s);
     }
-    const BlockSums b = block_sums(s);
-    if (threadIdx.x < NS) part[(size_t)REC * blockIdx.x + threadIdx.x] = b.total(threadIdx.x);
+    const GsrBlockSums<double, NS> b = gsr_block_sums<NT>(s, s_red);
+    if (threadIdx.x < NS) part[(size_t)REC * blockIdx.x + threadIdx.x] = b.pairwise(threadIdx.x);
 }
 
-// one workgroup: thread t adds records t, t + 256, ... in ascending order, then the same reduction; thread 0 forms the results
+// one workgroup: the record walk, then the same tree; thread 0 forms the results
 __global__ __launch_bounds__(NT) void depth_corr_finish_kernel(const double *__restrict__ part, int n, float weight, float *__restrict__ loss,
                                                                float *__restrict__ fit /* may be NULL */, double *__restrict__ stats)
 {
-    double s[NS] = {};
-    for (int r = threadIdx.x; r < n; r += NT) {
-        const double2 *rec = reinterpret_cast<const double2 *>(part + (size_t)REC * r);
-        const double2 a = rec[0], b = rec[1], c = rec[2];
-        s[0] += a.x, s[1] += a.y, s[2] += b.x, s[3] += b.y, s[4] += c.x, s[5] += c.y;
-    }
-    const BlockSums b = block_sums(s);
+    __shared__ double s_red[GSR_SUM_WAVES][NS];
+    GsrLaneSums<double, NS> s = gsr_record_walk<NS, REC>(part, n);
+    const GsrBlockSums<double, NS> b = gsr_block_sums<NT>(s.v, s_red);
     if (threadIdx.x != 0) return;
-    const double M = b.total(0);
+    const double M = b.pairwise(0);
     double mu_r = 0.0, mu_t = 0.0, k1 = 0.0, k2 = 0.0, rho = 0.0, sc = 0.0, off = 0.0;
     bool ok = M > 0.0;
     if (ok) {
-        mu_r = b.total(1) / M, mu_t = b.total(2) / M;
-        const double err2 = b.total(3) / M, ett2 = b.total(4) / M;
-        const double Vr = err2 - mu_r * mu_r, Vt = ett2 - mu_t * mu_t, C = b.total(5) / M - mu_r * mu_t;
+        mu_r = b.pairwise(1) / M, mu_t = b.pairwise(2) / M;
+        const double err2 = b.pairwise(3) / M, ett2 = b.pairwise(4) / M;
+        const double Vr = err2 - mu_r * mu_r, Vt = ett2 - mu_t * mu_t, C = b.pairwise(5) / M - mu_r * mu_t;
         ok = Vr > GSR_DEPTH_CORR_MIN_REL_VAR * err2 && Vt > GSR_DEPTH_CORR_MIN_REL_VAR * ett2;   // (false for a NaN too)
         if (ok) {
             const double sd = sqrt(Vr * Vt);
@@ -158,15 +135,7 @@ __global__ __launch_bounds__(NT) void depth_corr_grad_kernel(int64_t P, const fl
         grad[i] = degenerate ? 0.0f : grad_pixel(rendered[i], target[i], MASK ? mask[i] : 1.0f, mu_r, mu_t, k1, k2);
 }
 
-constexpr int64_t MAX_PIXELS = (int64_t)1 << 28;
-bool dims_ok(int32_t W, int32_t H) { return W > 0 && H > 0 && (int64_t)W * H <= MAX_PIXELS; }
-bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }   // null counts as aligned
-int64_t sum_blocks(int64_t P)
-{
-    const int64_t nb = gsr_div_up(P, GSR_DEPTH_CORR_BLOCK_PIXELS);
-    return nb < GSR_DEPTH_CORR_MAX_BLOCKS ? nb : GSR_DEPTH_CORR_MAX_BLOCKS;
-}
-int done() { return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP; }
+int64_t sum_blocks(int64_t P) { return gsr_record_count(P, GSR_DEPTH_CORR_BLOCK_PIXELS, GSR_DEPTH_CORR_MAX_BLOCKS); }
 
 } // namespace
 
@@ -174,7 +143,7 @@ extern "C" {
 
 size_t gsr_depth_corr_workspace_bytes(int32_t W, int32_t H)
 {
-    if (!dims_ok(W, H)) return 0;
+    if (!gsr_image_dims_ok(W, H)) return 0;
     return gsr_align((size_t)GSR_DEPTH_CORR_RECORD_BYTES * (size_t)(sum_blocks((int64_t)W * H) + 1));   // + the moments' record
 }
 
@@ -182,9 +151,9 @@ int gsr_depth_corr_loss_grad(const float *rendered, const float *target, const f
                              float weight, void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!rendered || !target || !loss || !workspace) return GSR_E_NULL;
-    if (!dims_ok(W, H) || !isfinite(weight)) return GSR_E_DIMS;
+    if (!gsr_image_dims_ok(W, H) || !isfinite(weight)) return GSR_E_DIMS;
     if (!gsr_aligned16(rendered) || !gsr_aligned16(target) || !gsr_aligned16(mask) || !gsr_aligned16(grad) || !gsr_aligned16(workspace) ||
-        !aligned4(loss) || !aligned4(fit))
+        !gsr_aligned4(loss) || !gsr_aligned4(fit))
         return GSR_E_ALIGN;
     if (workspace_bytes < gsr_depth_corr_workspace_bytes(W, H)) return GSR_E_WORKSPACE;
     const int64_t P = (int64_t)W * H, groups = gsr_div_up(P, GROUP);
@@ -199,7 +168,7 @@ int gsr_depth_corr_loss_grad(const float *rendered, const float *target, const f
         if (mask) hipLaunchKernelGGL(depth_corr_grad_kernel<true>, grid, dim3(NT), 0, s, P, rendered, target, mask, (const double *)stats, grad);
         else hipLaunchKernelGGL(depth_corr_grad_kernel<false>, grid, dim3(NT), 0, s, P, rendered, target, mask, (const double *)stats, grad);
     }
-    return done();
+    return gsr_done();
 }
 
 } // extern "C"

@@ -1,6 +1,6 @@
 // dssim_window.h -- the separable 11-tap window of the D-SSIM kernels: tile staging, horizontal and vertical window sums, S and
-// its adjoint weights at one pixel, and the per-workgroup partial sums.  Shared by dssim.hip and dssim_weighted.hip (not part of
-// the C ABI); everything sits in the including file's anonymous namespace.
+// its adjoint weights at one pixel.  Used by dssim.hip (not part of the C ABI); everything sits in the including file's anonymous
+// namespace.
 #pragma once
 #include <math.h>
 
@@ -147,24 +147,6 @@ __device__ __forceinline__ float ssim_terms(const float (&s)[5], float inv_wp, f
     return S;
 }
 
-// workgroup sums of two per-thread values into part[blockIdx] (fixed order: the same bits every call)
-__device__ __forceinline__ void block_partials(float l1, float ss, float2 *part, float *s_red)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        l1 += __shfl_xor(l1, d, 64);
-        ss += __shfl_xor(ss, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        s_red[threadIdx.x >> 6] = l1;
-        s_red[4 + (threadIdx.x >> 6)] = ss;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-        part[blockIdx.y * gridDim.x + blockIdx.x] = make_float2((s_red[0] + s_red[1]) + (s_red[2] + s_red[3]),
-                                                                (s_red[4] + s_red[5]) + (s_red[6] + s_red[7]));
-}
-
 // the taps by distance 0..5, sigma = 1.5 as loss.py:33-45; the reference window indexes the Gaussian centred on 5 by distance (Q21)
 inline DssimW window_taps(bool reference)
 {
@@ -176,13 +158,11 @@ inline DssimW window_taps(bool reference)
     return k;
 }
 
-constexpr int64_t MAX_PIXELS = (int64_t)1 << 28;
-
 // workspace: [partials: one float2 per workgroup, padded to 256 bytes] [9 planes of W * H floats: alpha, beta, gamma per channel]
 inline size_t partial_bytes(int32_t W, int32_t H) { return gsr_align(sizeof(float2) * (size_t)gsr_div_up(W, TX) * (size_t)gsr_div_up(H, TY)); }
 inline size_t dssim_workspace_bytes(int32_t W, int32_t H)
 {
-    if (W <= 0 || H <= 0 || (int64_t)W * H > MAX_PIXELS) return 0;
+    if (!gsr_image_dims_ok(W, H)) return 0;
     return gsr_align(partial_bytes(W, H) + 9 * sizeof(float) * (size_t)W * H);
 }
 

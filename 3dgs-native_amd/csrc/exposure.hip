@@ -8,12 +8,12 @@
 // 12 wave-uniform values behind a __restrict__ pointer: they arrive through the scalar cache once per wave and live in SGPRs.
 // Cache policy: default everywhere -- the render is read again by the backward, `out` by the loss kernel that follows, and
 // dL_drendered by the backward blend (an 800 x 800 image is 7.7 MB: it stays in L2 / the Infinity Cache between the launches).
-// The 12 sums never meet a float atomic: registers, a wave butterfly, the workgroup's 4 waves through LDS, one 64-byte record per
-// workgroup in the workspace, and a one-workgroup launch that adds the records in a fixed order.
+// The 12 sums never meet a float atomic: they are a fixed-order sum ("The fixed-order sum"; fixed_sum.h) with pairwise
+// wave sums and one 64-byte record per workgroup in the workspace.
 #include <math.h>
 
+#include "fixed_sum.h"
 #include "gsr_exposure.h"
-#include "gsr_internal.h"
 
 namespace {
 
@@ -95,27 +95,13 @@ __global__ __launch_bounds__(NT) void exposure_apply_kernel(int64_t P, const flo
     }
 }
 
-// the 12 sums of a workgroup's lanes into dst[0..11]: a butterfly over the wave, the 4 waves through LDS, in a fixed order
-__device__ __forceinline__ void block_sums(float s[NE], float *dst)
-{
-    __shared__ float s_red[NT / GSR_WAVE][NE];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1)
-#pragma unroll
-        for (int k = 0; k < NE; ++k) s[k] += __shfl_xor(s[k], d, 64);
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < NE; ++k) s_red[threadIdx.x >> 6][k] = s[k];
-    __syncthreads();
-    if (threadIdx.x < NE) dst[threadIdx.x] = (s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + (s_red[2][threadIdx.x] + s_red[3][threadIdx.x]);
-}
-
 // A fixed grid of at most GSR_EXPOSURE_MAX_BLOCKS workgroups walks the 4-pixel groups (`groups` = ceil(P / 4)); workgroup k leaves
 // its sums in part[REC * k].  `dL_drendered` may be `dL_dout`: neither is __restrict__.
 template <bool WRITE>
 __global__ __launch_bounds__(NT) void exposure_backward_kernel(int64_t P, int64_t groups, const float *__restrict__ rendered, const float *__restrict__ E,
                                                                const float *dL_dout, float *dL_drendered, float *__restrict__ part)
 {
+    __shared__ float s_red[GSR_SUM_WAVES][NE];
     const Exposure e = load_exposure(E);
     float s[NE] = {};
     const int64_t stride = (int64_t)gridDim.x * NT;
@@ -137,20 +123,8 @@ __global__ __launch_bounds__(NT) void exposure_backward_kernel(int64_t P, int64_
             if (WRITE) dL_drendered[3 * i] = dc[0], dL_drendered[3 * i + 1] = dc[1], dL_drendered[3 * i + 2] = dc[2];
         }
     }
-    block_sums(s, part + (size_t)REC * blockIdx.x);
-}
-
-// one workgroup: thread t adds records t, t + 256, ... in ascending order, then the same reduction into dL_dE
-__global__ __launch_bounds__(NT) void exposure_finish_kernel(const float *__restrict__ part, int n, float *__restrict__ dL_dE)
-{
-    float s[NE] = {};
-    for (int r = threadIdx.x; r < n; r += NT) {
-        float v[NE];
-        ld12(part + (size_t)REC * r, 0, v);
-#pragma unroll
-        for (int k = 0; k < NE; ++k) s[k] += v[k];
-    }
-    block_sums(s, dL_dE);
+    const GsrBlockSums<float, NE> b = gsr_block_sums<NT>(s, s_red);
+    if (threadIdx.x < NE) part[(size_t)REC * blockIdx.x + threadIdx.x] = b.pairwise(threadIdx.x);
 }
 
 // one wave; lanes 0-11 own one element each
@@ -166,15 +140,7 @@ __global__ __launch_bounds__(GSR_WAVE) void exposure_adam_kernel(float *__restri
     E[k] = E[k] - lr * ((mk / bc1) / (sqrtf(vk / bc2) + eps));
 }
 
-constexpr int64_t MAX_PIXELS = (int64_t)1 << 28;
-bool dims_ok(int32_t W, int32_t H) { return W > 0 && H > 0 && (int64_t)W * H <= MAX_PIXELS; }
-bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-int64_t backward_blocks(int64_t P)
-{
-    const int64_t nb = gsr_div_up(P, GSR_EXPOSURE_BLOCK_PIXELS);
-    return nb < GSR_EXPOSURE_MAX_BLOCKS ? nb : GSR_EXPOSURE_MAX_BLOCKS;
-}
-int done() { return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP; }
+int64_t backward_blocks(int64_t P) { return gsr_record_count(P, GSR_EXPOSURE_BLOCK_PIXELS, GSR_EXPOSURE_MAX_BLOCKS); }
 
 } // namespace
 
@@ -182,27 +148,27 @@ extern "C" {
 
 size_t gsr_exposure_workspace_bytes(int32_t W, int32_t H)
 {
-    if (!dims_ok(W, H)) return 0;
+    if (!gsr_image_dims_ok(W, H)) return 0;
     return gsr_align((size_t)GSR_EXPOSURE_RECORD_BYTES * (size_t)backward_blocks((int64_t)W * H));
 }
 
 int gsr_exposure_apply(const float *rendered, const float *E, float *out, int32_t W, int32_t H, void *stream)
 {
     if (!rendered || !E || !out) return GSR_E_NULL;
-    if (!dims_ok(W, H)) return GSR_E_DIMS;
-    if (!gsr_aligned16(rendered) || !gsr_aligned16(out) || !aligned4(E)) return GSR_E_ALIGN;
+    if (!gsr_image_dims_ok(W, H)) return GSR_E_DIMS;
+    if (!gsr_aligned16(rendered) || !gsr_aligned16(out) || !gsr_aligned4(E)) return GSR_E_ALIGN;
     const int64_t P = (int64_t)W * H;
     hipLaunchKernelGGL(exposure_apply_kernel, dim3((unsigned)gsr_div_up(gsr_div_up(P, GROUP), NT)), dim3(NT), 0, (hipStream_t)stream, P, rendered, E, out);
-    return done();
+    return gsr_done();
 }
 
 int gsr_exposure_backward(const float *rendered, const float *E, const float *dL_dout, float *dL_drendered, float *dL_dE, int32_t W, int32_t H,
                           void *workspace, size_t workspace_bytes, void *stream)
 {
     if (!rendered || !E || !dL_dout || !dL_dE || !workspace) return GSR_E_NULL;
-    if (!dims_ok(W, H)) return GSR_E_DIMS;
-    if (!gsr_aligned16(rendered) || !gsr_aligned16(dL_dout) || !gsr_aligned16(dL_drendered) || !gsr_aligned16(workspace) || !aligned4(E) ||
-        !aligned4(dL_dE))
+    if (!gsr_image_dims_ok(W, H)) return GSR_E_DIMS;
+    if (!gsr_aligned16(rendered) || !gsr_aligned16(dL_dout) || !gsr_aligned16(dL_drendered) || !gsr_aligned16(workspace) || !gsr_aligned4(E) ||
+        !gsr_aligned4(dL_dE))
         return GSR_E_ALIGN;
     if (workspace_bytes < gsr_exposure_workspace_bytes(W, H)) return GSR_E_WORKSPACE;
     const int64_t P = (int64_t)W * H, groups = gsr_div_up(P, GROUP);
@@ -213,8 +179,8 @@ int gsr_exposure_backward(const float *rendered, const float *E, const float *dL
         hipLaunchKernelGGL(exposure_backward_kernel<true>, dim3(nb), dim3(NT), 0, s, P, groups, rendered, E, dL_dout, dL_drendered, part);
     else
         hipLaunchKernelGGL(exposure_backward_kernel<false>, dim3(nb), dim3(NT), 0, s, P, groups, rendered, E, dL_dout, (float *)nullptr, part);
-    hipLaunchKernelGGL(exposure_finish_kernel, dim3(1), dim3(NT), 0, s, part, nb, dL_dE);
-    return done();
+    hipLaunchKernelGGL((gsr_finish_kernel<NE, REC, 1>), dim3(1), dim3(NT), 0, s, (const float *)part, nb, GsrSumOut<1>{{dL_dE}});
+    return gsr_done();
 }
 
 int gsr_exposure_adam(float *E, const float *dL_dE, float *m, float *v, float lr, float beta1, float beta2, float eps, int32_t step, void *stream)
@@ -223,11 +189,11 @@ int gsr_exposure_adam(float *E, const float *dL_dE, float *m, float *v, float lr
     if (step < 1 || !(lr >= 0.0f) || !isfinite(lr) || !(beta1 >= 0.0f && beta1 < 1.0f) || !(beta2 >= 0.0f && beta2 < 1.0f) || !(eps > 0.0f) ||
         !isfinite(eps))
         return GSR_E_DIMS;
-    if (!aligned4(E) || !aligned4(dL_dE) || !aligned4(m) || !aligned4(v)) return GSR_E_ALIGN;
+    if (!gsr_aligned4(E) || !gsr_aligned4(dL_dE) || !gsr_aligned4(m) || !gsr_aligned4(v)) return GSR_E_ALIGN;
     // bias corrections in float32 on the host, as gsr_adam_update forms them
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
     hipLaunchKernelGGL(exposure_adam_kernel, dim3(1), dim3(GSR_WAVE), 0, (hipStream_t)stream, E, dL_dE, m, v, lr, beta1, beta2, eps, bc1, bc2);
-    return done();
+    return gsr_done();
 }
 
 } // extern "C"

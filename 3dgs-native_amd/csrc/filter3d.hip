@@ -146,7 +146,6 @@ __global__ __launch_bounds__(256) void filter3d_map_kernel(int64_t N, const floa
     }
 }
 
-int done() { return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP; }
 constexpr int64_t MAX_ROWS = ((int64_t)1 << 31) - 1;
 constexpr size_t WS_BYTES = 256; // one uint32, the smallest positive nu
 
@@ -174,7 +173,7 @@ int gsr_filter3d_from_views(int64_t N, const float *means, int32_t V, const GsrF
     const dim3 grid((unsigned)gsr_div_up(N, 256));
     hipLaunchKernelGGL(filter3d_nu_kernel, grid, dim3(256), 0, s, N, means, (int)V, views, filter_3d, min_bits);
     hipLaunchKernelGGL(filter3d_finish_kernel, grid, dim3(256), 0, s, N, filter_3d, min_bits, sqrtf(variance));
-    return done();
+    return gsr_done();
 }
 
 int gsr_filter3d_apply(int64_t N, const float *scales, const float *opacity, const float *filter_3d, float *scales_out, float *opacity_out,
@@ -187,7 +186,7 @@ int gsr_filter3d_apply(int64_t N, const float *scales, const float *opacity, con
         return GSR_E_ALIGN;
     hipLaunchKernelGGL(filter3d_map_kernel<false>, dim3((unsigned)gsr_div_up(gsr_div_up(N, 4), 256)), dim3(256), 0, (hipStream_t)stream, N, scales,
                        opacity, filter_3d, (const float *)nullptr, (const float *)nullptr, scales_out, opacity_out);
-    return done();
+    return gsr_done();
 }
 
 int gsr_filter3d_backward(int64_t N, const float *scales, const float *opacity, const float *filter_3d, const float *dL_dscale_f,
@@ -201,7 +200,7 @@ int gsr_filter3d_backward(int64_t N, const float *scales, const float *opacity, 
         return GSR_E_ALIGN;
     hipLaunchKernelGGL(filter3d_map_kernel<true>, dim3((unsigned)gsr_div_up(gsr_div_up(N, 4), 256)), dim3(256), 0, (hipStream_t)stream, N, scales,
                        opacity, filter_3d, dL_dscale_f, dL_dopacity_f, dL_dscale, dL_dopacity);
-    return done();
+    return gsr_done();
 }
 
 } // extern "C"

@@ -32,6 +32,17 @@ struct __attribute__((aligned(8))) TileRect {
 static inline bool gsr_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; } // null counts as aligned
 static inline int64_t gsr_div_up(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t gsr_align(size_t x) { return (x + 255) & ~(size_t)255; }
+// The host checks of the image-sized entry points (each reports NULL, DIMS, ALIGN, WORKSPACE in the order its ABI test holds).
+#define GSR_MAX_PIXELS ((int64_t)1 << 28)
+static inline bool gsr_image_dims_ok(int32_t W, int32_t H) { return W > 0 && H > 0 && (int64_t)W * H <= GSR_MAX_PIXELS; }
+static inline bool gsr_aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; } // single floats: any slot of a float array; null counts as aligned
+static inline int gsr_done() { return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP; }
+// records of a fixed-order sum over P pixels (fixed_sum.h): ceil(P / block pixels), capped
+static inline int64_t gsr_record_count(int64_t P, int64_t block_pixels, int64_t cap)
+{
+    const int64_t nb = gsr_div_up(P, block_pixels);
+    return nb < cap ? nb : cap;
+}
 
 #define GSR_FO_MAX_TILES 4096  // forward tile order (see below): images of at most this many tiles
 #ifndef GSR_FO_CLASSES

@@ -2,19 +2,21 @@
 // (SURVEY.md section 8(f) rows f2 and f3): L1 loss + pixel gradient, and the fused Adam update.
 #include <math.h>
 
+#include "fixed_sum.h"
 #include "gsr_aux_grads.h"
-#include "gsr_internal.h"
 #include "sh_stage.h"
 
 namespace {
 
 // ---- f2: reference loss.py:12-31 (l1_loss_kernel) + :122-146 (backprop_l1_pixel_gradients) in one pass ----
-// Flat over H*W*3 floats, float4 per lane (the image is packed vec3, so any 16-byte group is valid).
+// Flat over H*W*3 floats, float4 per lane (the image is packed vec3, so any 16-byte group is valid).  The four loss sums of this
+// file are the workgroup half of a fixed-order sum ("The fixed-order sum") with serial wave sums, ended by one atomic
+// per workgroup: the order across workgroups is not specified.
 __global__ __launch_bounds__(256) void l1_loss_grad_kernel(const float *__restrict__ rendered, const float *__restrict__ target,
                                                            float *__restrict__ pixel_grad, float *__restrict__ loss_sum, int64_t n,
                                                            float l1_weight)
 {
-    __shared__ float s_part[4];
+    __shared__ float s_part[GSR_SUM_WAVES][1];
     float acc = 0.0f;
     const int64_t n4 = n >> 2;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
@@ -32,11 +34,8 @@ __global__ __launch_bounds__(256) void l1_loss_grad_kernel(const float *__restri
         acc += fabsf(d);
         if (pixel_grad) pixel_grad[i] = l1_weight * (d < 0.0f ? -1.0f : 1.0f);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+    const GsrBlockSums<float, 1> b = gsr_block_sum<256>(acc, s_part);
+    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, b.serial(0));
 }
 
 // ---- loss.py:47-119 (ssim_kernel): one 16x16 pixel tile per workgroup, the tile and its 5-pixel halo of both images staged
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float *__restrict__ ren
 {
     constexpr int HALF = 5, SIDE = 16 + 2 * HALF;
     __shared__ float s_r[SIDE * SIDE * 3], s_t[SIDE * SIDE * 3];
-    __shared__ float s_part[4];
+    __shared__ float s_part[GSR_SUM_WAVES][1];
     const int tx0 = blockIdx.x * 16, ty0 = blockIdx.y * 16;
     for (int k = threadIdx.x; k < SIDE * SIDE; k += 256) {
         const int ly = k / SIDE, lx = k - ly * SIDE;
@@ -95,26 +94,20 @@ __global__ __launch_bounds__(256) void ssim_kernel(const float *__restrict__ ren
         }
         val = (ss[0] + ss[1] + ss[2]) / 3.0f;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) val += __shfl_xor(val, d, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = val;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(ssim_sum, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+    const GsrBlockSums<float, 1> b = gsr_block_sum<256>(val, s_part);
+    if (threadIdx.x == 0) unsafeAtomicAdd(ssim_sum, b.serial(0));
 }
 
 // ---- loss.py:247-269 (depth_loss_kernel): sum |rendered - target| * mask ----
 __global__ __launch_bounds__(256) void depth_loss_kernel(const float *__restrict__ rendered, const float *__restrict__ target,
                                                          const float *__restrict__ mask, float *__restrict__ loss_sum, int64_t n)
 {
-    __shared__ float s_part[4];
+    __shared__ float s_part[GSR_SUM_WAVES][1];
     float acc = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
         acc += fabsf(rendered[i] - target[i]) * mask[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+    const GsrBlockSums<float, 1> b = gsr_block_sum<256>(acc, s_part);
+    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, b.serial(0));
 }
 
 // ---- include/gsr_aux_grads.h: masked L1 of the inverse-depth image (ALPHA = false) or of the alpha image 1 - final_T (true),
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(256) void aux_l1_loss_grad_kernel(const float *__re
                                                                const float *__restrict__ mask, float *__restrict__ grad,
                                                                float *__restrict__ loss_sum, int64_t n, float weight)
 {
-    __shared__ float s_part[4];
+    __shared__ float s_part[GSR_SUM_WAVES][1];
     float acc = 0.0f;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const float r = ALPHA ? 1.0f - rendered[i] : rendered[i];
@@ -132,11 +125,8 @@ __global__ __launch_bounds__(256) void aux_l1_loss_grad_kernel(const float *__re
         acc += fabsf(d) * m;
         if (grad) grad[i] = weight * m * (d < 0.0f ? -1.0f : 1.0f);
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) acc += __shfl_xor(acc, d, 64);
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, s_part[0] + s_part[1] + s_part[2] + s_part[3]);
+    const GsrBlockSums<float, 1> b = gsr_block_sum<256>(acc, s_part);
+    if (threadIdx.x == 0) unsafeAtomicAdd(loss_sum, b.serial(0));
 }
 
 // ---- f3: reference optimizer.py:7-139 (adam_update) ----
