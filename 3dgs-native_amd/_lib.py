@@ -230,6 +230,21 @@ KNN_K = 3                           # GSR_KNN_K
 KNN_BLOCK_POINTS = 256              # GSR_KNN_BLOCK_POINTS
 KNN_MAX_POINTS = 1 << 27            # GSR_KNN_MAX_POINTS
 
+class GsrFeaturesFrame(C.Structure):
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("N", C.c_int64), ("D", C.c_int64), ("xy", vp), ("xy_stride", C.c_int64),
+                ("conic_opacity", vp), ("conic_opacity_stride", C.c_int64), ("point_list", vp), ("ranges", vp), ("n_contrib", vp),
+                ("block_masks", vp)]
+
+
+# include/gsr_features.h: N-channel feature rendering over a frame's lists, and its gradient with respect to the features (its own
+# header, so its own table)
+FEATURES_EXPORTS = {
+    "gsr_features_forward": (C.c_int, [C.POINTER(GsrFeaturesFrame), C.c_int32, vp, vp, vp]),
+    "gsr_features_backward": (C.c_int, [C.POINTER(GsrFeaturesFrame), C.c_int32, vp, vp, vp]),
+}
+FEATURES_MAX_CHANNELS = 64          # GSR_FEATURES_MAX_CHANNELS
+FEATURES_MAX_SIDE = 32768           # GSR_FEATURES_MAX_SIDE
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -264,7 +279,8 @@ def lib():
                                   + list(DENSIFY_STATS_EXPORTS.items()) + list(ANTIALIAS_EXPORTS.items())
                                   + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
                                   + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
-                                  + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())):
+                                  + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
+                                  + list(FEATURES_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:
