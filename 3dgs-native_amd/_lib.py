@@ -245,6 +245,23 @@ FEATURES_EXPORTS = {
 FEATURES_MAX_CHANNELS = 64          # GSR_FEATURES_MAX_CHANNELS
 FEATURES_MAX_SIDE = 32768           # GSR_FEATURES_MAX_SIDE
 
+# include/gsr_normals.h: surface normals from the rendered depth, their gradient back to the inverse-depth and alpha images, and the
+# cosine loss against a normal prior (its own header, so its own table)
+NORMALS_EXPORTS = {
+    "gsr_normals_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "gsr_normals_from_depth": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, vp, vp, vp]),
+    "gsr_normals_from_depth_backward": (C.c_int, [vp, vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, vp, vp, vp, vp, C.c_size_t, vp]),
+    "gsr_normals_loss_grad": (C.c_int, [vp, vp, vp, C.POINTER(C.c_float), vp, C.c_float, C.c_float, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                        vp, vp, vp, vp, C.c_size_t, vp]),
+}
+NORMALS_MIN_NORM2 = 1e-12           # GSR_NORMALS_MIN_NORM2 (a float32 constant: 1e-12f)
+NORMALS_ALPHA_MIN = 0.5             # GSR_NORMALS_ALPHA_MIN
+NORMALS_TILE_W = 32                 # GSR_NORMALS_TILE_W
+NORMALS_TILE_H = 8                  # GSR_NORMALS_TILE_H
+NORMALS_MAX_BLOCKS = 2048           # GSR_NORMALS_MAX_BLOCKS
+NORMALS_RECORD_BYTES = 16           # GSR_NORMALS_RECORD_BYTES
+NORMALS_SUMS_FLOATS = 2             # GSR_NORMALS_SUMS_FLOATS: (loss_sum, weight_sum)
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -280,7 +297,7 @@ def lib():
                                   + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
                                   + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
                                   + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
-                                  + list(FEATURES_EXPORTS.items())):
+                                  + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

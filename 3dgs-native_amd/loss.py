@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _host, _lib
+from . import normals as _n
 
 _WS = {}         # (kind, device, stream, W, H) -> workspace of a loss call (one per stream: views in flight on several streams)
 
@@ -299,3 +300,61 @@ def depth_corr_loss_and_gradients(rendered, target, mask=None, weight=1.0, want_
                                               weight, _host.ptr(ws), ws.numel(), stream))
     _host.written_in_place(loss_out, fit_out)
     return loss, grad, fit
+
+
+def _rotation(target_rotation):
+    """The `target_rotation` keyword as 9 host floats, row-major (None: identity, passed on as NULL)."""
+    if target_rotation is None:
+        return None
+    if isinstance(target_rotation, torch.Tensor):
+        target_rotation = target_rotation.detach().cpu().numpy()
+    R = np.asarray(target_rotation, dtype=np.float64)
+    if R.shape != (3, 3) or not np.isfinite(R).all():
+        raise ValueError(f"normal_loss_and_gradients: target_rotation must be a finite 3 x 3 matrix, not shape {R.shape}")
+    return R.astype(np.float32).reshape(9)
+
+
+def normal_loss_and_gradients(depth, final_Ts, target, camera, mask=None, weight=1.0, target_rotation=None, alpha_min=_lib.NORMALS_ALPHA_MIN,
+                              want_grad=True, loss_out=None):
+    """The cosine loss between the normals of the rendered depth and a normal prior, with its exact gradient, two launches, no host
+    sync (include/gsr_normals.h).  `depth` is the forward's inverse-depth image, `final_Ts` its img_buffer["final_Ts"], `camera` a
+    dict with tan_fovx, tan_fovy, width, height; `target` (H, W, 3), any length, in camera space after `target_rotation` (a 3 x 3
+    matrix applied to every target vector: the view rotation camera["R"] for world-space normals, a flip for another axis
+    convention; None: identity); `mask` (H, W) weights m >= 0 (None: all ones).  Normals face the camera: a fronto-parallel surface
+    has (0, 0, -1).  A pixel counts where its depth normal is valid (normals.normals_from_depth) and its target is not zero.
+    Returns (sums, dL_ddepth_image, dL_dalpha_image): sums a device tensor [2] = (sum m (1 - n . t^), sum m) over those pixels (the
+    mean loss is sums[0] / sums[1]); the two (H, W) images are the gradient of weight / (W H) * sums[0] -- depth_loss_and_gradients'
+    normalisation -- and go straight into backward(dL_ddepth_image=..., dL_dalpha_image=...); None without want_grad.
+    `loss_out`: a 2-element contiguous float32 device tensor that receives the sums instead of a fresh one."""
+    who = "normal_loss_and_gradients"
+    tx, ty, W, H = _n.camera_params(camera, who)
+    a = _n.check_alpha_min(alpha_min, who)
+    _n.check_image(depth, "depth", H, W, who=who)
+    _n.check_image(final_Ts, "final_Ts", H, W, who=who)
+    _n.check_image(target, "target", H, W, 3, who=who)
+    if mask is not None:
+        _n.check_image(mask, "mask", H, W, who=who)
+    weight = float(weight)
+    if not np.isfinite(weight):
+        raise ValueError(f"{who}: weight must be finite, not {weight}")
+    R = _rotation(target_rotation)
+    if loss_out is not None and not (isinstance(loss_out, torch.Tensor) and loss_out.is_cuda and loss_out.dtype == torch.float32
+                                     and loss_out.numel() == _lib.NORMALS_SUMS_FLOATS and loss_out.is_contiguous()):
+        raise ValueError(f"{who}: loss_out must be a contiguous 2-element float32 device tensor")
+    L = _lib.lib()
+    dev = _host.device_of(depth, final_Ts, target, mask)
+    d = _host.to_dev(depth, torch.float32, dev, (H, W))
+    t = _host.to_dev(final_Ts, torch.float32, dev, (H, W))
+    tg = _host.to_dev(target, torch.float32, dev, (H, W, 3))
+    m = _host.to_dev(mask, torch.float32, dev, (H, W)) if mask is not None else None
+    gD = torch.empty((H, W), dtype=torch.float32, device=dev) if want_grad else None
+    gA = torch.empty((H, W), dtype=torch.float32, device=dev) if want_grad else None
+    sums = torch.empty(_lib.NORMALS_SUMS_FLOATS, dtype=torch.float32, device=dev) if loss_out is None else loss_out
+    Rp = R.ctypes.data_as(_lib.C.POINTER(_lib.C.c_float)) if R is not None else None
+    with _host.on_device(dev):
+        stream = _host.stream_ptr(dev)
+        ws = _n.workspace(L, dev, stream, W, H)
+        _lib.check(L.gsr_normals_loss_grad(_host.ptr(d), _host.ptr(t), _host.ptr(tg), Rp, _host.ptr(m), tx, ty, W, H, a, weight / (W * H),
+                                           _host.ptr(gD), _host.ptr(gA), _host.ptr(sums), _host.ptr(ws), ws.numel(), stream))
+    _host.written_in_place(loss_out)
+    return sums, gD, gA

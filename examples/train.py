@@ -24,6 +24,15 @@ O(1) already: no W H).  For experiments, --depth-noise S (seed --depth-seed) sto
 masked pixels, a_v = exp(U(-S, S)), b_v = U(0, S) times the view's mean target; the summary then scores the depth against the
 clean targets too (train_depth_l1_clean_mean), and always reports the mean correlation and each view's fitted (s, b).
 
+A normal prior (include/gsr_normals.h): --lambda-normal adds lambda_n times the cosine loss 1 - n . t between the normals of the
+rendered depth (the unit cross product of the central differences of the camera-space points, where the pixel's and its four
+neighbours' alpha reaches --normal-alpha-min) and normal targets, normalised by W H; its two gradient images are added to those of
+the depth and alpha terms.  Targets: --normal-dir with --dataset, one float32 (H, W, 3) .npy per frame named after its file_path, in
+camera space (x right, y down, z forward: normals that face the camera have z < 0) or, with --normal-space world, in world space;
+else the normals of the hidden scene's own depth.  --normal-noise S (seed --normal-seed) adds N(0, S^2) to every component of every
+target once at load, for experiments.  The summary reports the mean angle between the depth normals and the clean targets
+(train_normal_angle_deg_mean) and the share of pixels that have a depth normal (train_normal_valid_share).
+
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
@@ -122,6 +131,20 @@ def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
             depths.append(d)
         cams.append(gsr.cameras.nerf_camera(fr["transform_matrix"], img.shape[1], img.shape[0], tf["camera_angle_x"]))
     out = (cams, targets) + ((alphas,) if alpha else ()) + ((depths,) if depth_dir is not None else ())
+    return out
+
+
+def load_normals(path, normal_dir, max_views, shapes, split="train"):
+    """The normal targets of --normal-dir: <normal_dir>/<basename of file_path>.npy per frame, float32 (H, W, 3), any length (a zero
+    vector: the pixel has no target)."""
+    with open(os.path.join(path, f"transforms_{split}.json")) as f:
+        tf = json.load(f)
+    out = []
+    for fr, hw in zip(tf["frames"][:max_views], shapes):
+        n = np.load(os.path.join(normal_dir, os.path.basename(fr["file_path"]) + ".npy")).astype(np.float32)
+        if n.shape != tuple(hw) + (3,):
+            raise ValueError(f"{fr['file_path']}: normal target {n.shape} for a {tuple(hw)} image")
+        out.append(n)
     return out
 
 
@@ -271,9 +294,32 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets=No
     return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None), extra
 
 
+def normal_scores(P, cams, normal_targets, normal_rots, bg, alpha_min):
+    """{"train_normal_angle_deg_mean": the mean angle between the normals of the rendered depth (include/gsr_normals.h) and the targets
+    over the pixels where both exist, averaged over the views that have such pixels; "train_normal_valid_share": the share of pixels
+    with a valid depth normal, averaged over the views}."""
+    angles, shares = [], []
+    for c, t, R in zip(cams, normal_targets, normal_rots):
+        _, dep, buf = gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
+                                           rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
+                                           tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
+                                           sh=P["shs"], degree=3, campos=c["camera_center"])
+        n, valid = gsr.normals.normals_from_depth(dep.reshape(c["height"], c["width"]), buf["final_Ts"].reshape(c["height"], c["width"]), c, alpha_min)
+        th = t.reshape(c["height"], c["width"], 3).double()
+        if R is not None:
+            th = th @ torch.as_tensor(np.asarray(R, np.float64).T, device=th.device)
+        length = th.norm(dim=-1)
+        both = (valid > 0) & (length > 0)
+        shares.append(float(valid.mean().item()))
+        if bool(both.any()):
+            cos = ((n.double() * th).sum(-1)[both] / length[both]).clamp(-1.0, 1.0)
+            angles.append(float(torch.rad2deg(torch.acos(cos)).mean().item()))
+    return {"train_normal_angle_deg_mean": float(np.mean(angles)) if angles else None, "train_normal_valid_share": float(np.mean(shares))}
+
+
 def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
            alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None, weights=None, clean_targets=None,
-           clean_depth_targets=None, init_info=None):
+           clean_depth_targets=None, init_info=None, normal_targets=None, normal_rots=None):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
     P = model.params
@@ -306,6 +352,8 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
     summary.update(d_extra)
     if a_l1 is not None:
         summary["train_alpha_l1_mean"] = a_l1
+    if normal_targets is not None:                                          # --lambda-normal / --normal-dir / the hidden scene's own
+        summary.update(normal_scores(P, cams, normal_targets, normal_rots, bg, args.normal_alpha_min))
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
@@ -413,6 +461,18 @@ def main():
                     "file_path (without --dataset the hidden scene's own inverse depth is the target)")
     ap.add_argument("--lambda-alpha", type=float, default=0.0, help="weight of the L1 of the alpha image 1 - final_T against the PNG "
                     "alpha (or the hidden scene's)")
+    ap.add_argument("--lambda-normal", type=float, default=0.0, help="weight of the normal term: the cosine loss between the normals of "
+                    "the rendered depth and a normal prior (include/gsr_normals.h), normalised by W H as the depth term; its two "
+                    "gradient images are added to those of --lambda-depth and --lambda-alpha")
+    ap.add_argument("--normal-dir", default=None, help="with --dataset: one float32 (H, W, 3) normal .npy per frame, named after its "
+                    "file_path (without --dataset the normals of the hidden scene's own depth are the targets)")
+    ap.add_argument("--normal-space", default="camera", choices=["camera", "world"], help="the space of --normal-dir's vectors: camera "
+                    "(x right, y down, z forward; normals face the camera, z < 0) or world (turned by each view's rotation)")
+    ap.add_argument("--normal-noise", type=float, default=0.0, metavar="S", help="perturb every normal target once, at load: N(0, S^2) added to "
+                    "each component of every non-zero target vector (a noisy prior); the summary scores against the clean targets")
+    ap.add_argument("--normal-seed", type=int, default=0, help="seed of the normal perturbation")
+    ap.add_argument("--normal-alpha-min", type=float, default=0.5, help="a pixel has a depth normal where its own and its four neighbours' "
+                    "alpha is at least this")
     ap.add_argument("--optimize-poses", action="store_true", help="refine each view's pose with Adam on the camera gradients "
                     "(include/gsr_camera_grads.h; one GPU; reads 35 floats back per view and iteration)")
     ap.add_argument("--pose-lr", type=float, default=1e-3, help="Adam learning rate of the pose corrections xi = (translation, "
@@ -504,6 +564,16 @@ def main():
         raise SystemExit("--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0")
     if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
         raise SystemExit("--lambda-depth and --lambda-alpha must be >= 0")
+    if not (args.lambda_normal >= 0.0 and np.isfinite(args.lambda_normal)):
+        raise SystemExit("--lambda-normal must be >= 0 and finite")
+    if not (args.normal_noise >= 0.0 and np.isfinite(args.normal_noise)):
+        raise SystemExit("--normal-noise must be >= 0 and finite")
+    if not np.isfinite(args.normal_alpha_min):
+        raise SystemExit("--normal-alpha-min must be finite")
+    if args.normal_dir and not args.dataset:
+        raise SystemExit("--normal-dir needs --dataset (the targets are named after its frames)")
+    if args.lambda_normal > 0.0 and args.dataset and not args.normal_dir:
+        raise SystemExit("--lambda-normal with --dataset needs --normal-dir (normal targets)")
     if args.depth_loss == "pearson" and not args.lambda_depth > 0.0:
         raise SystemExit("--depth-loss pearson needs --lambda-depth > 0 (its weight)")
     if not (args.depth_noise >= 0.0 and np.isfinite(args.depth_noise)):
@@ -535,17 +605,23 @@ def main():
         rank, world = gsr.dist.init_from_env(backend=args.backend, device=dev)
 
     bg = np.zeros(3, np.float32)
-    depth_targets = alpha_targets = None
+    depth_targets = alpha_targets = normal_targets = None
     if args.dataset:
         cams, targets, alpha_targets, *dt = load_nerf(args.dataset, args.views, alpha=True, depth_dir=args.depth_dir)
         targets = [torch.as_tensor(t).to(dev) for t in targets]
         alpha_targets = [torch.as_tensor(t).to(dev) for t in alpha_targets]
         depth_targets = [torch.as_tensor(t).to(dev) for t in dt[0]] if dt else None
+        if args.normal_dir:
+            try:
+                normal_targets = [torch.as_tensor(t).to(dev) for t in
+                                  load_normals(args.dataset, args.normal_dir, args.views, [(c["height"], c["width"]) for c in cams])]
+            except (ValueError, OSError) as e:
+                raise SystemExit(f"--normal-dir: {e}") from None
     else:
         cams = [gsr.cameras.nerf_camera(gsr.scenes.orbit_pose(k, args.views), args.size, args.size, gsr.scenes.LEGO_CAMERA_ANGLE_X)
                 for k in range(args.views)]
         hidden = gsr.scenes.synthetic_scene(args.gaussians, 0.05, 0.5, seed=7)
-        targets, depth_targets, alpha_targets = [], [], []
+        targets, depth_targets, alpha_targets, normal_targets = [], [], [], []
         for c in cams:
             img, dep, hb = gsr.render_gaussians(**MODE_KW, background=bg, means3D=hidden["means"], opacity=hidden["opacities"], scales=hidden["scales"],
                                              rotations=hidden["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
@@ -554,6 +630,8 @@ def main():
             targets.append(img)
             depth_targets.append(dep.reshape(c["height"], c["width"]).clone())
             alpha_targets.append((1.0 - hb["final_Ts"].reshape(c["height"], c["width"])).contiguous())
+            normal_targets.append(gsr.normals.normals_from_depth(dep.reshape(c["height"], c["width"]), hb["final_Ts"].reshape(c["height"], c["width"]),
+                                                                 c, args.normal_alpha_min)[0])     # camera space; zero where it has none
     eval_scales = parse_eval_scales(args.eval_scales, cams[0]["width"], cams[0]["height"])
     if args.exposure_noise > 0.0:                                            # every target as a camera with that exposure error stored it
         noise = gsr.exposure.random_exposures(len(targets), args.exposure_noise, args.exposure_seed)
@@ -596,7 +674,14 @@ def main():
     clean_depth_targets = None
     if args.depth_noise > 0.0:                                              # every depth target as a relative depth source stored it
         clean_depth_targets, depth_targets = depth_targets, perturb_depth_targets(depth_targets, args.depth_noise, args.depth_seed)
-    aux = args.lambda_depth > 0.0 or args.lambda_alpha > 0.0
+    # the rotation that takes each view's normal targets to camera space (None: they are there already)
+    normal_rots = [c["R"] if args.dataset and args.normal_space == "world" else None for c in cams] if normal_targets is not None else None
+    clean_normal_targets = normal_targets
+    if args.normal_noise > 0.0 and normal_targets is not None:              # every normal target as a noisy prior stored it
+        gen = torch.Generator(device="cpu").manual_seed(args.normal_seed)
+        normal_targets = [torch.where((t != 0).any(-1, keepdim=True), t + args.normal_noise * torch.randn(t.shape, generator=gen).to(dev), t).contiguous()
+                          for t in normal_targets]
+    aux = args.lambda_depth > 0.0 or args.lambda_alpha > 0.0 or args.lambda_normal > 0.0
 
     n = args.gaussians
     if args.init == "reference":
@@ -714,6 +799,11 @@ def main():
                 aux_kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
             if args.lambda_alpha > 0.0:
                 aux_kw["dL_dalpha_image"] = gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], alpha_targets[v], None, args.lambda_alpha)[1]
+            if args.lambda_normal > 0.0:                                    # its two images are ADDED to the depth and alpha terms'
+                _, gD, gA = gsr.loss.normal_loss_and_gradients(dep.reshape(c["height"], c["width"]), buf["final_Ts"].reshape(c["height"], c["width"]),
+                                                               normal_targets[v], c, None, args.lambda_normal, normal_rots[v], args.normal_alpha_min)
+                aux_kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in aux_kw else aux_kw["dL_ddepth_image"].reshape(gD.shape) + gD
+                aux_kw["dL_dalpha_image"] = gA if "dL_dalpha_image" not in aux_kw else aux_kw["dL_dalpha_image"].reshape(gA.shape) + gA
             if expo is not None:                                            # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
                 dpix, dE = gsr.exposure.exposure_backward(raw, expo.matrix(v), dpix, out=dpix)
             if aux:                                                         # the forward's depths: records re-packed with 1/depth
@@ -862,7 +952,7 @@ def main():
                      "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets, init_info)
+               poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets, init_info, clean_normal_targets, normal_rots)
 
 
 if __name__ == "__main__":
