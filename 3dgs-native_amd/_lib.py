@@ -262,6 +262,34 @@ NORMALS_MAX_BLOCKS = 2048           # GSR_NORMALS_MAX_BLOCKS
 NORMALS_RECORD_BYTES = 16           # GSR_NORMALS_RECORD_BYTES
 NORMALS_SUMS_FLOATS = 2             # GSR_NORMALS_SUMS_FLOATS: (loss_sum, weight_sum)
 
+class GsrTsdfVolume(C.Structure):
+    _fields_ = [("Gx", C.c_int32), ("Gy", C.c_int32), ("Gz", C.c_int32), ("voxel_size", C.c_float), ("origin", C.c_float * 3), ("pad", C.c_int32),
+                ("tsdf", vp), ("weight", vp), ("color", vp)]
+
+
+class GsrTsdfView(C.Structure):
+    _fields_ = [("depth", vp), ("color", vp), ("view", C.c_float * 16), ("tan_fovx", C.c_float), ("tan_fovy", C.c_float), ("W", C.c_int32),
+                ("H", C.c_int32), ("w_obs", C.c_float), ("pad", C.c_int32)]   # 104 bytes
+
+
+# include/gsr_tsdf.h: TSDF fusion of depth images into a dense volume and marching-tetrahedra mesh extraction (its own header, so its
+# own table)
+TSDF_EXPORTS = {
+    "gsr_mesh_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "gsr_tsdf_reset": (C.c_int, [C.POINTER(GsrTsdfVolume), vp]),
+    "gsr_tsdf_integrate": (C.c_int, [C.POINTER(GsrTsdfVolume), C.c_int32, C.POINTER(GsrTsdfView), C.c_float, C.c_float, C.c_float, vp]),
+    "gsr_tsdf_depth": (C.c_int, [vp, vp, C.c_int32, C.c_int32, C.c_float, vp, vp]),
+    "gsr_mesh_count": (C.c_int, [C.POINTER(GsrTsdfVolume), C.c_float, vp, C.c_size_t, vp, vp]),
+    "gsr_mesh_emit": (C.c_int, [C.POINTER(GsrTsdfVolume), C.c_float, vp, C.c_size_t, C.c_int64, vp, vp, vp, vp]),
+}
+TSDF_MAX_DIM = 2048                 # GSR_TSDF_MAX_DIM
+TSDF_MAX_VOXELS = 1 << 31           # GSR_TSDF_MAX_VOXELS
+TSDF_MAX_SIDE = 1 << 24             # GSR_TSDF_MAX_SIDE
+TSDF_VIEWS_PER_LAUNCH = 16          # GSR_TSDF_VIEWS_PER_LAUNCH
+MESH_GROUP_CELLS = 256              # GSR_MESH_GROUP_CELLS
+MESH_SCAN_GROUPS = 1024             # GSR_MESH_SCAN_GROUPS
+MESH_DIRECTIONS = 7                 # GSR_MESH_DIRECTIONS
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -297,7 +325,8 @@ def lib():
                                   + list(FILTER3D_EXPORTS.items()) + list(EXPOSURE_EXPORTS.items())
                                   + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
                                   + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
-                                  + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())):
+                                  + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
+                                  + list(TSDF_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -215,3 +215,36 @@ def gaussians_from_points(xyz, rgb=None, opacity=0.1, device="cuda"):
     if rgb is not None:
         P["shs"].view(n, 16, 3)[:, 0, :] = torch.from_numpy((rgb - np.float32(0.5)) / np.float32(SH_C0)).to(dev)
     return P
+
+
+def save_mesh_ply(path, verts, faces, colors=None):
+    """An indexed triangle mesh (tsdf.weld's) as a binary little-endian PLY: `element vertex` with x y z (and uchar red green blue from
+    `colors` in [0, 1], when given), `element face` with `property list uchar int vertex_indices`: what MeshLab, Blender and Open3D
+    read."""
+    v = np.ascontiguousarray(np.asarray(verts, dtype=np.float32)).reshape(-1, 3)
+    f = np.ascontiguousarray(np.asarray(faces)).reshape(-1, 3)
+    if f.dtype.kind not in "iu" or (len(f) and (f.min() < 0 or f.max() >= len(v))):
+        raise ValueError("save_mesh_ply: faces must be integer indices into verts")
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if colors is not None:
+        c = np.asarray(colors, dtype=np.float32).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError(f"save_mesh_ply: colors must hold one row per vertex, not {len(c)} for {len(v)}")
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    vr = np.zeros(len(v), dtype=np.dtype(fields))
+    vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors is not None:
+        rgb = np.clip(np.nan_to_num(c) * np.float32(255), np.float32(0), np.float32(255)).astype(np.int64)
+        vr["red"], vr["green"], vr["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    fr = np.zeros(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    fr["n"], fr["i"] = 3, f
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {len(vr)}"]
+    lines += [f"property {_PLY_TYPE[t.lstrip('<')]} {name}" for name, t in fields]
+    lines += [f"element face {len(fr)}", "property list uchar int vertex_indices", "end_header"]
+    d = os.path.dirname(str(path))
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as out:
+        out.write(("\n".join(lines) + "\n").encode("ascii"))
+        vr.tofile(out)
+        fr.tofile(out)

@@ -69,6 +69,11 @@ the isotropic scale the original 3DGS starts with, the root of the mean squared 
 of the constant 0.1; --init-points FILE.ply starts from the points (and uchar colours) of a binary PLY the same way
 (point_cloud.gaussians_from_points) and takes the point count from the file.  The --log header records `init`, the smallest, median and
 largest initial scale, and `first_iteration_pairs`, the (tile, Gaussian) pair count D of the run's first frame.
+
+A mesh of the result (include/gsr_tsdf.h, tsdf.py): --mesh-out FILE.ply renders depth and colour from the training views after the
+last iteration, fuses them into a TSDF volume of --mesh-resolution voxels per side (default 256) and writes the marching-tetrahedra
+mesh of the cells observed with weight --mesh-min-weight; the function examples/extract_mesh.py runs on a checkpoint.  Off by
+default; nothing changes when it is off.
 """
 import argparse
 import importlib
@@ -473,6 +478,11 @@ def main():
     ap.add_argument("--normal-seed", type=int, default=0, help="seed of the normal perturbation")
     ap.add_argument("--normal-alpha-min", type=float, default=0.5, help="a pixel has a depth normal where its own and its four neighbours' "
                     "alpha is at least this")
+    ap.add_argument("--mesh-out", default=None, metavar="FILE", help="after the last iteration, fuse depth and colour renders of the training "
+                    "views into a TSDF volume and write the extracted triangle mesh (include/gsr_tsdf.h; what examples/extract_mesh.py does). "
+                    "Off by default; training itself is unchanged")
+    ap.add_argument("--mesh-resolution", type=int, default=256, metavar="R", help="voxels per side of --mesh-out's volume")
+    ap.add_argument("--mesh-min-weight", type=float, default=1.0, metavar="K", help="--mesh-out keeps cells whose corners all have weight K")
     ap.add_argument("--optimize-poses", action="store_true", help="refine each view's pose with Adam on the camera gradients "
                     "(include/gsr_camera_grads.h; one GPU; reads 35 floats back per view and iteration)")
     ap.add_argument("--pose-lr", type=float, default=1e-3, help="Adam learning rate of the pose corrections xi = (translation, "
@@ -564,6 +574,10 @@ def main():
         raise SystemExit("--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0")
     if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
         raise SystemExit("--lambda-depth and --lambda-alpha must be >= 0")
+    if args.mesh_out and not 2 <= args.mesh_resolution <= 2048:
+        raise SystemExit("--mesh-resolution must be in 2 .. 2048")
+    if args.mesh_out and not args.mesh_min_weight > 0.0:
+        raise SystemExit("--mesh-min-weight must be positive")
     if not (args.lambda_normal >= 0.0 and np.isfinite(args.lambda_normal)):
         raise SystemExit("--lambda-normal must be >= 0 and finite")
     if not (args.normal_noise >= 0.0 and np.isfinite(args.normal_noise)):
@@ -953,6 +967,10 @@ def main():
                      "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
         finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
                poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets, init_info, clean_normal_targets, normal_rots)
+        if args.mesh_out:                                                   # the model's surface from its training views (extract_mesh.py)
+            from extract_mesh import mesh_from_model
+            mesh_from_model(gsr, model.params, cams, args.mesh_out, bg=bg, mode_kw=MODE_KW, resolution=args.mesh_resolution,
+                            min_weight=args.mesh_min_weight, alpha_min=args.normal_alpha_min)
 
 
 if __name__ == "__main__":
