@@ -318,3 +318,17 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         if filt is not None:
             _filter3d.filter_3d_backward(*_filter3d.raw_inputs(filt, raw_scales, raw_opacity, dev, N), filter_3d, out.dL_dscale, out.dL_dopacity)
     return _result(out, N, dev, dcam, aux, absgrad)
+
+
+def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
+    """backward() of a frame forward.render_view() drew: `buffers` is the dict it returned, regrouped here into the reference's
+    arguments (points_xy_image -> means2D, colors -> rgb, clamped_state -> clamped, binning_buffer, img_buffer) -- the key names
+    of three dicts, nothing else; the tensors go through as they are.  **kw: sh_gradient, camera_grad, absgrad, dL_ddepth_image,
+    dL_dalpha_image, geom_buffer, rasterize_mode, filter_3d."""
+    return backward(background=background, means3D=params["positions"], dL_dpixels=dL_dpixels, opacity=params["opacities"],
+                    shs=params["shs"], scales=params["scales"], rotations=params["rotations"], viewmatrix=camera["world_to_camera"],
+                    projmatrix=camera["full_proj_matrix"], tan_fovx=camera["tan_fovx"], tan_fovy=camera["tan_fovy"],
+                    image_height=camera["height"], image_width=camera["width"], campos=camera["camera_center"], radii=buffers["radii"],
+                    means2D=buffers["points_xy_image"], conic_opacity=buffers["conic_opacity"], rgb=buffers["colors"],
+                    cov3Ds=buffers["cov3Ds"], clamped=buffers["clamped_state"], binning_buffer={"point_list": buffers["point_list"]},
+                    img_buffer={"ranges": buffers["ranges"], "final_Ts": buffers["final_Ts"], "n_contrib": buffers["n_contrib"]}, **kw)

@@ -7,6 +7,7 @@ reference's inputs bit-for-meaning:
 
 * `nerf_camera`  -- NeRF-synthetic `transform_matrix` -> the dict train.py feeds to the rasterizer
                     (reference utils/camera_utils.py:8-89; utils/math_utils.py:8-41).
+* `nerf_frames`  -- the frames of a NeRF-synthetic transforms_<split>.json, for every loader that walks one.
 * `load_camera` / `world_to_view` / `projection_matrix` / `matrix_to_quaternion`
                  -- the reference's own helper names (utils/camera_utils.py:8-106, utils/math_utils.py:8-95) over the
                     same math, for callers written against them.
@@ -14,7 +15,9 @@ reference's inputs bit-for-meaning:
                     its quirk of passing the un-transposed `world_to_view` matrix as the view matrix
                      and degrees-as-radians FoV (tan(22.5 rad)).
 """
+import json
 import math
+import os
 
 import numpy as np
 
@@ -65,6 +68,16 @@ def nerf_camera(transform_matrix, width, height, camera_angle_x, znear=0.01, zfa
         "camera_center": np.linalg.inv(world_to_camera)[3, :3],
         "width": int(width), "height": int(height), "fx": focal, "fy": focal,
     }
+
+
+def nerf_frames(path, max_views=None, split="train"):
+    """(camera_angle_x, frames) of a NeRF-synthetic directory's transforms_<split>.json: the first `max_views` frames (None:
+    all), each as (file_path as the file writes it, the path of its PNG, the base name its per-frame side files carry -- depth,
+    normal and mask targets --, transform_matrix)."""
+    with open(os.path.join(path, f"transforms_{split}.json")) as f:
+        tf = json.load(f)
+    return tf["camera_angle_x"], [(fr["file_path"], os.path.join(path, fr["file_path"] + ".png"), os.path.basename(fr["file_path"]),
+                                   fr["transform_matrix"]) for fr in tf["frames"][:max_views]]
 
 
 def toy_camera(image_width=1800, image_height=1800, fovx=45.0, fovy=45.0, znear=0.01, zfar=100.0):

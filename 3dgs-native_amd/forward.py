@@ -153,6 +153,16 @@ def render_gaussians(background, means3D, colors=None, opacity=None, scales=None
     }
 
 
+def render_view(params, camera, background, **kw):
+    """render_gaussians() of a trainer's parameter dict (positions, scales, rotations, opacities, shs) from a cameras.nerf_camera
+    dict at SH degree 3: the key names of the two dicts, nothing else.  The tensors go through as they are (the frame's tags ride
+    on them); **kw is render_gaussians' keyword-only part (rasterize_mode, filter_3d, capacity, capacity_hint)."""
+    return render_gaussians(background=background, means3D=params["positions"], opacity=params["opacities"], scales=params["scales"],
+                            rotations=params["rotations"], viewmatrix=camera["world_to_camera"], projmatrix=camera["full_proj_matrix"],
+                            tan_fovx=camera["tan_fovx"], tan_fovy=camera["tan_fovy"], image_height=camera["height"],
+                            image_width=camera["width"], sh=params["shs"], degree=3, campos=camera["camera_center"], **kw)
+
+
 def _check_capacity(capacity, hint):
     """Capacity-mode arguments, checked before anything touches the GPU."""
     out = []

@@ -26,12 +26,10 @@ import numpy as np  # noqa: E402
 def load_cameras(gsr, path, max_views, split="train"):
     """The dataset's cameras (NeRF-synthetic transforms_<split>.json); the image size is the first frame's."""
     from PIL import Image
-    with open(os.path.join(path, f"transforms_{split}.json")) as f:
-        tf = json.load(f)
-    frames = tf["frames"][:max_views] if max_views else tf["frames"]
-    with Image.open(os.path.join(path, frames[0]["file_path"] + ".png")) as im:
+    angle, frames = gsr.cameras.nerf_frames(path, max_views or None, split)
+    with Image.open(frames[0][1]) as im:
         W, H = im.size
-    return [gsr.cameras.nerf_camera(fr["transform_matrix"], W, H, tf["camera_angle_x"]) for fr in frames]
+    return [gsr.cameras.nerf_camera(pose, W, H, angle) for _, _, _, pose in frames]
 
 
 def mesh_from_model(gsr, P, cams, out, bg=None, mode_kw=None, log=print, **fuse):
@@ -41,10 +39,7 @@ def mesh_from_model(gsr, P, cams, out, bg=None, mode_kw=None, log=print, **fuse)
     bg = np.zeros(3, np.float32) if bg is None else bg
 
     def render(c):
-        return gsr.render_gaussians(**(mode_kw or {}), background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
-                                    rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
-                                    tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"], sh=P["shs"],
-                                    degree=3, campos=c["camera_center"])
+        return gsr.render_view(P, c, bg, **(mode_kw or {}))
     t0 = time.perf_counter()
     verts, faces, cols, info = gsr.tsdf.fuse_views(render, cams, **fuse)
     torch.cuda.synchronize()

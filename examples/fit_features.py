@@ -66,17 +66,14 @@ def main(argv=None):
     sc = gsr.scenes.synthetic_scene(a.gaussians, 0.05, 0.6, a.seed)
     N = sc["means"].shape[0]
     tens = {k: torch.as_tensor(np.ascontiguousarray(v, dtype=np.float32), device=dev) for k, v in sc.items()}
+    P = {"positions": tens["means"], "scales": tens["scales"], "rotations": tens["rotations"], "opacities": tens["opacities"],
+         "shs": tens["shs"].reshape(-1, 3)}
     labels = (sc["means"][:, 0] > 0).astype(np.int64) + 2 * (sc["means"][:, 1] > 0) + 4 * (sc["means"][:, 2] > 0)
     hidden = torch.nn.functional.one_hot(torch.as_tensor(labels, device=dev), N_CLASSES).to(torch.float32).contiguous()
 
     def frame(k):
         cam = gsr.cameras.nerf_camera(gsr.scenes.orbit_pose(k, N_VIEWS), S, S, gsr.scenes.LEGO_CAMERA_ANGLE_X)
-        _, _, buf = gsr.render_gaussians(
-            background=np.zeros(3, np.float32), means3D=tens["means"], colors=None, opacity=tens["opacities"], scales=tens["scales"],
-            rotations=tens["rotations"], scale_modifier=1.0, viewmatrix=cam["world_to_camera"], projmatrix=cam["full_proj_matrix"],
-            tan_fovx=cam["tan_fovx"], tan_fovy=cam["tan_fovy"], image_height=S, image_width=S, sh=tens["shs"].reshape(-1, 3), degree=3,
-            campos=cam["camera_center"], prefiltered=False, antialiasing=False, clamped=True)
-        return buf
+        return gsr.render_view(P, cam, np.zeros(3, np.float32))[2]
 
     frames = [frame(k) for k in range(N_VIEWS)]                                  # the frozen geometry: drawn once per view
     targets = [feat.render_features(hidden, b, S, S) for b in frames]

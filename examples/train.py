@@ -88,6 +88,19 @@ sys.path.insert(0, ROOT)
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 
+# flags whose state one rank owns: refused before the ranks start (_self_launch) and again, with the world size known, in check_args
+ONE_GPU_ONLY = {
+    "optimize_poses": "--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus",
+    "optimize_exposure": "--optimize-exposure trains on one GPU only (per-rank exposure ownership is not implemented): drop --gpus"}
+
+
+def refuse(rules):
+    """rules: (violated, message) in the order that decides which message a doubly wrong command line gets"""
+    for violated, message in rules:
+        if violated:
+            raise SystemExit(message)
+
+
 def _self_launch():
     """`python examples/train.py --gpus N` (no WORLD_SIZE): start the N ranks before anything here touches the GPU."""
     ap = argparse.ArgumentParser(add_help=False)
@@ -96,10 +109,7 @@ def _self_launch():
     ap.add_argument("--optimize-exposure", action="store_true")
     known = ap.parse_known_args()[0]
     gpus = known.gpus
-    if known.optimize_exposure and gpus > 1:
-        raise SystemExit("--optimize-exposure trains on one GPU only (per-rank exposure ownership is not implemented): drop --gpus")
-    if known.optimize_poses and gpus > 1:
-        raise SystemExit("--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus")
+    refuse((gpus > 1 and getattr(known, flag), ONE_GPU_ONLY[flag]) for flag in ("optimize_exposure", "optimize_poses"))
     if gpus > 1 and "WORLD_SIZE" not in os.environ:
         from importlib import util as _ilu
         spec = _ilu.spec_from_file_location("gsr_launch", os.path.join(ROOT, "3dgs-native_amd", "launch.py"))
@@ -112,6 +122,9 @@ def _self_launch():
 if __name__ == "__main__":
     _self_launch()
 
+import time  # noqa: E402
+from types import SimpleNamespace  # noqa: E402
+
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
@@ -122,19 +135,18 @@ def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
     """(cams, targets), and with alpha=True also the PNGs' alpha channels / 255 as (H, W) float32 (ones for a PNG without one);
     with depth_dir also the inverse-depth targets, <depth_dir>/<basename of file_path>.npy."""
     from PIL import Image
-    with open(os.path.join(path, f"transforms_{split}.json")) as f:
-        tf = json.load(f)
+    angle, frames = gsr.cameras.nerf_frames(path, max_views, split)
     cams, targets, alphas, depths = [], [], [], []
-    for fr in tf["frames"][:max_views]:
-        img = np.asarray(Image.open(os.path.join(path, fr["file_path"] + ".png")), dtype=np.float32) / 255.0
+    for file_path, png, name, pose in frames:
+        img = np.asarray(Image.open(png), dtype=np.float32) / 255.0
         targets.append(img[:, :, :3].copy())
         alphas.append(img[:, :, 3].copy() if img.ndim == 3 and img.shape[2] == 4 else np.ones(img.shape[:2], np.float32))
         if depth_dir is not None:
-            d = np.load(os.path.join(depth_dir, os.path.basename(fr["file_path"]) + ".npy")).astype(np.float32)
+            d = np.load(os.path.join(depth_dir, name + ".npy")).astype(np.float32)
             if d.shape != img.shape[:2]:
-                raise ValueError(f"{fr['file_path']}: depth target {d.shape} for a {img.shape[:2]} image")
+                raise ValueError(f"{file_path}: depth target {d.shape} for a {img.shape[:2]} image")
             depths.append(d)
-        cams.append(gsr.cameras.nerf_camera(fr["transform_matrix"], img.shape[1], img.shape[0], tf["camera_angle_x"]))
+        cams.append(gsr.cameras.nerf_camera(pose, img.shape[1], img.shape[0], angle))
     out = (cams, targets) + ((alphas,) if alpha else ()) + ((depths,) if depth_dir is not None else ())
     return out
 
@@ -142,13 +154,11 @@ def load_nerf(path, max_views, split="train", alpha=False, depth_dir=None):
 def load_normals(path, normal_dir, max_views, shapes, split="train"):
     """The normal targets of --normal-dir: <normal_dir>/<basename of file_path>.npy per frame, float32 (H, W, 3), any length (a zero
     vector: the pixel has no target)."""
-    with open(os.path.join(path, f"transforms_{split}.json")) as f:
-        tf = json.load(f)
     out = []
-    for fr, hw in zip(tf["frames"][:max_views], shapes):
-        n = np.load(os.path.join(normal_dir, os.path.basename(fr["file_path"]) + ".npy")).astype(np.float32)
+    for (file_path, _, name, _), hw in zip(gsr.cameras.nerf_frames(path, max_views, split)[1], shapes):
+        n = np.load(os.path.join(normal_dir, name + ".npy")).astype(np.float32)
         if n.shape != tuple(hw) + (3,):
-            raise ValueError(f"{fr['file_path']}: normal target {n.shape} for a {tuple(hw)} image")
+            raise ValueError(f"{file_path}: normal target {n.shape} for a {tuple(hw)} image")
         out.append(n)
     return out
 
@@ -157,14 +167,12 @@ def load_masks(path, mask_dir, max_views, shapes, split="train"):
     """The weight images of --mask-dir: <mask_dir>/<basename of file_path>.png per frame, first channel / 255, (H, W) float32; its
     shape must be its image's."""
     from PIL import Image
-    with open(os.path.join(path, f"transforms_{split}.json")) as f:
-        tf = json.load(f)
     masks = []
-    for fr, shape in zip(tf["frames"][:max_views], shapes):
-        png = np.asarray(Image.open(os.path.join(mask_dir, os.path.basename(fr["file_path"]) + ".png")))
+    for (file_path, _, name, _), shape in zip(gsr.cameras.nerf_frames(path, max_views, split)[1], shapes):
+        png = np.asarray(Image.open(os.path.join(mask_dir, name + ".png")))
         m = (png if png.ndim == 2 else png[:, :, 0]).astype(np.float32) / 255.0
         if m.shape != tuple(shape):
-            raise ValueError(f"{fr['file_path']}: mask {m.shape} for a {tuple(shape)} image")
+            raise ValueError(f"{file_path}: mask {m.shape} for a {tuple(shape)} image")
         masks.append(np.ascontiguousarray(m))
     return masks
 
@@ -193,8 +201,10 @@ def paste_occluders(target, rects):
     return out, mask
 
 
-MODE_KW = {}     # --rasterize-mode antialiased: {"rasterize_mode": "antialiased"} for every render and backward of the run;
-                 # --filter-3d: also {"filter_3d": the current filter}, replaced at every recomputation
+def mode_keywords(args):
+    """What every render and backward of a run is given beside its view (run.mode_kw): --rasterize-mode antialiased's keyword;
+    --filter-3d adds {"filter_3d": the current filter} at every recompute_filter()."""
+    return {"rasterize_mode": args.rasterize_mode} if args.rasterize_mode != "classic" else {}
 
 
 def parse_eval_scales(text, W, H):
@@ -211,30 +221,33 @@ def parse_eval_scales(text, W, H):
     return scales
 
 
-def score_scales(P, cams, targets, bg, scales, exposure=None):
+def row_mean(rows, key):
+    return float(np.mean([r[key] for r in rows]))
+
+
+def row_means(rows, prefix):
+    """{"<prefix>_l1_mean", "<prefix>_psnr_mean", "<prefix>_ssim_mean"} of score_views' rows"""
+    return {f"{prefix}_{k}_mean": row_mean(rows, k) for k in ("l1", "psnr", "ssim")}
+
+
+def score_scales(P, cams, targets, bg, mode_kw, scales, exposure=None):
     """{s: {"psnr", "ssim"}}: every view also rendered at W/s x H/s with the same field of view, against its target box-averaged by
     s x s (what a camera s times as far away, or a zoom-out by s, would record)."""
     out = {}
     for sc in scales:
         small = [dict(c, width=c["width"] // sc, height=c["height"] // sc) for c in cams]
         tg = [t.reshape(c["height"] // sc, sc, c["width"] // sc, sc, 3).mean((1, 3)).contiguous() for c, t in zip(cams, targets)]
-        rows, _ = score_views(P, small, tg, bg, exposure)
-        out[str(sc)] = {"psnr": float(np.mean([r["psnr"] for r in rows])), "ssim": float(np.mean([r["ssim"] for r in rows]))}
+        rows, _ = score_views(P, small, tg, bg, mode_kw, exposure)
+        out[str(sc)] = {"psnr": row_mean(rows, "psnr"), "ssim": row_mean(rows, "ssim")}
     return out
 
 
-def render_view(P, c, bg):
-    return gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
-                                viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"], tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"],
-                                image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"])[0]
-
-
-def score_views(P, cams, targets, bg, exposure=None):
+def score_views(P, cams, targets, bg, mode_kw, exposure=None):
     """Per-view mean L1, PSNR (10 log10(1 / MSE), colours in [0, 1]) and SSIM (gaussian window, gsr_loss.h) of the current model;
     the images come back too.  `exposure` (an ExposureModel whose rows are these views): view k is scored through its E_k."""
     rows, images = [], []
     for k, (c, t) in enumerate(zip(cams, targets)):
-        img = render_view(P, c, bg).reshape(t.shape)
+        img = gsr.render_view(P, c, bg, **mode_kw)[0].reshape(t.shape)
         if exposure is not None:
             img = gsr.exposure.apply_exposure(img, exposure.matrix(k), out=img)
         d = img - t
@@ -268,7 +281,7 @@ def perturb_depth_targets(depth_targets, noise, seed):
     return out
 
 
-def aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets=None):
+def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None):
     """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets.
     Third: with depth targets, {"train_depth_corr_mean": the mean Pearson correlation rho of the rendered inverse depth with the
     targets as given, "train_depth_fit": each view's (s, b) of render ~ s target + b (include/gsr_depth_corr.h)}, and with
@@ -276,10 +289,7 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets=No
     dl, al, dc = [], [], []
     fits = torch.zeros((len(cams), 4), device=P["positions"].device) if depth_targets is not None else None
     for k, c in enumerate(cams):
-        _, dep, buf = gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
-                                           rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
-                                           tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
-                                           sh=P["shs"], degree=3, campos=c["camera_center"])
+        _, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
         if depth_targets is not None:
             t = depth_targets[k]
             dl.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
@@ -299,16 +309,13 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets=No
     return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None), extra
 
 
-def normal_scores(P, cams, normal_targets, normal_rots, bg, alpha_min):
+def normal_scores(P, cams, normal_targets, normal_rots, bg, mode_kw, alpha_min):
     """{"train_normal_angle_deg_mean": the mean angle between the normals of the rendered depth (include/gsr_normals.h) and the targets
     over the pixels where both exist, averaged over the views that have such pixels; "train_normal_valid_share": the share of pixels
     with a valid depth normal, averaged over the views}."""
     angles, shares = [], []
     for c, t, R in zip(cams, normal_targets, normal_rots):
-        _, dep, buf = gsr.render_gaussians(**MODE_KW, background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"],
-                                           rotations=P["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
-                                           tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
-                                           sh=P["shs"], degree=3, campos=c["camera_center"])
+        _, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
         n, valid = gsr.normals.normals_from_depth(dep.reshape(c["height"], c["width"]), buf["final_Ts"].reshape(c["height"], c["width"]), c, alpha_min)
         th = t.reshape(c["height"], c["width"], 3).double()
         if R is not None:
@@ -322,55 +329,58 @@ def normal_scores(P, cams, normal_targets, normal_rots, bg, alpha_min):
     return {"train_normal_angle_deg_mean": float(np.mean(angles)) if angles else None, "train_normal_valid_share": float(np.mean(shares))}
 
 
-def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log=(), ssim_hist=None, depth_targets=None,
-           alpha_targets=None, poses=None, filter_log=(), eval_scales=(), exposure=None, weights=None, clean_targets=None,
-           clean_depth_targets=None, init_info=None, normal_targets=None, normal_rots=None):
+def pose_errors(run):
+    """--pose-noise-* / --optimize-poses: every view's error against the dataset poses (degrees, scene units) at the start and now"""
+    V = run.views
+    e0, e1 = ([gsr.pose.pose_error(c, t) for c, t in zip(cams, V.true_cams)] for cams in (V.start_cams, V.cams))
+    return {"pose_error_start": {"rot_deg": [r for r, _ in e0], "trans": [t for _, t in e0]},
+            "pose_error_final": {"rot_deg": [r for r, _ in e1], "trans": [t for _, t in e1]},
+            "pose_rot_deg_mean_start": row_mean(e0, 0), "pose_trans_mean_start": row_mean(e0, 1),
+            "pose_rot_deg_mean_final": row_mean(e1, 0), "pose_trans_mean_final": row_mean(e1, 1)}
+
+
+def finish(run, wall):
     """The run record: parameters finite, loss curve, point count after every density-control call, timing, per-view scores, PNGs."""
     from PIL import Image
-    P = model.params
+    args, V, model, bg, mode_kw, expo = run.args, run.views, run.model, run.bg, run.mode_kw, run.expo
+    P, cams, targets = model.params, V.cams, V.targets
     finite = {k: bool(torch.isfinite(P[k]).all().item()) for k in gsr.optimizer.GROUPS}
-    rows, images = score_views(P, cams, targets, bg, exposure)
+    rows, images = score_views(P, cams, targets, bg, mode_kw, expo)
     summary = {"iterations": args.iterations, "wall_s": round(wall, 3), "iterations_per_s": round(args.iterations / wall, 1) if wall > 0 else None,
-               "points_start": density_log[0]["points"], "points_final": model.num_points, "density_control_calls": len(density_log) - 1,
-               "parameters_finite": finite, "train_views": rows, "train_l1_mean": float(np.mean([r["l1"] for r in rows])),
-               "train_psnr_mean": float(np.mean([r["psnr"] for r in rows])), "train_ssim_mean": float(np.mean([r["ssim"] for r in rows]))}
+               "points_start": run.density_log[0]["points"], "points_final": model.num_points, "density_control_calls": len(run.density_log) - 1,
+               "parameters_finite": finite, "train_views": rows, **row_means(rows, "train")}
     if args.capacity:
-        summary["capacity_retries"] = len(capacity_log)
-    if weights is not None:                                                 # the same three scores under each view's weights
-        wrows = [weighted_scores(img, t.reshape(img.shape), w) for img, t, w in zip(images, targets, weights)]
-        summary.update({"train_views_weighted": wrows, "train_weighted_l1_mean": float(np.mean([r["l1"] for r in wrows])),
-                        "train_weighted_psnr_mean": float(np.mean([r["psnr"] for r in wrows])),
-                        "train_weighted_ssim_mean": float(np.mean([r["ssim"] for r in wrows]))})
-    if clean_targets is not None:                                           # --occluders: against the targets before the rectangles
-        crows, _ = score_views(P, cams, clean_targets, bg, exposure)
-        summary.update({"clean_views": crows, "clean_l1_mean": float(np.mean([r["l1"] for r in crows])),
-                        "clean_psnr_mean": float(np.mean([r["psnr"] for r in crows])), "clean_ssim_mean": float(np.mean([r["ssim"] for r in crows]))})
-    if poses is not None:                                                   # --pose-noise-* / --optimize-poses: error vs the dataset poses
-        summary.update(poses)
-    if exposure is not None:                                                # --optimize-exposure: which rows went through a matrix, and the matrices
+        summary["capacity_retries"] = len(run.capacity_log)
+    if V.weights is not None:                                               # the same three scores under each view's weights
+        wrows = [weighted_scores(img, t.reshape(img.shape), w) for img, t, w in zip(images, targets, V.weights)]
+        summary.update({"train_views_weighted": wrows, **row_means(wrows, "train_weighted")})
+    if V.clean_targets is not None:                                         # --occluders: against the targets before the rectangles
+        crows, _ = score_views(P, cams, V.clean_targets, bg, mode_kw, expo)
+        summary.update({"clean_views": crows, **row_means(crows, "clean")})
+    if V.true_cams is not V.start_cams or args.optimize_poses:
+        summary.update(pose_errors(run))
+    if expo is not None:                                                    # --optimize-exposure: which rows went through a matrix, and the matrices
         summary["exposure_applied"] = {"train_views": True, "train_eval_scales": True, "holdout_views": False, "holdout_eval_scales": False}
-        summary["exposure_final"] = exposure.state_dict()["E"]
-        summary["exposure_steps"] = list(exposure.steps)
-    d_l1, a_l1, d_extra = aux_scores(P, cams, depth_targets, alpha_targets, bg, clean_depth_targets)
+        summary["exposure_final"] = expo.state_dict()["E"]
+        summary["exposure_steps"] = list(expo.steps)
+    d_l1, a_l1, d_extra = aux_scores(P, cams, V.depth_targets, V.alpha_targets, bg, mode_kw, V.clean_depth_targets)
     if d_l1 is not None:
         summary["train_depth_l1_mean"] = d_l1
     summary.update(d_extra)
     if a_l1 is not None:
         summary["train_alpha_l1_mean"] = a_l1
-    if normal_targets is not None:                                          # --lambda-normal / --normal-dir / the hidden scene's own
-        summary.update(normal_scores(P, cams, normal_targets, normal_rots, bg, args.normal_alpha_min))
+    if V.clean_normal_targets is not None:                                  # --lambda-normal / --normal-dir / the hidden scene's own
+        summary.update(normal_scores(P, cams, V.clean_normal_targets, V.normal_rots, bg, mode_kw, args.normal_alpha_min))
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
-        ht = [torch.as_tensor(t).to(dev) for t in ht]
-        hrows, _ = score_views(P, hc, ht, bg)
-        if eval_scales:
-            summary["holdout_eval_scales"] = score_scales(P, hc, ht, bg, eval_scales)
-        summary.update({"holdout": args.holdout, "holdout_views": hrows, "holdout_l1_mean": float(np.mean([r["l1"] for r in hrows])),
-                        "holdout_psnr_mean": float(np.mean([r["psnr"] for r in hrows])),
-                        "holdout_ssim_mean": float(np.mean([r["ssim"] for r in hrows]))})
-    if eval_scales:
-        summary["train_eval_scales"] = score_scales(P, cams, targets, bg, eval_scales, exposure)
+        ht = [torch.as_tensor(t).to(run.dev) for t in ht]
+        hrows, _ = score_views(P, hc, ht, bg, mode_kw)
+        if V.eval_scales:
+            summary["holdout_eval_scales"] = score_scales(P, hc, ht, bg, mode_kw, V.eval_scales)
+        summary.update({"holdout": args.holdout, "holdout_views": hrows, **row_means(hrows, "holdout")})
+    if V.eval_scales:
+        summary["train_eval_scales"] = score_scales(P, cams, targets, bg, mode_kw, V.eval_scales, expo)
         for name in ("train_eval_scales", "holdout_eval_scales"):
             if name in summary:
                 print(name + ": " + "; ".join(f"1/{k}: PSNR {v['psnr']:.2f} dB SSIM {v['ssim']:.4f}" for k, v in summary[name].items()), flush=True)
@@ -380,16 +390,13 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
           + f"; parameters finite: {all(finite.values())}", flush=True)
     if args.log:
         os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
-        curve = loss_hist[:args.iterations].cpu().numpy()
-        scurve = ssim_hist[:args.iterations].cpu().numpy() if ssim_hist is not None else None
+        curve = run.loss_hist[:args.iterations].cpu().numpy()
+        scurve = run.ssim_hist[:args.iterations].cpu().numpy() if run.ssim_hist is not None else None
         with open(args.log, "w") as f:
-            f.write(json.dumps({"record": "arguments", **{k: v for k, v in vars(args).items()}, **(init_info or {})}) + "\n")
-            for d in density_log:
-                f.write(json.dumps({"record": "density_control", **d}) + "\n")
-            for d in capacity_log:
-                f.write(json.dumps({"record": "capacity_retry", **d}) + "\n")
-            for d in filter_log:
-                f.write(json.dumps({"record": "filter_3d", **d}) + "\n")
+            f.write(json.dumps({"record": "arguments", **{k: v for k, v in vars(args).items()}, **run.init_info}) + "\n")
+            for kind, log in (("density_control", run.density_log), ("capacity_retry", run.capacity_log), ("filter_3d", run.filter_log)):
+                for d in log:
+                    f.write(json.dumps({"record": kind, **d}) + "\n")
             for i in range(0, len(curve), 100):               # every iteration's loss, 100 per line
                 rec = {"record": "loss", "from_iteration": i, "l1": [round(float(x), 6) for x in curve[i:i + 100]]}
                 if scurve is not None:                        # --lambda-dssim > 0: the mean SSIM of the same iterations
@@ -406,7 +413,7 @@ def finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, ca
             Image.fromarray(np.concatenate([r8, t8], axis=1)).save(os.path.join(args.eval_dir, f"pair_{k}.png"))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1, help="ranks (one per GPU); > 1 without WORLD_SIZE launches them itself")
     ap.add_argument("--dataset", default=None)
@@ -534,7 +541,13 @@ def main():
     ap.add_argument("--occluder-seed", type=int, default=0, help="seed of the rectangles")
     ap.add_argument("--occluder-size", type=float, default=0.25, metavar="F", help="largest side of a rectangle, as a fraction of the image's")
     ap.add_argument("--mask-occluders", action="store_true", help="train with the masks of exactly those rectangles (dilated by --mask-dilate)")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def check_args(args):
+    """Every refusal that needs no data, before anything touches the GPU, in the order that decides which message a doubly wrong
+    command line gets.  --init-points is read here, where its refusals stand: returns its (points, colours) or None, and settles
+    args.init and args.gaussians."""
     if args.init_points and args.init in ("reference", "random"):
         raise SystemExit(f"--init-points starts from the file's points: it cannot be combined with --init {args.init}")
     init_cloud = None
@@ -548,77 +561,70 @@ def main():
         print(f"--init-points: {len(init_cloud[0])} points from {args.init_points} (--gaussians {args.gaussians} is overridden)", flush=True)
         args.gaussians, args.init = len(init_cloud[0]), "points"
     args.init = args.init or "reference"
-    if args.mask_dilate < 0 or args.occluders < 0 or not 0.0 < args.occluder_size <= 1.0:
-        raise SystemExit("--mask-dilate and --occluders must be >= 0, --occluder-size in (0, 1]")
-    if args.mask_dir and not args.dataset:
-        raise SystemExit("--mask-dir needs --dataset (the masks are named after its frames)")
-    if args.mask_occluders and args.occluders == 0:
-        raise SystemExit("--mask-occluders needs --occluders K")
-    if not (args.exposure_lr_init > 0.0 and args.exposure_lr_final > 0.0 and np.isfinite(args.exposure_lr_init + args.exposure_lr_final)):
-        raise SystemExit("--exposure-lr-init and --exposure-lr-final must be positive and finite")
-    if not (args.exposure_noise >= 0.0 and np.isfinite(args.exposure_noise)):
-        raise SystemExit("--exposure-noise must be >= 0 and finite")
-    if args.optimize_exposure and args.capacity:
-        raise SystemExit("--optimize-exposure does not combine with --capacity (an overflowed frame's exposure step would have to be undone): drop one")
-    if not (args.filter_3d_variance > 0.0 and np.isfinite(args.filter_3d_variance)) or args.filter_3d_interval < 1:
-        raise SystemExit("--filter-3d-variance must be positive and finite, --filter-3d-interval >= 1")
+    finite = lambda *xs: bool(np.isfinite(sum(xs)))
+    refuse([
+        (args.mask_dilate < 0 or args.occluders < 0 or not 0.0 < args.occluder_size <= 1.0,
+         "--mask-dilate and --occluders must be >= 0, --occluder-size in (0, 1]"),
+        (args.mask_dir and not args.dataset, "--mask-dir needs --dataset (the masks are named after its frames)"),
+        (args.mask_occluders and args.occluders == 0, "--mask-occluders needs --occluders K"),
+        (not (args.exposure_lr_init > 0.0 and args.exposure_lr_final > 0.0 and finite(args.exposure_lr_init, args.exposure_lr_final)),
+         "--exposure-lr-init and --exposure-lr-final must be positive and finite"),
+        (not (args.exposure_noise >= 0.0 and finite(args.exposure_noise)), "--exposure-noise must be >= 0 and finite"),
+        (args.optimize_exposure and args.capacity,
+         "--optimize-exposure does not combine with --capacity (an overflowed frame's exposure step would have to be undone): drop one"),
+        (not (args.filter_3d_variance > 0.0 and finite(args.filter_3d_variance)) or args.filter_3d_interval < 1,
+         "--filter-3d-variance must be positive and finite, --filter-3d-interval >= 1")])
     if not args.dataset:
         parse_eval_scales(args.eval_scales, args.size, args.size)          # (a dataset's size is known once it is loaded)
-    if args.rasterize_mode != "classic":
-        MODE_KW["rasterize_mode"] = args.rasterize_mode
-    if not args.densify_grad_threshold >= 0.0 or not args.prune_screen_size >= 0.0 or not args.prune_world_size >= 0.0:
-        raise SystemExit("--densify-grad-threshold, --prune-screen-size and --prune-world-size must be >= 0")
-    if args.densify_stat != "screen" and (args.absgrad or args.prune_screen_size > 0.0 or args.prune_world_size > 0.0):
-        raise SystemExit("--absgrad, --prune-screen-size and --prune-world-size need --densify-stat screen")
-    if not args.pose_lr >= 0.0 or not args.pose_noise_deg >= 0.0 or not args.pose_noise_trans >= 0.0:
-        raise SystemExit("--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0")
-    if not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0:
-        raise SystemExit("--lambda-depth and --lambda-alpha must be >= 0")
-    if args.mesh_out and not 2 <= args.mesh_resolution <= 2048:
-        raise SystemExit("--mesh-resolution must be in 2 .. 2048")
-    if args.mesh_out and not args.mesh_min_weight > 0.0:
-        raise SystemExit("--mesh-min-weight must be positive")
-    if not (args.lambda_normal >= 0.0 and np.isfinite(args.lambda_normal)):
-        raise SystemExit("--lambda-normal must be >= 0 and finite")
-    if not (args.normal_noise >= 0.0 and np.isfinite(args.normal_noise)):
-        raise SystemExit("--normal-noise must be >= 0 and finite")
-    if not np.isfinite(args.normal_alpha_min):
-        raise SystemExit("--normal-alpha-min must be finite")
-    if args.normal_dir and not args.dataset:
-        raise SystemExit("--normal-dir needs --dataset (the targets are named after its frames)")
-    if args.lambda_normal > 0.0 and args.dataset and not args.normal_dir:
-        raise SystemExit("--lambda-normal with --dataset needs --normal-dir (normal targets)")
-    if args.depth_loss == "pearson" and not args.lambda_depth > 0.0:
-        raise SystemExit("--depth-loss pearson needs --lambda-depth > 0 (its weight)")
-    if not (args.depth_noise >= 0.0 and np.isfinite(args.depth_noise)):
-        raise SystemExit("--depth-noise must be >= 0 and finite")
-    if args.depth_noise > 0.0 and args.dataset and not args.depth_dir:
-        raise SystemExit("--depth-noise with --dataset needs --depth-dir (there is no depth target to perturb)")
-    if args.lambda_depth > 0.0 and args.dataset and not args.depth_dir:
-        raise SystemExit("--lambda-depth with --dataset needs --depth-dir (inverse-depth targets)")
-    if not 0.0 <= args.lambda_dssim <= 1.0:
-        raise SystemExit(f"--lambda-dssim must be in [0, 1], not {args.lambda_dssim}")
-    if args.capacity_initial is not None and not (args.capacity and 0 <= args.capacity_initial <= (1 << 30)):
-        raise SystemExit("--capacity-initial needs --capacity and a value in [0, 2^30]")
-
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    if args.optimize_poses and (args.gpus > 1 or world > 1):
-        raise SystemExit("--optimize-poses trains on one GPU only (per-rank pose ownership is not implemented): drop --gpus")
-    if args.optimize_exposure and (args.gpus > 1 or world > 1):
-        raise SystemExit("--optimize-exposure trains on one GPU only (per-rank exposure ownership is not implemented): drop --gpus")
-    if args.gpus > 1 and world != args.gpus:
-        raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
-    if not 1 <= args.views_per_step <= args.views:
-        raise SystemExit(f"--views-per-step {args.views_per_step} must be in 1..--views ({args.views}): a step draws its views without replacement")
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    local = 0 if args.single_device else local
+    refuse([
+        (not args.densify_grad_threshold >= 0.0 or not args.prune_screen_size >= 0.0 or not args.prune_world_size >= 0.0,
+         "--densify-grad-threshold, --prune-screen-size and --prune-world-size must be >= 0"),
+        (args.densify_stat != "screen" and (args.absgrad or args.prune_screen_size > 0.0 or args.prune_world_size > 0.0),
+         "--absgrad, --prune-screen-size and --prune-world-size need --densify-stat screen"),
+        (not args.pose_lr >= 0.0 or not args.pose_noise_deg >= 0.0 or not args.pose_noise_trans >= 0.0,
+         "--pose-lr, --pose-noise-deg and --pose-noise-trans must be >= 0"),
+        (not args.lambda_depth >= 0.0 or not args.lambda_alpha >= 0.0, "--lambda-depth and --lambda-alpha must be >= 0"),
+        (args.mesh_out and not 2 <= args.mesh_resolution <= 2048, "--mesh-resolution must be in 2 .. 2048"),
+        (args.mesh_out and not args.mesh_min_weight > 0.0, "--mesh-min-weight must be positive"),
+        (not (args.lambda_normal >= 0.0 and finite(args.lambda_normal)), "--lambda-normal must be >= 0 and finite"),
+        (not (args.normal_noise >= 0.0 and finite(args.normal_noise)), "--normal-noise must be >= 0 and finite"),
+        (not finite(args.normal_alpha_min), "--normal-alpha-min must be finite"),
+        (args.normal_dir and not args.dataset, "--normal-dir needs --dataset (the targets are named after its frames)"),
+        (args.lambda_normal > 0.0 and args.dataset and not args.normal_dir, "--lambda-normal with --dataset needs --normal-dir (normal targets)"),
+        (args.depth_loss == "pearson" and not args.lambda_depth > 0.0, "--depth-loss pearson needs --lambda-depth > 0 (its weight)"),
+        (not (args.depth_noise >= 0.0 and finite(args.depth_noise)), "--depth-noise must be >= 0 and finite"),
+        (args.depth_noise > 0.0 and args.dataset and not args.depth_dir,
+         "--depth-noise with --dataset needs --depth-dir (there is no depth target to perturb)"),
+        (args.lambda_depth > 0.0 and args.dataset and not args.depth_dir, "--lambda-depth with --dataset needs --depth-dir (inverse-depth targets)"),
+        (not 0.0 <= args.lambda_dssim <= 1.0, f"--lambda-dssim must be in [0, 1], not {args.lambda_dssim}"),
+        (args.capacity_initial is not None and not (args.capacity and 0 <= args.capacity_initial <= (1 << 30)),
+         "--capacity-initial needs --capacity and a value in [0, 2^30]"),
+        *(((args.gpus > 1 or world > 1) and getattr(args, flag), ONE_GPU_ONLY[flag]) for flag in ("optimize_poses", "optimize_exposure")),
+        (args.gpus > 1 and world != args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"),
+        (not 1 <= args.views_per_step <= args.views,
+         f"--views-per-step {args.views_per_step} must be in 1..--views ({args.views}): a step draws its views without replacement")])
+    return init_cloud
+
+
+def open_device(args):
+    """(dev, rank, world): this rank's GPU, and the process group when there are several ranks"""
+    local = 0 if args.single_device else int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    rank = 0
+    rank, world = 0, int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:
         rank, world = gsr.dist.init_from_env(backend=args.backend, device=dev)
+    return dev, rank, world
 
-    bg = np.zeros(3, np.float32)
+
+def load_views(args, dev):
+    """Everything the run holds per view, as one record: the cameras (`cams`: the current ones, a list --optimize-poses writes;
+    `start_cams`: after --pose-noise-*; `true_cams`: the dataset's), the colour, alpha, depth and normal targets with their clean
+    copies (None: that perturbation is off), `depth_masks`, `normal_rots`, `weights` (loss.PixelWeights or None) with their totals
+    `w_total`, and `eval_scales`.  Targets: the dataset's, or renders of a hidden seeded scene.  The load-time perturbations follow
+    in a fixed order, each on its own seeded stream."""
+    bg, mode_kw = np.zeros(3, np.float32), mode_keywords(args)
     depth_targets = alpha_targets = normal_targets = None
     if args.dataset:
         cams, targets, alpha_targets, *dt = load_nerf(args.dataset, args.views, alpha=True, depth_dir=args.depth_dir)
@@ -635,12 +641,11 @@ def main():
         cams = [gsr.cameras.nerf_camera(gsr.scenes.orbit_pose(k, args.views), args.size, args.size, gsr.scenes.LEGO_CAMERA_ANGLE_X)
                 for k in range(args.views)]
         hidden = gsr.scenes.synthetic_scene(args.gaussians, 0.05, 0.5, seed=7)
+        hidden = {"positions": hidden["means"], "scales": hidden["scales"], "rotations": hidden["rotations"], "opacities": hidden["opacities"],
+                  "shs": hidden["shs"]}
         targets, depth_targets, alpha_targets, normal_targets = [], [], [], []
         for c in cams:
-            img, dep, hb = gsr.render_gaussians(**MODE_KW, background=bg, means3D=hidden["means"], opacity=hidden["opacities"], scales=hidden["scales"],
-                                             rotations=hidden["rotations"], viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"],
-                                             tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"], image_height=c["height"], image_width=c["width"],
-                                             sh=hidden["shs"], degree=3, campos=c["camera_center"])
+            img, dep, hb = gsr.render_view(hidden, c, bg, **mode_kw)
             targets.append(img)
             depth_targets.append(dep.reshape(c["height"], c["width"]).clone())
             alpha_targets.append((1.0 - hb["final_Ts"].reshape(c["height"], c["width"])).contiguous())
@@ -668,22 +673,18 @@ def main():
             if args.mask_occluders:
                 masks[v] = masks[v] * hole
         targets = pasted
-    pix_w = None                                                            # per view: loss.PixelWeights (the grown mask and its total M_v)
+    weights = w_total = None                                                # per view: loss.PixelWeights (the grown mask and its total M_v)
     if masks is not None:
-        pix_w = [gsr.loss.PixelWeights(torch.as_tensor(m).to(dev), dilate=args.mask_dilate) for m in masks]
-        w_total = [float(p.total.item()) for p in pix_w]
+        weights = [gsr.loss.PixelWeights(torch.as_tensor(m).to(dev), dilate=args.mask_dilate) for m in masks]
+        w_total = [float(p.total.item()) for p in weights]
         if min(w_total) <= 0.0:
             raise SystemExit(f"the mask of view {int(np.argmin(w_total))} leaves no pixel with weight (after --mask-dilate {args.mask_dilate})")
-    expo = gsr.exposure.ExposureModel(len(cams), dev) if args.optimize_exposure else None
     # --pose-noise-*: the poses the trainer starts from; the dataset's stay in true_cams for the pose error (the targets are the
     # dataset's images, or renders of the hidden scene from the dataset poses)
     true_cams = cams
     if args.pose_noise_deg > 0.0 or args.pose_noise_trans > 0.0:
         prng = np.random.default_rng(args.pose_seed)
         cams = [gsr.pose.apply_pose_delta(c, gsr.pose.random_pose_delta(prng, args.pose_noise_deg, args.pose_noise_trans)) for c in cams]
-    start_cams = cams
-    pose_xi = [np.zeros(6) for _ in cams]                                    # --optimize-poses: each view's correction, its Adam state
-    pose_m, pose_v, pose_t = [np.zeros(6) for _ in cams], [np.zeros(6) for _ in cams], [0] * len(cams)
     depth_masks = [(t > 0).float() for t in depth_targets] if depth_targets is not None else None   # (from the clean targets)
     clean_depth_targets = None
     if args.depth_noise > 0.0:                                              # every depth target as a relative depth source stored it
@@ -695,8 +696,15 @@ def main():
         gen = torch.Generator(device="cpu").manual_seed(args.normal_seed)
         normal_targets = [torch.where((t != 0).any(-1, keepdim=True), t + args.normal_noise * torch.randn(t.shape, generator=gen).to(dev), t).contiguous()
                           for t in normal_targets]
-    aux = args.lambda_depth > 0.0 or args.lambda_alpha > 0.0 or args.lambda_normal > 0.0
+    return SimpleNamespace(
+        cams=list(cams), start_cams=cams, true_cams=true_cams, targets=targets, clean_targets=clean_targets, alpha_targets=alpha_targets,
+        depth_targets=depth_targets, clean_depth_targets=clean_depth_targets, depth_masks=depth_masks, normal_targets=normal_targets,
+        clean_normal_targets=clean_normal_targets, normal_rots=normal_rots, weights=weights, w_total=w_total, eval_scales=eval_scales,
+        sum_scale=float(cams[0]["height"] * cams[0]["width"] * 3))          # an unweighted L1 sum -> mean (all views of a dataset share one size)
 
+
+def init_params(args, dev, cloud):
+    """(P, init_info): the Gaussians the run starts from (--init, or --init-points' cloud) and what the --log header says of them"""
     n = args.gaussians
     if args.init == "reference":
         # the reference trainer's start (train.py:37-92, 193-214): randf-hashed positions in (-1.3, 1.3)^3, scale 0.1, opacity 0.1
@@ -706,7 +714,7 @@ def main():
         P = gsr.densify.init_gaussian_params(n, 0.1, dev)
         P["scales"].copy_(gsr.knn.init_scales(P["positions"]))
     elif args.init == "points":
-        P = gsr.point_cloud.gaussians_from_points(init_cloud[0], init_cloud[1], device=dev)
+        P = gsr.point_cloud.gaussians_from_points(cloud[0], cloud[1], device=dev)
     else:
         init = gsr.scenes.synthetic_scene(n, 0.05, 0.5, seed=8)             # same on every rank (replicated parameters)
         t = lambda a, shape: torch.as_tensor(np.ascontiguousarray(a, np.float32)).reshape(shape).to(dev)
@@ -719,257 +727,302 @@ def main():
                           "init_scale_max": float(s0.max().item())})
         print(f"--init {args.init}: {n} Gaussians, initial scale min {init_info['init_scale_min']:.4g} median "
               f"{init_info['init_scale_median']:.4g} max {init_info['init_scale_max']:.4g}", flush=True)
+    return P, init_info
+
+
+def new_run(args, dev, rank, world, views, P, init_info):
+    """The run record: everything a step reads or writes beside the library's own state, made once."""
     model = gsr.densify.GaussianModel(
-        P, scene_extent=gsr.densify.calculate_scene_extent([c["camera_center"] for c in cams]),
+        P, scene_extent=gsr.densify.calculate_scene_extent([c["camera_center"] for c in views.cams]),
         config={"densify_from_iter": args.densify_from, "densify_until_iter": args.densify_until, "densification_interval": args.densify_interval,
                 "opacity_reset_interval": args.opacity_reset_interval, "max_allowed_prune_ratio": 1.0, "background_color": [0.0, 0.0, 0.0],
                 "densify_statistic": args.densify_stat, "densify_grad_threshold": args.densify_grad_threshold,
                 "prune_screen_size": args.prune_screen_size, "prune_world_size": args.prune_world_size})
-    screen_stats = args.densify_stat == "screen"
-    abs_kw = {"absgrad": True} if args.absgrad else {}
-    sched = {k: gsr.scheduler.LRScheduler(lr) for k, lr in gsr.optimizer.DEFAULT_LR.items()}
-    rng = np.random.default_rng(0)                                          # same stream on every rank -> same view batch
-    loss_hist = torch.zeros(max(1, args.iterations), device=dev)            # the loss curve stays on the device until the end
-    dssim = args.lambda_dssim > 0.0
-    ssim_hist = torch.zeros(max(1, args.iterations), device=dev) if dssim else None   # --lambda-dssim: the SSIM curve beside it
-    ssim_of = {}                                                            # (several views per rank: each view's mean SSIM)
+    n_views, dssim = len(views.cams), args.lambda_dssim > 0.0
     per_rank_views = -(-args.views_per_step // world)
-    sum_scale = float(cams[0]["height"] * cams[0]["width"] * 3)             # an L1 sum -> mean (all views of a dataset share one size)
-    view_of = []                                                            # with weights the scale is the view's: 3 M_v (one view per rank and step)
-    streams_few, streams_many = gsr.dist.ViewStreams(1, dev), gsr.dist.ViewStreams(min(per_rank_views, args.view_streams or 3), dev)
-    density_log = [{"iteration": -1, "points": model.num_points}]
-    # --capacity: K (None = render sized), the point count K was last confirmed for, the largest D seen, and each view's last D (its
-    # shape hint: the backward's block shape then follows the view's own count, as on the sized path)
-    cap = {"K": args.capacity_initial, "n": model.num_points if args.capacity_initial is not None else None, "max_D": 0, "D_of": {}}
-    capacity_log, sized_D = [], []
-    def pose_step(v, grad):
-        """One Adam step (beta 0.9 / 0.999, eps 1e-15) on view v's xi; its camera dict is rebuilt for the next render."""
-        pose_t[v] += 1
-        pose_m[v] = 0.9 * pose_m[v] + 0.1 * grad
-        pose_v[v] = 0.999 * pose_v[v] + 0.001 * grad * grad
-        mh, vh = pose_m[v] / (1.0 - 0.9 ** pose_t[v]), pose_v[v] / (1.0 - 0.999 ** pose_t[v])
-        pose_xi[v] = pose_xi[v] - args.pose_lr * mh / (np.sqrt(vh) + 1e-15)
-        cams[v] = gsr.pose.apply_pose_delta(start_cams[v], pose_xi[v])
+    return SimpleNamespace(
+        args=args, dev=dev, rank=rank, world=world, views=views, model=model, init_info=init_info, bg=np.zeros(3, np.float32),
+        mode_kw=mode_keywords(args),
+        # what the flags select, settled once.  The SH gradient is never materialised: backward() returns the 3-float view payload it
+        # is an outer product of, the ranks exchange that (11 + 3 floats per Gaussian instead of 59, dist.py) and the Adam kernel forms
+        # basis x payload inside the SH update (optimizer.adam_update(sh_views=...)) -- also with one rank.  --dense-sh keeps the
+        # 48-float path.
+        factored=not args.dense_sh, dssim=dssim, screen_stats=args.densify_stat == "screen", abs_kw={"absgrad": True} if args.absgrad else {},
+        aux=args.lambda_depth > 0.0 or args.lambda_alpha > 0.0 or args.lambda_normal > 0.0,
+        sched={k: gsr.scheduler.LRScheduler(lr) for k, lr in gsr.optimizer.DEFAULT_LR.items()},
+        rng=np.random.default_rng(0),                                       # same stream on every rank -> same view batch
+        per_rank_views=per_rank_views, streams_few=gsr.dist.ViewStreams(1, dev),
+        streams_many=gsr.dist.ViewStreams(min(per_rank_views, args.view_streams or 3), dev),
+        expo=gsr.exposure.ExposureModel(n_views, dev) if args.optimize_exposure else None,
+        # --optimize-poses: each view's correction xi and its Adam state
+        pose=SimpleNamespace(xi=[np.zeros(6) for _ in range(n_views)], m=[np.zeros(6) for _ in range(n_views)],
+                             v=[np.zeros(6) for _ in range(n_views)], t=[0] * n_views),
+        # --capacity: K (None = render sized), the point count K was last confirmed for, the largest D seen, and each view's last D (its
+        # shape hint: the backward's block shape then follows the view's own count, as on the sized path)
+        cap={"K": args.capacity_initial, "n": model.num_points if args.capacity_initial is not None else None, "max_D": 0, "D_of": {}},
+        density_log=[{"iteration": -1, "points": model.num_points}], capacity_log=[], filter_log=[],
+        loss_hist=torch.zeros(max(1, args.iterations), device=dev),         # the loss curve stays on the device until the end
+        ssim_hist=torch.zeros(max(1, args.iterations), device=dev) if dssim else None,   # --lambda-dssim: the SSIM curve beside it
+        ssim_of={},                                                         # (several views per rank: each view's mean SSIM)
+        view_of=[])                                                         # (one view per rank and step: the view of every iteration)
 
-    if args.optimize_poses:
-        cams = list(cams)
-    filter_log = []
 
-    def recompute_filter(it, why):
-        """--filter-3d: the filter of the current point set from ALL training cameras at their current poses (every rank computes
-        the same bits: no collective).  One record per call; its statistics are the one read-back."""
-        f = gsr.filter3d.compute_filter_3d(model.params["positions"], cams, args.filter_3d_variance)
-        assert f.shape[0] == model.num_points == model.params["scales"].shape[0], (f.shape, model.num_points)
-        MODE_KW["filter_3d"] = f
-        q = torch.stack((f.min(), f.median(), f.max())).tolist() if f.numel() else [0.0, 0.0, 0.0]
-        filter_log.append({"iteration": it, "why": why, "points": model.num_points, "min": q[0], "median": q[1], "max": q[2]})
+def mean_divisor(run, v, host=True):
+    """What divides an L1 sum over view v to give the view's mean; an SSIM sum's is a third of it.  Under per-pixel weights 3 M_v, M_v
+    the view's weight total -- host=False: from the device scalar, no wait; v a list of views: the device vector of theirs -- else
+    the 3 W H that all views share.  Where it is applied follows the step's layout: with one view per rank and step the loss
+    kernel writes the SUMS into the curves' slots, which are divided when they are printed and once at the end (rescale_curves);
+    with several, every view's sums are divided in the step and the slots hold means."""
+    V = run.views
+    if V.weights is None:
+        return V.sum_scale
+    if isinstance(v, list):
+        return 3.0 * torch.tensor(V.w_total, device=run.dev)[torch.tensor(v, device=run.dev)]
+    return 3.0 * (V.w_total[v] if host else V.weights[v].total)
 
+
+def pose_step(run, v, grad):
+    """One Adam step (beta 0.9 / 0.999, eps 1e-15) on view v's xi; its camera dict is rebuilt for the next render."""
+    p, V = run.pose, run.views
+    p.t[v] += 1
+    p.m[v] = 0.9 * p.m[v] + 0.1 * grad
+    p.v[v] = 0.999 * p.v[v] + 0.001 * grad * grad
+    mh, vh = p.m[v] / (1.0 - 0.9 ** p.t[v]), p.v[v] / (1.0 - 0.999 ** p.t[v])
+    p.xi[v] = p.xi[v] - run.args.pose_lr * mh / (np.sqrt(vh) + 1e-15)
+    V.cams[v] = gsr.pose.apply_pose_delta(V.start_cams[v], p.xi[v])
+
+
+def recompute_filter(run, it, why):
+    """--filter-3d: the filter of the current point set from ALL training cameras at their current poses (every rank computes
+    the same bits: no collective).  One record per call; its statistics are the one read-back."""
+    model = run.model
+    f = gsr.filter3d.compute_filter_3d(model.params["positions"], run.views.cams, run.args.filter_3d_variance)
+    assert f.shape[0] == model.num_points == model.params["scales"].shape[0], (f.shape, model.num_points)
+    run.mode_kw["filter_3d"] = f
+    q = torch.stack((f.min(), f.median(), f.max())).tolist() if f.numel() else [0.0, 0.0, 0.0]
+    run.filter_log.append({"iteration": it, "why": why, "points": model.num_points, "min": q[0], "median": q[1], "max": q[2]})
+
+
+def train_view(run, it, v, alone, capacity=None):
+    """One view of a step: render, the loss terms and their pixel gradients, backward.  Returns (loss, the gradient arena, the SH
+    view payload, frame).  `alone`: v is its rank's only view of the step -- the loss kernel then writes the sums into the curves'
+    slots and `loss` is the L1 sum; otherwise it is the view's mean.  frame: None, and under --capacity (buffers, backward's dict):
+    the frame's D, and for a capacity-mode frame (`capacity` = K) the screen statistics that capacity_views() adds only once the
+    overflow check has passed."""
+    args, V, P, bg, mode_kw = run.args, run.views, run.model.params, run.bg, run.mode_kw
+    c = V.cams[v]
+    if capacity is None:
+        img, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
+        run.init_info.setdefault("first_iteration_pairs", int(buf["point_list"].shape[0]))   # D of the run's first frame (sized: the host has it)
+    else:
+        img, dep, buf = gsr.render_view(P, c, bg, **mode_kw, capacity=capacity, capacity_hint=run.cap["D_of"].get(v, run.cap["max_D"]))
+    raw, expo = img, run.expo
+    if expo is not None:                                                # the loss (and its curve) sees the corrected render
+        raw = img.reshape(c["height"], c["width"], 3)
+        img = gsr.exposure.apply_exposure(raw, expo.matrix(v))
+    w_v = V.weights[v] if V.weights is not None else None               # the colour loss under this view's weights (None: the plain call)
+    mean_of = mean_divisor(run, v, host=False)
+    loss_out = run.loss_hist[it:it + 1] if alone else None              # (alone: the L1 sum goes straight into this iteration's slot)
+    if run.dssim:                                                       # ... and the SSIM sum into the SSIM curve's
+        loss_sum, ssim_sum, dpix = gsr.loss.l1_dssim_loss_and_gradients(img, V.targets[v], args.lambda_dssim, args.ssim_window, loss_out=loss_out,
+                                                                        ssim_out=run.ssim_hist[it:it + 1] if alone else None, weights=w_v)
+        run.ssim_of[v] = ssim_sum / (mean_of / 3.0)                     # (a re-run of an overflowed view replaces its entry)
+    else:
+        loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, V.targets[v], loss_out=loss_out, weights=w_v)
+    kw = {}
+    if args.lambda_depth > 0.0 and args.depth_loss == "pearson":        # lambda_d (1 - rho): blind to the target's scale and shift
+        kw["dL_ddepth_image"] = gsr.loss.depth_corr_loss_and_gradients(dep, V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
+    elif args.lambda_depth > 0.0:                                       # (the curve keeps the colour loss: the terms are in the summary)
+        kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
+    if args.lambda_alpha > 0.0:
+        kw["dL_dalpha_image"] = gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], V.alpha_targets[v], None, args.lambda_alpha)[1]
+    if args.lambda_normal > 0.0:                                        # its two images are ADDED to the depth and alpha terms'
+        _, gD, gA = gsr.loss.normal_loss_and_gradients(dep.reshape(c["height"], c["width"]), buf["final_Ts"].reshape(c["height"], c["width"]),
+                                                       V.normal_targets[v], c, None, args.lambda_normal, V.normal_rots[v], args.normal_alpha_min)
+        kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in kw else kw["dL_ddepth_image"].reshape(gD.shape) + gD
+        kw["dL_dalpha_image"] = gA if "dL_dalpha_image" not in kw else kw["dL_dalpha_image"].reshape(gA.shape) + gA
+    if expo is not None:                                                # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
+        dpix, dE = gsr.exposure.exposure_backward(raw, expo.matrix(v), dpix, out=dpix)
+    if run.aux:                                                         # the forward's depths: records re-packed with 1/depth
+        kw["geom_buffer"] = {"depths": buf["depths"]}
+    g = gsr.backward_view(P, c, bg, buf, dpix, sh_gradient="factored" if run.factored else "dense", camera_grad=args.optimize_poses,
+                          **kw, **run.abs_kw, **mode_kw)
+    if run.screen_stats and capacity is None:                           # this view's statistics, on this view's stream
+        run.model.stats.update(buf["radii"], g, use_abs=args.absgrad)
+    if expo is not None:                                                # one single-wave launch; no read-back
+        expo.step(v, dE, gsr.scheduler.decayed_lr(args.exposure_lr_init, args.exposure_lr_final, it, args.iterations))
+    if args.optimize_poses:                                             # 35 floats back: the wait this flag accepts
+        gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
+        pose_step(run, v, gsr.pose.pose_gradient(V.start_cams[v], run.pose.xi[v], gv.view(4, 4), gp.view(4, 4), gc))
+    return (loss_sum if alone else loss_sum / mean_of), g["_arena"], g["_view_payload"], ((buf, g) if args.capacity else None)
+
+
+def capacity_views(run, it, mine, n):
+    """--capacity: every view enqueued without a wait for D; then, with the backward enqueued and before Adam, each view's count
+    is read (the GPU is long past the scan) and an overflowed view is run again with the sized path."""
+    cap, alone = run.cap, len(mine) == 1
+    sized = cap["K"] is None or cap["n"] != n
+    out = []
+    for v in mine:
+        l_v, a_v, p_v, (buf, g) = train_view(run, it, v, alone, None if sized else cap["K"])
+        # (sized -- the first iteration, or the point count changed: the host has D, what K is learnt from)
+        D, overflowed = (int(buf["point_list"].shape[0]), False) if sized else gsr.forward.rendered_count(buf)
+        cap["D_of"][v] = D
+        cap["max_D"] = max(cap["max_D"], D)
+        if overflowed:                                                  # nothing computed from that frame is trusted
+            run.capacity_log.append({"iteration": it, "view": v, "capacity": cap["K"], "D": D})
+            l_v, a_v, p_v, _ = train_view(run, it, v, alone)
+        elif run.screen_stats and not sized:
+            run.model.stats.update(buf["radii"], g, use_abs=run.args.absgrad)
+        if sized or overflowed:                                         # K = ceil(1.25 x the largest D seen), at most 2^30
+            cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
+        out.append((l_v, a_v, p_v, None))
+    if sized:
+        cap["n"] = n
+    return out
+
+
+def exchange_gradients(run, n, n_batch, arena, payloads):
+    """Between "views done" and adam_update: this rank's summed gradient arena (None: it had no view) and its views' SH payloads
+    become the batch-mean gradient that every rank applies.  Returns optimizer.adam_update's (grads, sh_views, sh_scale): factored,
+    the payloads of all ranks' views, each rank padded with zero payloads to the same count (None, None once they are more than
+    one kernel call takes: the SH gradient is then rebuilt in chunks); --dense-sh, the all-reduced dense arena."""
+    dev, world, factored = run.dev, run.world, run.factored
+    per_rank = -(-n_batch // world)                                     # views per rank, rounded up
+    if arena is None:
+        arena = torch.zeros(gsr.dist.arena_size(n, small=factored), device=dev)
+    while factored and len(payloads) < per_rank:                        # ranks with a view less gather a zero payload
+        payloads.append(torch.zeros(3 * n + 4, device=dev))
+    if world != n_batch:
+        arena.mul_(world / n_batch)                                     # mean over the batch after the /world of the average
+    if not factored:
+        if world > 1:
+            gsr.dist.reduce_gradients(arena, world, average=True)
+        return gsr.dist.arena_views(arena, n), None, None
+    if world == 1:
+        sh_views = payloads                                             # nothing to exchange: the Adam kernel takes the list as it is
+    else:
+        sh_views = gsr.dist.exchange_factored(arena, torch.stack(payloads).view(-1), average=True).view(world * per_rank, 3 * n + 4)
+    grads = gsr.dist.small_arena_views(arena, n)
+    grads["dL_dshs"] = None
+    sh_scale = 1.0 / n_batch
+    if len(sh_views) > gsr.dist.MAX_VIEWS_PER_CALL:                     # more views than one kernel call takes: rebuild in chunks
+        grads["dL_dshs"] = gsr.dist.sh_gradients_from_views(run.model.params["positions"], torch.stack(list(sh_views)), 3, scale=sh_scale)
+        sh_views, sh_scale = None, None
+    return grads, sh_views, sh_scale
+
+
+def density_control(run, it, n):
+    """The reference's adaptive density control on the step's gradients (train.py:1060), its record and stdout line, and the 3D
+    filter of the point set it leaves."""
+    args, model = run.args, run.model
+    if (run.screen_stats and run.world > 1 and it > args.densify_from and it < args.densify_until and it % args.densify_interval == 0):
+        gsr.dist.reduce_densify_stats(model.stats, run.world)           # once per density-control call: every rank marks the same rows
+    log = model.densification_and_pruning(it)
+    if log["cloned"] or log["split"] or log["pruned"] or log["opacity_reset"] or log["prune_skipped"]:
+        run.density_log.append({"iteration": it, "cloned": log["cloned"], "split": log["split"], "split_removed": log["split_removed"],
+                                "pruned": log["pruned"], "prune_skipped": log["prune_skipped"], "opacity_reset": log["opacity_reset"],
+                                "points": model.num_points})
     if args.filter_3d:
-        recompute_filter(-1, "start")
-    import time
+        if model.num_points != n or log["cloned"] or log["split"] or log["pruned"]:
+            recompute_filter(run, it, "density_control")
+        elif log["opacity_reset"]:
+            recompute_filter(run, it, "opacity_reset")
+        elif it >= args.densify_until and it % args.filter_3d_interval == 0:
+            recompute_filter(run, it, "interval")
+    if run.rank == 0 and (log["cloned"] or log["split"] or log["pruned"] or log["opacity_reset"]):
+        print(f"iter {it:5d}  densify: +{log['cloned']} cloned, {log['split']} split, -{log['pruned']} pruned"
+              f"{', opacity reset' if log['opacity_reset'] else ''} -> {model.num_points} points")
+
+
+def print_loss(run, it, mine):
+    """The iteration's loss line: one read of the curves' slots (a wait, hence --print-interval)"""
+    args = run.args
+    scale = mean_divisor(run, mine[0]) if len(mine) == 1 else None      # (one view: the slots hold sums)
+    if run.dssim:                                                       # the combined loss (one read of both slots)
+        l1_v, ssim_v = torch.stack([run.loss_hist[it], run.ssim_hist[it]]).tolist()
+        l1_v, ssim_v = (l1_v / scale, ssim_v * 3.0 / scale) if scale is not None else (l1_v, ssim_v)
+        shown = (1.0 - args.lambda_dssim) * l1_v + args.lambda_dssim * (1.0 - ssim_v)
+    else:
+        shown = float(run.loss_hist[it].item()) / (scale if scale is not None else 1.0)
+    print(f"iter {it:5d}  loss {shown:.6f}", flush=True)
+
+
+def train_step(run, it):
+    """One iteration: this rank's views of the batch, the gradient exchange, Adam, density control, and what rank 0 writes."""
+    args, model, dev, world, rank = run.args, run.model, run.dev, run.world, run.rank
+    P, n = model.params, model.num_points
+    assert not args.filter_3d or run.mode_kw["filter_3d"].shape[0] == n          # never a filter of another point set
+    batch = run.rng.choice(len(run.views.cams), size=args.views_per_step, replace=False)
+    mine = [int(batch[i]) for i in gsr.dist.views_for_rank(len(batch), rank, world)]
+    alone = len(mine) == 1
+    arena, loss_acc, payloads = None, (torch.zeros(1, device=dev) if len(mine) > 1 else None), []
+    if args.capacity:
+        done = capacity_views(run, it, mine, n)
+    else:
+        # a rank with several views renders them on separate streams (one view's sort chain under another's blend kernels) and
+        # then sums them in view order, exactly as the serial loop does
+        streams = run.streams_many if (args.view_streams > 1 or (args.view_streams == 0 and n >= (1 << 17))) else run.streams_few
+        done = streams.map(lambda v: train_view(run, it, v, alone), mine)
+    for l_v, a_v, p_v, _ in done:
+        if len(mine) > 1:
+            loss_acc += l_v
+        arena = a_v if arena is None else arena.add_(a_v)
+        if run.factored:
+            payloads.append(p_v)
+    grads, sh_views, sh_scale = exchange_gradients(run, n, len(batch), arena, payloads)
+    lrs = {k: s.get_lr(it, args.iterations) for k, s in run.sched.items()}
+    model.grads = gsr.optimizer.grads_from_backward(grads)              # train.py:1047-1051
+    gsr.optimizer.adam_update(P, model.grads, model.adam_m, model.adam_v, lrs, iteration=it, sh_views=sh_views, sh_degree=3, sh_scale=sh_scale)
+    if len(mine) > 1:
+        run.loss_hist[it] = loss_acc[0] / len(mine)
+        if run.dssim:
+            run.ssim_hist[it] = sum(run.ssim_of[v] for v in mine)[0] / len(mine)
+    elif alone:
+        run.view_of.append(mine[0])                                     # written by the loss kernel as a SUM: scaled once, at the end
+    density_control(run, it, n)
+    if rank == 0 and args.output and (it % args.save_interval == 0 or it == args.iterations - 1):
+        where = os.path.join(args.output, "point_cloud", f"iteration_{it}")
+        gsr.point_cloud.save_ply(model.params, os.path.join(where, "point_cloud.ply"), model.num_points, filter_3d=run.mode_kw.get("filter_3d"))
+        if run.expo is not None:                                        # the matrices beside the PLY
+            with open(os.path.join(where, "exposure.json"), "w") as f:
+                json.dump(run.expo.state_dict(), f)
+    if rank == 0 and (it % args.print_interval == 0 or it == args.iterations - 1):
+        print_loss(run, it, mine)
+
+
+def rescale_curves(run):
+    """After the last step: with one view per rank and step the curves' slots hold sums (mean_divisor): one division for each curve."""
+    if run.per_rank_views != 1:
+        return
+    full = len(run.view_of) == run.loss_hist.numel()                    # (weighted sums: each iteration by its view's 3 M_v)
+    scale = mean_divisor(run, run.view_of) if full else run.views.sum_scale
+    run.loss_hist /= scale
+    if run.dssim:
+        run.ssim_hist /= scale / 3.0                                    # ... and sums of per-pixel SSIM
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cloud = check_args(args)
+    dev, rank, world = open_device(args)
+    views = load_views(args, dev)
+    P, init_info = init_params(args, dev, cloud)
+    run = new_run(args, dev, rank, world, views, P, init_info)
+    if args.filter_3d:
+        recompute_filter(run, -1, "start")
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
     for it in range(args.iterations):
-        P, M, V, n = model.params, model.adam_m, model.adam_v, model.num_points
-        assert not args.filter_3d or MODE_KW["filter_3d"].shape[0] == n             # never a filter of another point set
-        batch = rng.choice(len(cams), size=args.views_per_step, replace=False)
-        mine = [int(batch[i]) for i in gsr.dist.views_for_rank(len(batch), rank, world)]
-        arena, loss_acc, payloads = None, (torch.zeros(1, device=dev) if len(mine) > 1 else None), []
-        # The SH gradient is never materialised: backward() returns the 3-float view payload it is an outer product of, the
-        # ranks exchange that (11 + 3 floats per Gaussian instead of 59, dist.py) and the Adam kernel forms basis x payload
-        # inside the SH update (optimizer.adam_update(sh_views=...)) -- also with one rank.  --dense-sh keeps the 48-float path.
-        factored = not args.dense_sh
-        def one_view(v, capacity=None):
-            c = cams[v]
-            kw = dict(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
-                      viewmatrix=c["world_to_camera"], projmatrix=c["full_proj_matrix"], tan_fovx=c["tan_fovx"], tan_fovy=c["tan_fovy"],
-                      image_height=c["height"], image_width=c["width"], sh=P["shs"], degree=3, campos=c["camera_center"], **MODE_KW)
-            if capacity is None:
-                img, dep, buf = gsr.render_gaussians(**kw)
-                init_info.setdefault("first_iteration_pairs", int(buf["point_list"].shape[0]))   # D of the run's first frame (sized: the host has it)
-                if args.capacity:
-                    sized_D.append(int(buf["point_list"].shape[0]))        # (the sized path's D: what --capacity learns K from)
-            else:
-                img, dep, buf = gsr.render_gaussians(**kw, capacity=capacity, capacity_hint=cap["D_of"].get(v, cap["max_D"]))
-            raw = img
-            if expo is not None:                                            # the loss (and its curve) sees the corrected render
-                raw = img.reshape(c["height"], c["width"], 3)
-                img = gsr.exposure.apply_exposure(raw, expo.matrix(v))
-            # (one view per rank and step: the L1 sum goes straight into this iteration's slot of the loss curve)
-            w_v = pix_w[v] if pix_w is not None else None                   # the colour loss under this view's weights (None: today's call)
-            mean_of = (3.0 * w_v.total) if w_v is not None else (c["height"] * c["width"] * 3)   # an L1 sum -> this view's mean
-            if dssim:                                                       # ... and the SSIM sum into the SSIM curve's
-                loss_sum, ssim_sum, dpix = gsr.loss.l1_dssim_loss_and_gradients(
-                    img, targets[v], args.lambda_dssim, args.ssim_window, loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None,
-                    ssim_out=ssim_hist[it:it + 1] if len(mine) == 1 else None, weights=w_v)
-                ssim_of[v] = ssim_sum / (mean_of / 3.0)                     # (a re-run of an overflowed view replaces its entry)
-            else:
-                loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, targets[v], loss_out=loss_hist[it:it + 1] if len(mine) == 1 else None,
-                                                                weights=w_v)
-            aux_kw = {}
-            if args.lambda_depth > 0.0 and args.depth_loss == "pearson":    # lambda_d (1 - rho): blind to the target's scale and shift
-                aux_kw["dL_ddepth_image"] = gsr.loss.depth_corr_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
-            elif args.lambda_depth > 0.0:                                   # (the curve keeps the colour loss: the terms are in the summary)
-                aux_kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, depth_targets[v], depth_masks[v], args.lambda_depth)[1]
-            if args.lambda_alpha > 0.0:
-                aux_kw["dL_dalpha_image"] = gsr.loss.alpha_loss_and_gradients(buf["final_Ts"], alpha_targets[v], None, args.lambda_alpha)[1]
-            if args.lambda_normal > 0.0:                                    # its two images are ADDED to the depth and alpha terms'
-                _, gD, gA = gsr.loss.normal_loss_and_gradients(dep.reshape(c["height"], c["width"]), buf["final_Ts"].reshape(c["height"], c["width"]),
-                                                               normal_targets[v], c, None, args.lambda_normal, normal_rots[v], args.normal_alpha_min)
-                aux_kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in aux_kw else aux_kw["dL_ddepth_image"].reshape(gD.shape) + gD
-                aux_kw["dL_dalpha_image"] = gA if "dL_dalpha_image" not in aux_kw else aux_kw["dL_dalpha_image"].reshape(gA.shape) + gA
-            if expo is not None:                                            # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
-                dpix, dE = gsr.exposure.exposure_backward(raw, expo.matrix(v), dpix, out=dpix)
-            if aux:                                                         # the forward's depths: records re-packed with 1/depth
-                aux_kw["geom_buffer"] = {"depths": buf["depths"]}
-            g = gsr.backward(background=bg, means3D=P["positions"], dL_dpixels=dpix, opacity=P["opacities"], shs=P["shs"], scales=P["scales"],
-                             rotations=P["rotations"], viewmatrix=kw["viewmatrix"], projmatrix=kw["projmatrix"], tan_fovx=kw["tan_fovx"],
-                             tan_fovy=kw["tan_fovy"], image_height=c["height"], image_width=c["width"], campos=kw["campos"],
-                             radii=buf["radii"], means2D=buf["points_xy_image"], conic_opacity=buf["conic_opacity"], rgb=buf["colors"],
-                             cov3Ds=buf["cov3Ds"], clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
-                             img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
-                             sh_gradient="factored" if factored else "dense", camera_grad=args.optimize_poses, **aux_kw, **abs_kw, **MODE_KW)
-            if screen_stats:
-                if capacity is None:                                        # this view's statistics, on this view's stream
-                    model.stats.update(buf["radii"], g, use_abs=args.absgrad)
-                else:                                                       # --capacity: only once the overflow check has passed
-                    buf["_backward_out"] = g
-            if expo is not None:                                            # one single-wave launch; no read-back
-                expo.step(v, dE, gsr.scheduler.decayed_lr(args.exposure_lr_init, args.exposure_lr_final, it, args.iterations))
-            if args.optimize_poses:                                         # 35 floats back: the wait this flag accepts
-                gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
-                pose_step(v, gsr.pose.pose_gradient(start_cams[v], pose_xi[v], gv.view(4, 4), gp.view(4, 4), gc))
-            if capacity is not None:
-                return (loss_sum if len(mine) == 1 else loss_sum / mean_of), g["_arena"], g["_view_payload"], buf
-            return (loss_sum if len(mine) == 1 else loss_sum / mean_of), g["_arena"], g["_view_payload"]
-
-        def capacity_views():
-            """--capacity: every view enqueued without a wait for D; then, with the backward enqueued and before Adam, each view's count
-            is read (the GPU is long past the scan) and an overflowed view is run again with the sized path."""
-            sized = cap["K"] is None or cap["n"] != n
-            out = []
-            for v in mine:
-                if sized:                                                   # learn D (first iteration, or the point count changed)
-                    out.append(one_view(v, None))
-                    cap["D_of"][v] = sized_D[-1]
-                    cap["max_D"] = max(cap["max_D"], sized_D[-1])
-                    cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
-                    continue
-                l_v, a_v, p_v, buf = one_view(v, cap["K"])
-                D, overflowed = gsr.forward.rendered_count(buf)
-                cap["D_of"][v] = D
-                cap["max_D"] = max(cap["max_D"], D)
-                if overflowed:                                              # nothing computed from that frame is trusted
-                    capacity_log.append({"iteration": it, "view": v, "capacity": cap["K"], "D": D})
-                    cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
-                    l_v, a_v, p_v = one_view(v)
-                elif screen_stats:
-                    model.stats.update(buf["radii"], buf["_backward_out"], use_abs=args.absgrad)
-                out.append((l_v, a_v, p_v))
-            if sized:
-                cap["n"] = n
-            return out
-
-        # a rank with several views renders them on separate streams (one view's sort chain under another's blend kernels) and
-        # then sums them in view order, exactly as the serial loop does
-        view_streams = streams_many if (args.view_streams > 1 or (args.view_streams == 0 and n >= (1 << 17))) else streams_few
-        for l_v, a_v, p_v in (capacity_views() if args.capacity else view_streams.map(one_view, mine)):
-            if len(mine) > 1:
-                loss_acc += l_v
-            arena = a_v if arena is None else arena.add_(a_v)
-            if factored:
-                payloads.append(p_v)
-        per_rank = -(-len(batch) // world)                                  # views per rank, rounded up
-        if factored:
-            if arena is None:
-                arena = torch.zeros(gsr.dist.arena_size(n, small=True), device=dev)
-            while len(payloads) < per_rank:                                 # ranks with a view less gather a zero payload
-                payloads.append(torch.zeros(3 * n + 4, device=dev))
-            if world != len(batch):
-                arena.mul_(world / len(batch))                              # mean over the batch after the /world of the average
-            if world == 1:
-                sh_views = payloads                                         # nothing to exchange: the Adam kernel takes the list as it is
-            else:
-                sh_views = gsr.dist.exchange_factored(arena, torch.stack(payloads).view(-1), average=True).view(world * per_rank, 3 * n + 4)
-            grads = gsr.dist.small_arena_views(arena, n)
-            grads["dL_dshs"] = None
-            sh_scale = 1.0 / len(batch)
-            if len(sh_views) > gsr.dist.MAX_VIEWS_PER_CALL:                 # more views than one kernel call takes: rebuild in chunks
-                grads["dL_dshs"] = gsr.dist.sh_gradients_from_views(P["positions"], torch.stack(list(sh_views)), 3, scale=sh_scale)
-                sh_views, sh_scale = None, None
-        else:
-            if arena is None:
-                arena = torch.zeros(gsr.dist.arena_size(n), device=dev)
-            if world != len(batch):
-                arena.mul_(world / len(batch))                              # mean over the batch after the /world of the average
-            if world > 1:
-                gsr.dist.reduce_gradients(arena, world, average=True)       # (this all-reduce was missing before round 4: --dense-sh
-            grads = gsr.dist.arena_views(arena, n)                          #  with several ranks trained every rank on its own views only)
-            sh_views, sh_scale = None, None
-        lrs = {k: s.get_lr(it, args.iterations) for k, s in sched.items()}
-        model.grads = gsr.optimizer.grads_from_backward(grads)              # train.py:1047-1051
-        gsr.optimizer.adam_update(P, model.grads, M, V, lrs, iteration=it, sh_views=sh_views, sh_degree=3, sh_scale=sh_scale)
-        if len(mine) > 1:
-            loss_hist[it] = loss_acc[0] / len(mine)
-            if dssim:
-                ssim_hist[it] = sum(ssim_of[v] for v in mine)[0] / len(mine)
-        elif len(mine) == 1:
-            view_of.append(mine[0])                                         # written by the loss kernel as a SUM: scaled once, at the end
-        if (screen_stats and world > 1 and it > args.densify_from and it < args.densify_until and it % args.densify_interval == 0):
-            gsr.dist.reduce_densify_stats(model.stats, world)               # once per density-control call: every rank marks the same rows
-        log = model.densification_and_pruning(it)                           # train.py:1060
-        if log["cloned"] or log["split"] or log["pruned"] or log["opacity_reset"] or log["prune_skipped"]:
-            density_log.append({"iteration": it, "cloned": log["cloned"], "split": log["split"], "split_removed": log["split_removed"],
-                                "pruned": log["pruned"], "prune_skipped": log["prune_skipped"], "opacity_reset": log["opacity_reset"],
-                                "points": model.num_points})
-        if args.filter_3d:
-            if model.num_points != n or log["cloned"] or log["split"] or log["pruned"]:
-                recompute_filter(it, "density_control")
-            elif log["opacity_reset"]:
-                recompute_filter(it, "opacity_reset")
-            elif it >= args.densify_until and it % args.filter_3d_interval == 0:
-                recompute_filter(it, "interval")
-        if rank == 0 and (log["cloned"] or log["split"] or log["pruned"] or log["opacity_reset"]):
-            print(f"iter {it:5d}  densify: +{log['cloned']} cloned, {log['split']} split, -{log['pruned']} pruned"
-                  f"{', opacity reset' if log['opacity_reset'] else ''} -> {model.num_points} points")
-        if rank == 0 and args.output and (it % args.save_interval == 0 or it == args.iterations - 1):
-            gsr.point_cloud.save_ply(model.params, os.path.join(args.output, "point_cloud", f"iteration_{it}", "point_cloud.ply"), model.num_points,
-                                    filter_3d=MODE_KW.get("filter_3d"))
-            if expo is not None:                                            # the matrices beside the PLY
-                with open(os.path.join(args.output, "point_cloud", f"iteration_{it}", "exposure.json"), "w") as f:
-                    json.dump(expo.state_dict(), f)
-        if rank == 0 and (it % args.print_interval == 0 or it == args.iterations - 1):
-            if dssim:                                                       # the combined loss (one read of both slots)
-                l1_v, ssim_v = torch.stack([loss_hist[it], ssim_hist[it]]).tolist()
-                scale = 3.0 * w_total[mine[0]] if pix_w is not None and len(mine) == 1 else sum_scale
-                l1_v, ssim_v = (l1_v / scale, ssim_v * 3.0 / scale) if len(mine) == 1 else (l1_v, ssim_v)
-                shown = (1.0 - args.lambda_dssim) * l1_v + args.lambda_dssim * (1.0 - ssim_v)
-            else:
-                shown = float(loss_hist[it].item()) / ((3.0 * w_total[mine[0]] if pix_w is not None else sum_scale) if len(mine) == 1 else 1.0)
-            print(f"iter {it:5d}  loss {shown:.6f}", flush=True)
+        train_step(run, it)
     torch.cuda.synchronize(dev)
     wall = time.perf_counter() - t_start
-    if per_rank_views == 1:
-        scale = sum_scale                                                   # slots hold sums of |difference|: one division for the whole curve
-        if pix_w is not None and len(view_of) == loss_hist.numel():         # ... weighted sums: each iteration by its view's 3 M_v
-            scale = 3.0 * torch.tensor(w_total, device=dev)[torch.tensor(view_of, device=dev)]
-        loss_hist /= scale
-        if dssim:
-            ssim_hist /= scale / 3.0                                        # ... and sums of per-pixel SSIM
+    rescale_curves(run)
     if rank == 0:
-        poses = None
-        if true_cams is not start_cams or args.optimize_poses:
-            err = lambda cs: [gsr.pose.pose_error(c, t) for c, t in zip(cs, true_cams)]
-            e0, e1 = err(start_cams), err(cams)
-            poses = {"pose_error_start": {"rot_deg": [r for r, _ in e0], "trans": [t for _, t in e0]},
-                     "pose_error_final": {"rot_deg": [r for r, _ in e1], "trans": [t for _, t in e1]},
-                     "pose_rot_deg_mean_start": float(np.mean([r for r, _ in e0])), "pose_trans_mean_start": float(np.mean([t for _, t in e0])),
-                     "pose_rot_deg_mean_final": float(np.mean([r for r, _ in e1])), "pose_trans_mean_final": float(np.mean([t for _, t in e1]))}
-        finish(args, model, cams, targets, bg, loss_hist, density_log, wall, dev, capacity_log, ssim_hist, depth_targets, alpha_targets,
-               poses, filter_log, eval_scales, expo, pix_w, clean_targets, clean_depth_targets, init_info, clean_normal_targets, normal_rots)
-        if args.mesh_out:                                                   # the model's surface from its training views (extract_mesh.py)
+        finish(run, wall)
+        if args.mesh_out:                                               # the model's surface from its training views (extract_mesh.py)
             from extract_mesh import mesh_from_model
-            mesh_from_model(gsr, model.params, cams, args.mesh_out, bg=bg, mode_kw=MODE_KW, resolution=args.mesh_resolution,
+            mesh_from_model(gsr, run.model.params, run.views.cams, args.mesh_out, bg=run.bg, mode_kw=run.mode_kw, resolution=args.mesh_resolution,
                             min_weight=args.mesh_min_weight, alpha_min=args.normal_alpha_min)
 
 

@@ -42,18 +42,9 @@ lrs = {k: 0.0 for k in gsr.optimizer.DEFAULT_LR}     # learning rate 0: the same
 
 
 def iteration(P, M, V, it, factored):
-    kw = dict(background=bg, means3D=P["positions"], opacity=P["opacities"], scales=P["scales"], rotations=P["rotations"],
-              viewmatrix=cam["world_to_camera"], projmatrix=cam["full_proj_matrix"], tan_fovx=cam["tan_fovx"], tan_fovy=cam["tan_fovy"],
-              image_height=H, image_width=W, sh=P["shs"], degree=3, campos=cam["camera_center"])
-    img, _, buf = gsr.render_gaussians(**kw)
+    img, _, buf = gsr.render_view(P, cam, bg)
     _, dpix = gsr.loss.l1_loss_and_gradients(img, target)
-    g = gsr.backward(background=bg, means3D=P["positions"], dL_dpixels=dpix, opacity=P["opacities"], shs=P["shs"], scales=P["scales"],
-                     rotations=P["rotations"], viewmatrix=kw["viewmatrix"], projmatrix=kw["projmatrix"], tan_fovx=kw["tan_fovx"],
-                     tan_fovy=kw["tan_fovy"], image_height=H, image_width=W, campos=kw["campos"], radii=buf["radii"],
-                     means2D=buf["points_xy_image"], conic_opacity=buf["conic_opacity"], rgb=buf["colors"], cov3Ds=buf["cov3Ds"],
-                     clamped=buf["clamped_state"], binning_buffer={"point_list": buf["point_list"]},
-                     img_buffer={"ranges": buf["ranges"], "final_Ts": buf["final_Ts"], "n_contrib": buf["n_contrib"]},
-                     sh_gradient="factored" if factored else "dense")
+    g = gsr.backward_view(P, cam, bg, buf, dpix, sh_gradient="factored" if factored else "dense")
     grads = gsr.optimizer.grads_from_backward(g)
     if factored:
         gsr.optimizer.adam_update(P, grads, M, V, lrs, iteration=it, sh_views=[g["_view_payload"]], sh_degree=3, sh_scale=1.0)
