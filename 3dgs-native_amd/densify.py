@@ -29,7 +29,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _host, _lib
+from . import _args, _host, _lib
 from .optimizer import GROUPS
 
 _WIDTH = {"positions": 3, "scales": 3, "rotations": 4, "opacities": 1, "shs": 48}
@@ -37,8 +37,7 @@ _WIDTH = {"positions": 3, "scales": 3, "rotations": 4, "opacities": 1, "shs": 48
 
 def _params_struct(params, n):
     for k in GROUPS:
-        t = params[k]
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n * _WIDTH[k]):
+        if not _args.is_packed(params[k], n * _WIDTH[k]):
             raise ValueError(f"densify: '{k}' must be a contiguous float32 device tensor with {n * _WIDTH[k]} elements")
     return _lib.GsrParams(n, *[_host.ptr(params[k]) for k in GROUPS])
 
@@ -62,7 +61,7 @@ def mark_candidates(params, pos_grad, grad_threshold, scene_extent, percent_dens
     dev = params["positions"].device
     p = _params_struct(params, n)
     n_grad = 0 if pos_grad is None else int(pos_grad.numel() // 3)
-    if n_grad and not (pos_grad.is_cuda and pos_grad.dtype == torch.float32 and pos_grad.is_contiguous()):
+    if n_grad and not _args.is_packed(pos_grad):
         raise ValueError("densify: pos_grad must be a contiguous float32 device tensor")
     mask = torch.empty(n, dtype=torch.int32, device=dev)
     with _host.on_device(dev):

@@ -259,16 +259,16 @@ def sh_gradients_from_views(means3D, payloads, degree=3, average=True, out=None,
     """dL_dshs [N*16, 3] summed (or averaged) over the views whose payloads are the rows of `payloads` ([V, 3*N + 4]) --
     the HIP kernel behind gsr_sh_grad_from_views.  `payloads` may also be a list of V separate [3*N + 4] tensors.
     `scale` overrides the factor (1/V when averaging) -- e.g. 1/batch when some rows are zero padding."""
-    from . import _host, _lib
+    from . import _args, _host, _lib
     rows = [payloads[v] for v in range(len(payloads))]
     if not rows:
         raise ValueError("sh_gradients_from_views: no view payloads")
     n = int(means3D.shape[0])
     dev = means3D.device
     for r in rows:
-        if not (r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() == 3 * n + 4):
+        if not _args.is_packed(r, 3 * n + 4):
             raise ValueError(f"sh_gradients_from_views: each payload must be a contiguous float32 device tensor of {3 * n + 4} elements")
-    if not (means3D.is_cuda and means3D.dtype == torch.float32 and means3D.is_contiguous()):
+    if not _args.is_packed(means3D):
         raise ValueError("sh_gradients_from_views: means3D must be a contiguous float32 device tensor")
     if out is None:
         out = torch.empty((n * 16, 3), dtype=torch.float32, device=dev)

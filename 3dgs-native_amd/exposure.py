@@ -23,29 +23,11 @@ Held-out views have no matrix: they are scored with the identity, i.e. not passe
 import numpy as np
 import torch
 
-from . import _host, _lib
+from . import _args, _host, _lib
 
 NE = _lib.EXPOSURE_FLOATS
 IDENTITY = (1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0)
 BETA1, BETA2, EPS = 0.9, 0.999, 1e-15       # 3DGS's exposure optimizer
-
-
-def _is_f32(x):
-    return x.dtype == (torch.float32 if isinstance(x, torch.Tensor) else np.float32)
-
-
-def _check_image(x, name, like=None):
-    """(H, W) of a float32 (H, W, 3) torch tensor or numpy array; refused before the library is touched."""
-    if not isinstance(x, (torch.Tensor, np.ndarray)):
-        raise ValueError(f"{name} must be a torch tensor or a numpy array (got {type(x).__name__})")
-    shape = tuple(x.shape)
-    if len(shape) != 3 or shape[2] != 3 or shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"{name} must have shape (H, W, 3) (got {shape})")
-    if like is not None and shape != like:
-        raise ValueError(f"{name} must have the image's shape {like} (got {shape})")
-    if not _is_f32(x):
-        raise ValueError(f"{name} must be float32 (got {x.dtype})")
-    return shape
 
 
 def _check_E(E, name="E"):
@@ -53,25 +35,8 @@ def _check_E(E, name="E"):
         raise ValueError(f"{name} must be a torch tensor or a numpy array of {NE} float32 (got {type(E).__name__})")
     if int(np.prod(tuple(E.shape))) != NE:
         raise ValueError(f"{name} must have {NE} elements, row-major (4, 3): A then b (got shape {tuple(E.shape)})")
-    if not _is_f32(E):
+    if not _args.is_f32(E):
         raise ValueError(f"{name} must be float32 (got {E.dtype})")
-
-
-def _check_one_device(*xs):
-    devs = {x.device for x in xs if isinstance(x, torch.Tensor) and x.is_cuda}
-    if len(devs) > 1:
-        raise ValueError(f"all tensors must live on one device (got {sorted(str(d) for d in devs)})")
-
-
-def _check_out(t, shape, name):
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and tuple(t.shape) == tuple(shape) and t.is_contiguous()
-            and t.data_ptr() % 16 == 0):
-        raise ValueError(f"{name} must be a contiguous, 16-byte aligned float32 device tensor of shape {tuple(shape)}")
-
-
-def _check_row(t, name):
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.numel() == NE and t.is_contiguous()):
-        raise ValueError(f"{name} must be a contiguous float32 device tensor of {NE} elements")
 
 
 def _row(E, dev):
@@ -84,11 +49,11 @@ def _row(E, dev):
 def apply_exposure(image, E, out=None):
     """The corrected image c' = c @ A + b, (H, W, 3) float32 on the device (gsr_exposure_apply), as a new tensor or into `out`, which
     may be `image` itself.  With E = identity the result is the input bit for bit (-0 comes back +0)."""
-    shape = _check_image(image, "image")
+    shape = _args.image_hw(image, "image", channels=3, f32=True) + (3,)
     _check_E(E)
     if out is not None:
-        _check_out(out, shape, "out")
-    _check_one_device(image, E, out)
+        _args.check_out(out, shape, "out")
+    _args.check_one_device(image, E, out)
     L = _lib.lib()
     dev = _host.device_of(image, E, out)
     r = _host.to_dev(image, torch.float32, dev, shape)
@@ -105,16 +70,15 @@ def exposure_backward(image, E, dL_dout, out=None, want_image_grad=True, dE_out=
     """(dL_dimage, dL_dE) from dL_dout = dL/d(corrected image) (gsr_exposure_backward): dL_dimage (H, W, 3) is a new tensor, or
     `out` -- in place on dL_dout when `out is dL_dout` -- or None with want_image_grad=False; dL_dE is (12,) float32 in E's layout, a
     new tensor or `dE_out`.  `image` is the UNcorrected render.  The sums use no atomics: the same inputs give the same bits."""
-    shape = _check_image(image, "image")
+    shape = _args.image_hw(image, "image", channels=3, f32=True) + (3,)
     _check_E(E)
-    _check_image(dL_dout, "dL_dout", like=shape)
+    _args.image_hw(dL_dout, "dL_dout", shape[:2], 3, f32=True)
     if out is not None:
         if not want_image_grad:
             raise ValueError("out was given with want_image_grad=False")
-        _check_out(out, shape, "out")
-    if dE_out is not None:
-        _check_row(dE_out, "dE_out")
-    _check_one_device(image, E, dL_dout, out, dE_out)
+        _args.check_out(out, shape, "out")
+    _args.check_slot(dE_out, NE, "dE_out", contiguous=True)
+    _args.check_one_device(image, E, dL_dout, out, dE_out)
     L = _lib.lib()
     dev = _host.device_of(image, E, dL_dout, out)
     r = _host.to_dev(image, torch.float32, dev, shape)

@@ -18,14 +18,10 @@ import numbers
 
 import torch
 
-from . import _host, _lib
+from . import _args, _host, _lib
 from .config import TILE_M, TILE_N
 
 FRAME_KEYS = ("points_xy_image", "conic_opacity", "point_list", "ranges", "n_contrib")
-
-
-def _is_dev(t, dtype):
-    return isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda
 
 
 def _check_frame(buffers, H, W):
@@ -40,17 +36,17 @@ def _check_frame(buffers, H, W):
     xy, co, pl, rg, nc = (buffers[k] for k in FRAME_KEYS)
     for name, t, width in (("points_xy_image", xy, 2), ("conic_opacity", co, 4)):
         # the strided column views of the blend records, or packed arrays: rows of `width` consecutive floats, any row stride
-        if not (_is_dev(t, torch.float32) and t.dim() == 2 and t.shape[1] == width and (t.shape[0] == 0 or (t.stride(1) == 1 and t.stride(0) >= width))):
+        if not (_args.is_dev(t, torch.float32) and t.dim() == 2 and t.shape[1] == width and (t.shape[0] == 0 or (t.stride(1) == 1 and t.stride(0) >= width))):
             raise ValueError(f"buffers['{name}'] must be a float32 device tensor of shape (N, {width}) with unit stride along its rows")
     N = int(xy.shape[0])
     if int(co.shape[0]) != N:
         raise ValueError("buffers['points_xy_image'] and buffers['conic_opacity'] disagree on the number of Gaussians")
-    if not (_is_dev(pl, torch.int32) and pl.dim() == 1 and pl.is_contiguous()):
+    if not (_args.is_dev(pl, torch.int32) and pl.dim() == 1 and pl.is_contiguous()):
         raise ValueError("buffers['point_list'] must be a contiguous int32 device tensor of shape (D,)")
     tiles = ((W + TILE_M - 1) // TILE_M) * ((H + TILE_N - 1) // TILE_N)
-    if not (_is_dev(rg, torch.int32) and tuple(rg.shape) == (tiles, 2) and rg.is_contiguous()):
+    if not (_args.is_dev(rg, torch.int32) and tuple(rg.shape) == (tiles, 2) and rg.is_contiguous()):
         raise ValueError(f"buffers['ranges'] must be a contiguous int32 device tensor of shape ({tiles}, 2) for a {W} x {H} image")
-    if not (_is_dev(nc, torch.int32) and tuple(nc.shape) == (H, W) and nc.is_contiguous()):
+    if not (_args.is_dev(nc, torch.int32) and tuple(nc.shape) == (H, W) and nc.is_contiguous()):
         raise ValueError(f"buffers['n_contrib'] must be a contiguous int32 device tensor of shape ({H}, {W})")
     D = int(pl.shape[0])
     if D > _lib.MAX_RENDERED:
@@ -61,7 +57,7 @@ def _check_frame(buffers, H, W):
 def _check_array(t, name, rows, what):
     """A (rows..., C) float32 contiguous device tensor; returns C."""
     lead = tuple(rows)
-    if not (_is_dev(t, torch.float32) and t.dim() == len(lead) + 1 and tuple(t.shape[:-1]) == lead):
+    if not (_args.is_dev(t, torch.float32) and t.dim() == len(lead) + 1 and tuple(t.shape[:-1]) == lead):
         raise ValueError(f"{name} must be a float32 device tensor of shape {what}")
     c = int(t.shape[-1])
     if not 1 <= c <= _lib.FEATURES_MAX_CHANNELS:
@@ -69,11 +65,6 @@ def _check_array(t, name, rows, what):
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
     return c
-
-
-def _check_out(out, shape, name):
-    if not (_is_dev(out, torch.float32) and tuple(out.shape) == tuple(shape) and out.is_contiguous() and out.data_ptr() % 16 == 0):
-        raise ValueError(f"{name} must be a contiguous, 16-byte aligned float32 device tensor of shape {tuple(shape)}")
 
 
 def _masks_of(buffers, D, dev):
@@ -93,11 +84,8 @@ def _masks_of(buffers, D, dev):
 def _call(entry, src, dst, frame_args, C_, use_masks):
     N, D, xy, co, pl, rg, nc = frame_args
     dev = src.device
-    for t in (xy, co, pl, rg, nc, dst):
-        if t.device != dev:
-            raise ValueError("every tensor of the call must live on the same device")
-    if src.data_ptr() % 16:             # an offset view: contiguous but not aligned
-        src = src.clone()
+    _args.check_one_device(src, xy, co, pl, rg, nc, dst)
+    src = _host.to_dev(src, torch.float32, dev)     # itself, or an aligned copy of an offset view
     L = _lib.lib()
     masks = use_masks if isinstance(use_masks, torch.Tensor) else None
     H, W = int(nc.shape[0]), int(nc.shape[1])
@@ -117,7 +105,7 @@ def render_features(features, buffers, image_height, image_width, out=None, *, u
     c = _check_array(features, "features", (fr[0],), "(N, C) with N the frame's number of Gaussians")
     shape = (int(image_height), int(image_width), c)
     if out is not None:
-        _check_out(out, shape, "out")
+        _args.check_out(out, shape, "out")
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=features.device)
     if fr[0] == 0:
@@ -132,7 +120,7 @@ def render_features_backward(dL_dout, buffers, image_height, image_width, out=No
     c = _check_array(dL_dout, "dL_dout", (int(image_height), int(image_width)), "(H, W, C)")
     shape = (fr[0], c)
     if out is not None:
-        _check_out(out, shape, "out")
+        _args.check_out(out, shape, "out")
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=dL_dout.device)
     if fr[0] == 0:

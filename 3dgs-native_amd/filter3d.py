@@ -14,7 +14,7 @@ collective is needed.  It is recomputed when the point set changes, not every it
 import numpy as np
 import torch
 
-from . import _host, _lib
+from . import _args, _host, _lib
 
 _VIEW_DTYPE = np.dtype([("view", "<f4", (16,)), ("focal", "<f4"), ("W", "<i4"), ("H", "<i4"), ("pad", "<i4")])   # GsrFilterView, 80 bytes
 _views = {}
@@ -50,9 +50,7 @@ def pack_views(cameras, dev):
 def compute_filter_3d(means3D, cameras, variance=_lib.FILTER3D_VARIANCE, out=None):
     """filter_3d (N,) float32 on the device, from all `cameras` (gsr_filter3d_from_views).  No camera, or no Gaussian seen by any:
     zeros, the pass-through.  `out`: a caller-owned (N,) float32 device tensor to write into."""
-    variance = float(variance)
-    if not (variance > 0.0 and np.isfinite(variance)):
-        raise ValueError(f"variance must be positive and finite (got {variance})")
+    variance = _args.positive(variance, "variance")
     L = _lib.lib()
     dev = _host.device_of(means3D, out)
     means = _host.to_dev(means3D, torch.float32, dev, (-1, 3))
@@ -101,7 +99,7 @@ def apply_filter_3d(scales, opacity, filter_3d, out=None):
     if out is None:
         out = torch.empty((N, 3), dtype=torch.float32, device=dev), torch.empty((N,), dtype=torch.float32, device=dev)
     so, oo = out
-    _check_out(so, (N, 3), dev, "scales_out"), _check_out(oo, (N,), dev, "opacity_out")
+    _args.check_out(so, (N, 3), "scales_out", dev=dev), _args.check_out(oo, (N,), "opacity_out", dev=dev)
     with _host.on_device(dev):
         _lib.check(L.gsr_filter3d_apply(N, _host.ptr(sc), _host.ptr(op), _host.ptr(f), _host.ptr(so), _host.ptr(oo), _host.raw_stream(dev)))
     _host.written_in_place(so, oo)
@@ -122,24 +120,18 @@ def filter_3d_backward(scales, opacity, filter_3d, dL_dscale, dL_dopacity, out=N
         raise ValueError("scales and opacity disagree on the number of Gaussians")
     if out is None:
         gs, go = dL_dscale, dL_dopacity
-        _check_out(gs, (N, 3), dev, "dL_dscale"), _check_out(go, (N,), dev, "dL_dopacity")
+        _args.check_out(gs, (N, 3), "dL_dscale", dev=dev), _args.check_out(go, (N,), "dL_dopacity", dev=dev)
         so, oo = gs, go
     else:
         gs = _host.to_dev(dL_dscale, torch.float32, dev, (N, 3))
         go = _host.to_dev(dL_dopacity, torch.float32, dev, (N,))
         so, oo = out
-        _check_out(so, (N, 3), dev, "dL_dscale out"), _check_out(oo, (N,), dev, "dL_dopacity out")
+        _args.check_out(so, (N, 3), "dL_dscale out", dev=dev), _args.check_out(oo, (N,), "dL_dopacity out", dev=dev)
     with _host.on_device(dev):
         _lib.check(L.gsr_filter3d_backward(N, _host.ptr(sc), _host.ptr(op), _host.ptr(f), _host.ptr(gs), _host.ptr(go), _host.ptr(so), _host.ptr(oo),
                                            _host.raw_stream(dev)))
     _host.written_in_place(so, oo)
     return so, oo
-
-
-def _check_out(t, shape, dev, name):
-    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.is_cuda and t.device == dev and tuple(t.shape) == tuple(shape)
-            and t.is_contiguous() and t.data_ptr() % 16 == 0):
-        raise ValueError(f"{name} must be a contiguous, 16-byte aligned float32 tensor of shape {tuple(shape)} on {dev}")
 
 
 # ---- the keyword of render_gaussians() / backward(): the filtered tensors ride on the frame, as rho of the antialiased mode does ----

@@ -11,7 +11,7 @@ the block boxes inside the library only prune.  Everything is enqueued on the cu
 """
 import torch
 
-from . import _host, _lib
+from . import _args, _host, _lib
 
 
 def _check_points(points):
@@ -30,12 +30,6 @@ def _check_points(points):
     return int(points.shape[0])
 
 
-def _check_out(t, shape, dtype, name):
-    if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.is_cuda and tuple(t.shape) == tuple(shape) and t.is_contiguous()
-            and t.data_ptr() % 16 == 0):
-        raise ValueError(f"{name} must be a contiguous, 16-byte aligned {str(dtype).replace('torch.', '')} device tensor of shape {tuple(shape)}")
-
-
 def knn(points, want_indices=False, out=None):
     """mean_dist2 (N,) float32 of the contiguous float32 (N, 3) device tensor `points`; with want_indices also the neighbours'
     indices (N, 3) int32 in (distance, index) order, as a pair.  `out`: caller-owned tensors to write into -- the (N,) float32
@@ -47,14 +41,13 @@ def knn(points, want_indices=False, out=None):
             if not (isinstance(out, (tuple, list)) and len(out) == 2):
                 raise ValueError("out must be the pair (mean_dist2, indices) when want_indices is set")
             mean, idx = out
-            _check_out(idx, (N, 3), torch.int32, "out[1] (indices)")
+            _args.check_out(idx, (N, 3), "out[1] (indices)", torch.int32)
         else:
             mean = out
-        _check_out(mean, (N,), torch.float32, "out (mean_dist2)" if not want_indices else "out[0] (mean_dist2)")
+        _args.check_out(mean, (N,), "out (mean_dist2)" if not want_indices else "out[0] (mean_dist2)")
     L = _lib.lib()
     dev = points.device
-    if points.data_ptr() % 16:          # an offset view such as cloud[1:]: contiguous but not aligned
-        points = points.clone()
+    points = _host.to_dev(points, torch.float32, dev)      # itself, or an aligned copy of an offset view such as cloud[1:]
     if mean is None:
         mean = torch.empty((N,), dtype=torch.float32, device=dev)
     if want_indices and idx is None:
@@ -70,7 +63,5 @@ def knn(points, want_indices=False, out=None):
 def init_scales(points, floor=1e-7):
     """(N, 3) raw scales for Gaussians at `points`: sqrt(max(mean_dist2, floor)) on all three axes -- the original's
     `sqrt(clamp_min(distCUDA2(points), 1e-7))`, without its log: this project's scales are raw (quirk Q5)."""
-    floor = float(floor)
-    if not floor > 0.0:
-        raise ValueError(f"floor must be positive (got {floor})")
+    floor = _args.positive(floor, "floor", allow_inf=True)
     return torch.sqrt(torch.clamp_min(knn(points), floor)).unsqueeze(1).repeat(1, 3)

@@ -9,29 +9,7 @@ The standard 3DGS loss (1 - lambda) L1 + lambda (1 - SSIM) with its full pixel g
 import numpy as np
 import torch
 
-from . import _host, _lib
-from . import normals as _n
-
-_WS = {}         # (kind, device, stream, W, H) -> workspace of a loss call (one per stream: views in flight on several streams)
-
-
-def _workspace(kind, nbytes, dev, stream, W, H):
-    key = (kind, dev, stream, W, H)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = _WS[key] = torch.empty(max(16, int(nbytes)), dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _weight_image(weights, what):
-    """A weight image as given: a torch tensor or numpy array, float32, (H, W) with H, W >= 1 -- judged before the GPU is touched."""
-    if not isinstance(weights, (torch.Tensor, np.ndarray)):
-        raise ValueError(f"{what} must be a torch tensor or a numpy array, not {type(weights).__name__}")
-    if weights.dtype not in (torch.float32, np.float32):
-        raise ValueError(f"{what} must be float32, not {weights.dtype}")
-    if weights.ndim != 2 or weights.shape[0] < 1 or weights.shape[1] < 1:
-        raise ValueError(f"{what} must have shape (H, W), not {tuple(weights.shape)}")
-    return weights
+from . import _args, _host, _lib
 
 
 def _weight_total(w):
@@ -41,7 +19,7 @@ def _weight_total(w):
     total = torch.empty(1, dtype=torch.float32, device=w.device)
     with _host.on_device(w.device):
         stream = _host.stream_ptr(w.device)
-        ws = _workspace("sum", L.gsr_weight_total_workspace_bytes(W, H), w.device, stream, W, H)
+        ws = _host.workspace("sum", L.gsr_weight_total_workspace_bytes(W, H), w.device, stream)
         _lib.check(L.gsr_weight_total(_host.ptr(w), W, H, _host.ptr(total), _host.ptr(ws), ws.numel(), stream))
     return total
 
@@ -54,11 +32,11 @@ class PixelWeights:
     region by r pixels.  The SSIM term reaches 5 pixels, so a region is excluded bit for bit only by a mask grown by 5."""
 
     def __init__(self, weights, dilate=0):
-        w = _weight_image(weights, "PixelWeights: weights")
+        _args.image_hw(weights, "PixelWeights: weights", squeeze=False, f32=True)     # a weight image is exactly (H, W)
         if not (isinstance(dilate, int) and dilate >= 0):
             raise ValueError(f"PixelWeights: dilate must be an integer >= 0, not {dilate!r}")
-        dev = _host.device_of(w)
-        w = _host.to_dev(w, torch.float32, dev)
+        dev = _host.device_of(weights)
+        w = _host.to_dev(weights, torch.float32, dev)
         if dilate:
             w = (-torch.nn.functional.max_pool2d(-w[None, None], 2 * dilate + 1, stride=1, padding=dilate))[0, 0].contiguous()
         self.weights, self.total = w, _weight_total(w)
@@ -67,7 +45,9 @@ class PixelWeights:
 def _checked_weights(weights, rendered, target, who):
     """The `weights` keyword before anything touches the GPU: a PixelWeights or a bare weight image whose shape is the images' and
     which lies on their device."""
-    w = weights.weights if isinstance(weights, PixelWeights) else _weight_image(weights, f"{who}: weights")
+    w = weights.weights if isinstance(weights, PixelWeights) else weights
+    if w is weights:
+        _args.image_hw(w, f"{who}: weights", squeeze=False, f32=True)
     hw = tuple(np.shape(rendered)[:2])
     if tuple(w.shape) != hw:
         raise ValueError(f"{who}: weights have shape {tuple(w.shape)} for a {hw} image")
@@ -101,14 +81,13 @@ def l1_loss_and_gradients(rendered, target, lambda_dssim=0.0, want_grad=True, lo
     r = r.reshape(H, W, 3)
     t = _host.to_dev(target, torch.float32, dev, (H, W, 3))   # alpha already dropped by the caller (train.py:323-334)
     grad = torch.empty((H, W, 3), dtype=torch.float32, device=dev) if want_grad else None
-    if loss_out is not None and not (isinstance(loss_out, torch.Tensor) and loss_out.is_cuda and loss_out.dtype == torch.float32 and loss_out.numel() == 1):
-        raise ValueError("l1_loss_and_gradients: loss_out must be a 1-element float32 device tensor")
+    _args.check_slot(loss_out, 1, "l1_loss_and_gradients: loss_out")
     loss_sum = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
     if weights is not None:
         m, total = _device_weights(weights, dev)
         with _host.on_device(dev):
             stream = _host.stream_ptr(dev)
-            ws = _workspace("sum", L.gsr_weight_total_workspace_bytes(W, H), dev, stream, W, H)
+            ws = _host.workspace("sum", L.gsr_weight_total_workspace_bytes(W, H), dev, stream)
             _lib.check(L.gsr_weighted_l1_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(total), _host.ptr(grad), _host.ptr(loss_sum),
                                                    W, H, 1.0 - float(lambda_dssim), _host.ptr(ws), ws.numel(), stream))
         return loss_sum, grad
@@ -131,12 +110,6 @@ def compute_image_gradients(rendered, target, lambda_dssim=0.2):
     return l1_loss_and_gradients(rendered, target, lambda_dssim)[1]
 
 
-def _slot(t, name):
-    if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() == 1):
-        raise ValueError(f"l1_dssim_loss_and_gradients: {name} must be a 1-element float32 device tensor")
-    return t
-
-
 def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaussian", want_grad=True, loss_out=None, ssim_out=None,
                                 weights=None):
     """L = (1 - lambda) L1 + lambda (1 - SSIM) in one call (include/gsr_loss.h), with no host sync.
@@ -153,8 +126,8 @@ def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaus
     lam = float(lambda_dssim)
     if not 0.0 <= lam <= 1.0:
         raise ValueError(f"lambda_dssim must be in [0, 1], not {lambda_dssim}")
-    _slot(loss_out, "loss_out")
-    _slot(ssim_out, "ssim_out")
+    _args.check_slot(loss_out, 1, "l1_dssim_loss_and_gradients: loss_out")
+    _args.check_slot(ssim_out, 1, "l1_dssim_loss_and_gradients: ssim_out")
     if weights is not None:
         _checked_weights(weights, rendered, target, "l1_dssim_loss_and_gradients")
     L = _lib.lib()
@@ -170,14 +143,14 @@ def l1_dssim_loss_and_gradients(rendered, target, lambda_dssim=0.2, window="gaus
         m, total = _device_weights(weights, dev)
         with _host.on_device(dev):
             stream = _host.stream_ptr(dev)
-            ws = _workspace("weighted_dssim", L.gsr_weighted_dssim_workspace_bytes(W, H), dev, stream, W, H)
+            ws = _host.workspace("weighted_dssim", L.gsr_weighted_dssim_workspace_bytes(W, H), dev, stream)
             _lib.check(L.gsr_weighted_l1_dssim_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(total), _host.ptr(grad),
                                                          _host.ptr(l1_sum), _host.ptr(ssim_sum), W, H, lam, _lib.SSIM_WINDOWS[window],
                                                          _host.ptr(ws), ws.numel(), stream))
         return l1_sum, ssim_sum, grad
     with _host.on_device(dev):
         stream = _host.stream_ptr(dev)
-        ws = _workspace("dssim", L.gsr_dssim_workspace_bytes(W, H), dev, stream, W, H)
+        ws = _host.workspace("dssim", L.gsr_dssim_workspace_bytes(W, H), dev, stream)
         _lib.check(L.gsr_l1_dssim_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(grad), _host.ptr(l1_sum), _host.ptr(ssim_sum), W, H,
                                             lam, _lib.SSIM_WINDOWS[window], _host.ptr(ws), ws.numel(), stream))
     return l1_sum, ssim_sum, grad
@@ -218,7 +191,7 @@ def depth_loss(rendered_depth, target_depth, depth_mask):
     return float(acc.item()) / (W * H)
 
 
-def _aux_l1(entry, rendered, target, mask, weight, want_grad, loss_out):
+def _aux_l1(entry, who, rendered, target, mask, weight, want_grad, loss_out):
     L = _lib.lib()
     dev = _host.device_of(rendered, target, mask)
     r = _host.to_dev(rendered, torch.float32, dev)
@@ -226,7 +199,7 @@ def _aux_l1(entry, rendered, target, mask, weight, want_grad, loss_out):
     r = r.reshape(H, W)
     t = _host.to_dev(target, torch.float32, dev, (H, W))
     m = _host.to_dev(mask, torch.float32, dev, (H, W)) if mask is not None else None
-    _slot(loss_out, "loss_out")
+    _args.check_slot(loss_out, 1, f"{who}: loss_out")
     grad = torch.empty((H, W), dtype=torch.float32, device=dev) if want_grad else None
     loss_sum = torch.empty(1, dtype=torch.float32, device=dev) if loss_out is None else loss_out
     with _host.on_device(dev):
@@ -240,27 +213,14 @@ def depth_loss_and_gradients(rendered, target, mask, weight=1.0, want_grad=True,
     Returns (loss_sum device tensor [1] = sum |rendered - target| * mask, grad (H, W) or None) with
     grad = weight / (W H) * mask * sign(rendered - target): the gradient of weight * loss_sum / (W H), the reference's depth_loss
     normalisation (loss.py:271-303).  mask may be None (all ones).  The gradient goes to backward(dL_ddepth_image=...)."""
-    return _aux_l1("gsr_depth_loss_grad", rendered, target, mask, weight, want_grad, loss_out)
+    return _aux_l1("gsr_depth_loss_grad", "depth_loss_and_gradients", rendered, target, mask, weight, want_grad, loss_out)
 
 
 def alpha_loss_and_gradients(final_Ts, target_alpha, mask=None, weight=1.0, want_grad=True, loss_out=None):
     """Masked L1 between the alpha image 1 - final_Ts and target_alpha, and its gradient with respect to the alpha image, as
     depth_loss_and_gradients (normalised by W H).  final_Ts is the forward's img_buffer["final_Ts"]; the gradient goes to
     backward(dL_dalpha_image=...)."""
-    return _aux_l1("gsr_alpha_loss_grad", final_Ts, target_alpha, mask, weight, want_grad, loss_out)
-
-
-def _depth_image(x, what, hw=None):
-    """An inverse-depth image, target or weight image as given: (H, W) or (H, W, 1) with H, W >= 1, of the shape `hw` when that is
-    known -- judged before the GPU is touched.  Returns (H, W)."""
-    shape = tuple(np.shape(x))
-    if len(shape) == 3 and shape[2] == 1:
-        shape = shape[:2]
-    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1:
-        raise ValueError(f"depth_corr_loss_and_gradients: {what} must have shape (H, W), not {tuple(np.shape(x))}")
-    if hw is not None and shape != hw:
-        raise ValueError(f"depth_corr_loss_and_gradients: {what} has shape {shape} for a {hw} render")
-    return shape
+    return _aux_l1("gsr_alpha_loss_grad", "alpha_loss_and_gradients", final_Ts, target_alpha, mask, weight, want_grad, loss_out)
 
 
 def depth_corr_loss_and_gradients(rendered, target, mask=None, weight=1.0, want_grad=True, loss_out=None, fit_out=None):
@@ -273,17 +233,14 @@ def depth_corr_loss_and_gradients(rendered, target, mask=None, weight=1.0, want_
     render or target) gives loss 1, a zero gradient and fit (0, 0, 0, M).  The loss is O(1) whatever the image size: there is no
     1 / (W H) in `weight`.  `loss_out`: a 1-element float32 device tensor that receives the loss instead of a fresh one; `fit_out`:
     the same for the 4 floats of the fit (a row of a (V, 4) tensor).  The gradient goes to backward(dL_ddepth_image=...)."""
-    hw = _depth_image(rendered, "rendered")
-    _depth_image(target, "target", hw)
+    who = "depth_corr_loss_and_gradients"
+    hw = _args.image_hw(rendered, f"{who}: rendered")
+    _args.image_hw(target, f"{who}: target", hw)
     if mask is not None:
-        _depth_image(mask, "mask", hw)
-    weight = float(weight)
-    if not np.isfinite(weight):
-        raise ValueError(f"depth_corr_loss_and_gradients: weight must be finite, not {weight}")
-    _slot(loss_out, "loss_out")
-    if fit_out is not None and not (isinstance(fit_out, torch.Tensor) and fit_out.is_cuda and fit_out.dtype == torch.float32
-                                    and fit_out.numel() == _lib.DEPTH_CORR_FIT_FLOATS and fit_out.is_contiguous()):
-        raise ValueError("depth_corr_loss_and_gradients: fit_out must be a contiguous 4-element float32 device tensor")
+        _args.image_hw(mask, f"{who}: mask", hw)
+    weight = _args.finite(weight, f"{who}: weight")
+    _args.check_slot(loss_out, 1, f"{who}: loss_out")
+    _args.check_slot(fit_out, _lib.DEPTH_CORR_FIT_FLOATS, f"{who}: fit_out", contiguous=True)
     L = _lib.lib()
     dev = _host.device_of(rendered, target, mask)
     H, W = hw
@@ -295,7 +252,7 @@ def depth_corr_loss_and_gradients(rendered, target, mask=None, weight=1.0, want_
     fit = torch.empty(_lib.DEPTH_CORR_FIT_FLOATS, dtype=torch.float32, device=dev) if fit_out is None else fit_out
     with _host.on_device(dev):
         stream = _host.stream_ptr(dev)
-        ws = _workspace("depth_corr", L.gsr_depth_corr_workspace_bytes(W, H), dev, stream, W, H)
+        ws = _host.workspace("depth_corr", L.gsr_depth_corr_workspace_bytes(W, H), dev, stream)
         _lib.check(L.gsr_depth_corr_loss_grad(_host.ptr(r), _host.ptr(t), _host.ptr(m), _host.ptr(grad), _host.ptr(loss), _host.ptr(fit), W, H,
                                               weight, _host.ptr(ws), ws.numel(), stream))
     _host.written_in_place(loss_out, fit_out)
@@ -327,20 +284,16 @@ def normal_loss_and_gradients(depth, final_Ts, target, camera, mask=None, weight
     normalisation -- and go straight into backward(dL_ddepth_image=..., dL_dalpha_image=...); None without want_grad.
     `loss_out`: a 2-element contiguous float32 device tensor that receives the sums instead of a fresh one."""
     who = "normal_loss_and_gradients"
-    tx, ty, W, H = _n.camera_params(camera, who)
-    a = _n.check_alpha_min(alpha_min, who)
-    _n.check_image(depth, "depth", H, W, who=who)
-    _n.check_image(final_Ts, "final_Ts", H, W, who=who)
-    _n.check_image(target, "target", H, W, 3, who=who)
+    tx, ty, W, H = _args.camera_params(camera, who)
+    a = _args.finite(alpha_min, f"{who}: alpha_min")
+    _args.image_hw(depth, f"{who}: depth", (H, W))
+    _args.image_hw(final_Ts, f"{who}: final_Ts", (H, W))
+    _args.image_hw(target, f"{who}: target", (H, W), 3)
     if mask is not None:
-        _n.check_image(mask, "mask", H, W, who=who)
-    weight = float(weight)
-    if not np.isfinite(weight):
-        raise ValueError(f"{who}: weight must be finite, not {weight}")
+        _args.image_hw(mask, f"{who}: mask", (H, W))
+    weight = _args.finite(weight, f"{who}: weight")
     R = _rotation(target_rotation)
-    if loss_out is not None and not (isinstance(loss_out, torch.Tensor) and loss_out.is_cuda and loss_out.dtype == torch.float32
-                                     and loss_out.numel() == _lib.NORMALS_SUMS_FLOATS and loss_out.is_contiguous()):
-        raise ValueError(f"{who}: loss_out must be a contiguous 2-element float32 device tensor")
+    _args.check_slot(loss_out, _lib.NORMALS_SUMS_FLOATS, f"{who}: loss_out", contiguous=True)
     L = _lib.lib()
     dev = _host.device_of(depth, final_Ts, target, mask)
     d = _host.to_dev(depth, torch.float32, dev, (H, W))
@@ -353,7 +306,7 @@ def normal_loss_and_gradients(depth, final_Ts, target, camera, mask=None, weight
     Rp = R.ctypes.data_as(_lib.C.POINTER(_lib.C.c_float)) if R is not None else None
     with _host.on_device(dev):
         stream = _host.stream_ptr(dev)
-        ws = _n.workspace(L, dev, stream, W, H)
+        ws = _host.workspace("normals", L.gsr_normals_workspace_bytes(W, H), dev, stream)
         _lib.check(L.gsr_normals_loss_grad(_host.ptr(d), _host.ptr(t), _host.ptr(tg), Rp, _host.ptr(m), tx, ty, W, H, a, weight / (W * H),
                                            _host.ptr(gD), _host.ptr(gA), _host.ptr(sums), _host.ptr(ws), ws.numel(), stream))
     _host.written_in_place(loss_out)

@@ -16,52 +16,14 @@ stream; nothing is read back.
 import numpy as np
 import torch
 
-from . import _host, _lib
-
-_WS = {}         # (device, stream, W, H) -> workspace (one per stream)
-
-
-def camera_params(camera, who="normals"):
-    """(tan_fovx, tan_fovy, W, H) of a camera dict, judged before the GPU is touched."""
-    try:
-        tx, ty, W, H = float(camera["tan_fovx"]), float(camera["tan_fovy"]), camera["width"], camera["height"]
-    except (KeyError, TypeError, IndexError):
-        raise ValueError(f"{who}: camera must be a dict with tan_fovx, tan_fovy, width and height") from None
-    if not (np.isfinite(tx) and np.isfinite(ty) and tx > 0.0 and ty > 0.0):
-        raise ValueError(f"{who}: tan_fovx and tan_fovy must be positive and finite, not {tx}, {ty}")
-    if int(W) != W or int(H) != H or W < 1 or H < 1 or int(W) * int(H) > 1 << 28:
-        raise ValueError(f"{who}: width and height must be integers >= 1 with width * height <= 2^28, not {W} x {H}")
-    return tx, ty, int(W), int(H)
-
-
-def check_alpha_min(alpha_min, who="normals"):
-    a = float(alpha_min)
-    if not np.isfinite(a):
-        raise ValueError(f"{who}: alpha_min must be finite, not {alpha_min}")
-    return a
-
-
-def check_image(x, what, H, W, channels=None, who="normals"):
-    """An image as given: (H, W) or (H, W, 1) without `channels`, (H, W, channels) with -- judged before the GPU is touched."""
-    shape = tuple(np.shape(x))
-    want = (H, W) if channels is None else (H, W, channels)
-    if shape != want and not (channels is None and shape == (H, W, 1)):
-        raise ValueError(f"{who}: {what} must have shape {want} for a {W} x {H} camera, not {shape}")
-
-
-def workspace(L, dev, stream, W, H):
-    key = (dev, stream, W, H)
-    ws = _WS.get(key)
-    if ws is None:
-        ws = _WS[key] = torch.empty(max(16, int(L.gsr_normals_workspace_bytes(W, H))), dtype=torch.uint8, device=dev)
-    return ws
+from . import _args, _host, _lib
 
 
 def pixel_rays(camera):
     """(H, W, 3) float64 numpy: the ray r = (((2x + 1) / W - 1) tan_fovx, ((2y + 1) / H - 1) tan_fovy, 1) of every pixel, the inverse
     of the forward's pixel convention (integer pixel coordinates are the sample positions).  depth z along +z of the camera puts
     the pixel's point at z r."""
-    tx, ty, W, H = camera_params(camera, "pixel_rays")
+    tx, ty, W, H = _args.camera_params(camera, "pixel_rays")
     x, y = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
     r = np.ones((H, W, 3))
     r[..., 0] = (((2.0 * x + 1.0) / W - 1.0) * tx)[None, :]
@@ -73,10 +35,11 @@ def normals_from_depth(depth, final_Ts, camera, alpha_min=_lib.NORMALS_ALPHA_MIN
     """(normals (H, W, 3), valid (H, W)) float32 device tensors: the camera-space unit normal of every pixel whose own and whose
     four neighbours' coverage 1 - final_Ts is at least alpha_min (and whose inverse depth is positive), (0, 0, 0) and valid = 0
     elsewhere.  A fronto-parallel surface gives (0, 0, -1)."""
-    tx, ty, W, H = camera_params(camera, "normals_from_depth")
-    a = check_alpha_min(alpha_min, "normals_from_depth")
-    check_image(depth, "depth", H, W, who="normals_from_depth")
-    check_image(final_Ts, "final_Ts", H, W, who="normals_from_depth")
+    who = "normals_from_depth"
+    tx, ty, W, H = _args.camera_params(camera, who)
+    a = _args.finite(alpha_min, f"{who}: alpha_min")
+    _args.image_hw(depth, f"{who}: depth", (H, W))
+    _args.image_hw(final_Ts, f"{who}: final_Ts", (H, W))
     L = _lib.lib()
     dev = _host.device_of(depth, final_Ts)
     d = _host.to_dev(depth, torch.float32, dev, (H, W))
@@ -92,11 +55,12 @@ def normals_from_depth_backward(dL_dnormals, depth, final_Ts, camera, alpha_min=
     """(dL_ddepth_image, dL_dalpha_image), (H, W) float32 each: the exact gradient of a loss with dL/dnormals = `dL_dnormals`
     (H, W, 3) with respect to the inverse-depth image and to the alpha image 1 - final_Ts, for the validity pattern of the call.
     Rows of dL_dnormals at pixels that are not valid are ignored.  Both go straight into backward()."""
-    tx, ty, W, H = camera_params(camera, "normals_from_depth_backward")
-    a = check_alpha_min(alpha_min, "normals_from_depth_backward")
-    check_image(depth, "depth", H, W, who="normals_from_depth_backward")
-    check_image(final_Ts, "final_Ts", H, W, who="normals_from_depth_backward")
-    check_image(dL_dnormals, "dL_dnormals", H, W, 3, who="normals_from_depth_backward")
+    who = "normals_from_depth_backward"
+    tx, ty, W, H = _args.camera_params(camera, who)
+    a = _args.finite(alpha_min, f"{who}: alpha_min")
+    _args.image_hw(depth, f"{who}: depth", (H, W))
+    _args.image_hw(final_Ts, f"{who}: final_Ts", (H, W))
+    _args.image_hw(dL_dnormals, f"{who}: dL_dnormals", (H, W), 3)
     L = _lib.lib()
     dev = _host.device_of(depth, final_Ts, dL_dnormals)
     d = _host.to_dev(depth, torch.float32, dev, (H, W))
@@ -106,7 +70,7 @@ def normals_from_depth_backward(dL_dnormals, depth, final_Ts, camera, alpha_min=
     gA = torch.empty((H, W), dtype=torch.float32, device=dev)
     with _host.on_device(dev):
         stream = _host.stream_ptr(dev)
-        ws = workspace(L, dev, stream, W, H)
+        ws = _host.workspace("normals", L.gsr_normals_workspace_bytes(W, H), dev, stream)
         _lib.check(L.gsr_normals_from_depth_backward(_host.ptr(d), _host.ptr(t), tx, ty, W, H, a, _host.ptr(g), _host.ptr(gD), _host.ptr(gA),
                                                      _host.ptr(ws), ws.numel(), stream))
     return gD, gA
@@ -132,10 +96,10 @@ def depth_to_normals(depth, final_Ts, camera, alpha_min=_lib.NORMALS_ALPHA_MIN):
     """normals_from_depth()'s normals as a torch.autograd.Function, differentiable in `depth` and `final_Ts` (device tensors): any
     torch loss on the normals reaches the two images.  d/d(depth) is normals_from_depth_backward's first image bit for bit;
     d/d(final_Ts) is its second NEGATED (the alpha image is 1 - final_Ts); feed backward() from normals_from_depth_backward."""
-    tx, ty, W, H = camera_params(camera, "depth_to_normals")
-    check_alpha_min(alpha_min, "depth_to_normals")
+    tx, ty, W, H = _args.camera_params(camera, "depth_to_normals")
+    _args.finite(alpha_min, "depth_to_normals: alpha_min")
     for name, t in (("depth", depth), ("final_Ts", final_Ts)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+        if not _args.is_dev(t, torch.float32):
             raise ValueError(f"depth_to_normals: {name} must be a float32 device tensor")
-        check_image(t, name, H, W, who="depth_to_normals")
+        _args.image_hw(t, f"depth_to_normals: {name}", (H, W))
     return _DepthToNormals.apply(depth, final_Ts, camera, float(alpha_min))

@@ -8,7 +8,7 @@ import ctypes as C
 
 import torch
 
-from . import _host, _lib
+from . import _args, _host, _lib
 
 GROUPS = ("positions", "scales", "rotations", "opacities", "shs")   # the reference's dict keys (train.py:129-143)
 DEFAULT_LR = {"positions": 1e-2, "scales": 5e-3, "rotations": 5e-3, "shs": 2e-3, "opacities": 5e-3}   # config.py:36-42
@@ -44,18 +44,16 @@ def adam_update(params, grads, m, v, lrs=None, beta1=0.9, beta2=0.999, epsilon=1
         if not 1 <= len(rows) <= 16:
             raise ValueError("adam_update: sh_views must hold 1..16 view payloads (GSR_MAX_VIEWS)")
         for r in rows:
-            if not (isinstance(r, torch.Tensor) and r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() == 3 * n + 4):
+            if not _args.is_packed(r, 3 * n + 4):
                 raise ValueError(f"adam_update: each view payload must be a contiguous float32 device tensor of {3 * n + 4} elements")
     groups = []
+    packed = _args.is_packed
     for k in GROUPS:
-        for d in (params, grads, m, v):
-            if d is grads and k == "shs" and rows is not None:
-                continue
-            t = d[k]
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == expect[k]):
-                raise ValueError(f"adam_update: '{k}' must be a contiguous float32 device tensor with {expect[k]} elements")
-        g = None if (k == "shs" and rows is not None) else grads[k]
-        groups.append(_lib.GsrAdamGroup(_host.ptr(params[k]), _host.ptr(g), _host.ptr(m[k]), _host.ptr(v[k]), float(lrs[k])))
+        views = k == "shs" and rows is not None      # the SH gradient is formed from the view payloads: grads["shs"] is not read
+        p, g, mk, vk, want = params[k], None if views else grads[k], m[k], v[k], expect[k]
+        if not (packed(p, want) and (views or packed(g, want)) and packed(mk, want) and packed(vk, want)):
+            raise ValueError(f"adam_update: '{k}' must be a contiguous float32 device tensor with {want} elements")
+        groups.append(_lib.GsrAdamGroup(_host.ptr(p), _host.ptr(g), _host.ptr(mk), _host.ptr(vk), float(lrs[k])))
     a = _lib.GsrAdam(n, groups[0], groups[1], groups[2], groups[3], groups[4], float(beta1), float(beta2), float(epsilon), int(iteration))
     with _host.on_device(dev):
         if rows is None:

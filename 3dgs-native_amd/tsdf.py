@@ -21,18 +21,7 @@ import math
 import numpy as np
 import torch
 
-from . import _host, _lib
-from .normals import camera_params, check_alpha_min, check_image
-
-
-def _positive(x, what, who, allow_inf=False):
-    try:
-        v = float(x)
-    except (TypeError, ValueError):
-        raise ValueError(f"{who}: {what} must be a number, not {x!r}") from None
-    if not (v > 0.0) or (math.isinf(v) and not allow_inf):
-        raise ValueError(f"{who}: {what} must be positive{'' if allow_inf else ' and finite'}, not {x}")
-    return v
+from . import _args, _host, _lib
 
 
 def check_volume(origin, voxel_size, dims, who="TSDFVolume"):
@@ -43,7 +32,7 @@ def check_volume(origin, voxel_size, dims, who="TSDFVolume"):
         o = np.zeros(0)
     if o.shape != (3,) or not np.isfinite(o).all():
         raise ValueError(f"{who}: origin must be 3 finite numbers, not {origin!r}")
-    s = _positive(voxel_size, "voxel_size", who)
+    s = _args.positive(voxel_size, f"{who}: voxel_size")
     try:
         g = tuple(dims)
         ok = len(g) == 3 and all(int(n) == n and 1 <= n <= _lib.TSDF_MAX_DIM for n in g)
@@ -56,7 +45,7 @@ def check_volume(origin, voxel_size, dims, who="TSDFVolume"):
 
 def check_view_camera(camera, who):
     """(view 16 floats, tan_fovx, tan_fovy, W, H) of a camera dict, judged before the GPU is touched."""
-    tx, ty, W, H = camera_params(camera, who)
+    tx, ty, W, H = _args.camera_params(camera, who)
     try:
         m = np.asarray(camera["world_to_camera"], dtype=np.float64)
     except (KeyError, TypeError, ValueError):
@@ -70,14 +59,11 @@ def depth_from_buffers(depth_image, final_Ts, alpha_min=_lib.NORMALS_ALPHA_MIN):
     """(H, W) float32 device tensor: the view depth z = (1 - final_Ts) / depth_image (`depth_image` is the forward's expected INVERSE
     depth) where gsr_normals.h defines the pixel -- coverage 1 - final_Ts at least alpha_min, inverse depth positive, both finite --
     and 0 elsewhere.  0 means "no measurement" to the integrator."""
-    a = check_alpha_min(alpha_min, "depth_from_buffers")
-    shape = tuple(np.shape(depth_image))
-    if len(shape) == 3 and shape[2] == 1:
-        shape = shape[:2]
-    if len(shape) != 2 or shape[0] < 1 or shape[1] < 1 or shape[0] * shape[1] > 1 << 28:
-        raise ValueError(f"depth_from_buffers: depth_image must have shape (H, W) or (H, W, 1) with H * W <= 2^28, not {tuple(np.shape(depth_image))}")
-    H, W = shape
-    check_image(final_Ts, "final_Ts", H, W, who="depth_from_buffers")
+    a = _args.finite(alpha_min, "depth_from_buffers: alpha_min")
+    H, W = _args.image_hw(depth_image, "depth_from_buffers: depth_image")
+    if H * W > 1 << 28:
+        raise ValueError(f"depth_from_buffers: depth_image must have H * W <= 2^28, not {H} x {W}")
+    _args.image_hw(final_Ts, "depth_from_buffers: final_Ts", (H, W))
     L = _lib.lib()
     dev = _host.device_of(depth_image, final_Ts)
     d = _host.to_dev(depth_image, torch.float32, dev, (H, W))
@@ -95,8 +81,8 @@ class TSDFVolume:
 
     def __init__(self, origin, voxel_size, dims, trunc=None, w_max=float("inf"), color=True, device=None):
         self.origin, self.voxel_size, self.dims = check_volume(origin, voxel_size, dims)
-        self.trunc = _positive(4.0 * self.voxel_size if trunc is None else trunc, "trunc", "TSDFVolume")
-        self.w_max = _positive(w_max, "w_max", "TSDFVolume", allow_inf=True)
+        self.trunc = _args.positive(4.0 * self.voxel_size if trunc is None else trunc, "TSDFVolume: trunc")
+        self.w_max = _args.positive(w_max, "TSDFVolume: w_max", allow_inf=True)
         L = _lib.lib()
         dev = torch.device(device) if device is not None else _host.device_of()
         if dev.type != "cuda":
@@ -143,14 +129,14 @@ class TSDFVolume:
         weights = [weights] * V if np.ndim(weights) == 0 else list(weights)
         if len(weights) != V:
             raise ValueError(f"{who}: weights must be one number or one per view, not {len(weights)} for {V} views")
-        dmax = _positive(depth_max, "depth_max", who, allow_inf=True)
+        dmax = _args.positive(depth_max, f"{who}: depth_max", allow_inf=True)
         parsed = []
         for k in range(V):
             view, tx, ty, W, H = check_view_camera(cameras[k], who)
-            check_image(depths[k], "depth", H, W, who=who)
+            _args.image_hw(depths[k], f"{who}: depth", (H, W))
             if colors[k] is not None:
-                check_image(colors[k], "color", H, W, 3, who=who)
-            parsed.append((view, tx, ty, W, H, _positive(weights[k], "weight", who)))
+                _args.image_hw(colors[k], f"{who}: color", (H, W), 3)
+            parsed.append((view, tx, ty, W, H, _args.positive(weights[k], f"{who}: weight")))
         L = _lib.lib()
         dev = self.device
         recs = (_lib.GsrTsdfView * V)()
@@ -171,7 +157,7 @@ class TSDFVolume:
         """(vertices (T, 3, 3), colors (T, 3, 3) or None, keys (T, 3) int64) device tensors: the triangle soup of the zero level set
         over the cells whose eight corners all have weight >= min_weight, in cell order.  Equal keys are the same vertex, bit for
         bit (weld).  Triangles are wound so that their normals point into free space.  One host read: the count."""
-        mw = _positive(min_weight, "min_weight", "extract_mesh", allow_inf=True)
+        mw = _args.positive(min_weight, "extract_mesh: min_weight", allow_inf=True)
         L = _lib.lib()
         dev = self.device
         vol = self._struct()

@@ -5,11 +5,17 @@ import re
 import subprocess
 
 import pytest
+import torch
 
 from conftest import ROOT, PKG_NAME, sub
 
 INCLUDE = os.path.join(ROOT, "include")
 A = 0x10000         # any 16-byte aligned non-null value: a fake pointer that a refused call never dereferences
+
+
+class OnDevice(torch.Tensor):
+    """A stand-in that claims to be a device tensor (there is no GPU here): `t.as_subclass(OnDevice)`."""
+    is_cuda = True
 
 
 @pytest.fixture(scope="module")

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from abi_helpers import A, compile_c99_probe, declared_names, libpath  # noqa: F401  (libpath: a fixture)
+from abi_helpers import A, OnDevice, compile_c99_probe, declared_names, libpath  # noqa: F401  (libpath: a fixture)
 from conftest import ROOT, sub
 
 HDR = os.path.join(ROOT, "include", "gsr_features.h")
@@ -95,10 +95,6 @@ def test_features_arguments_are_checked_in_order_before_any_hip_call(libpath):
         for k in ("a", "b"):
             assert call(**{k: A + 4}) == call(**{k: A + 8}) == _lib.GSR_E_ALIGN, k
         assert call(point_list=None, D=0, c=0) == _lib.GSR_E_DIMS                                      # (a frame with D = 0 needs no list)
-
-
-class OnDevice(torch.Tensor):
-    is_cuda = True
 
 
 def test_python_validators_raise_before_the_library_is_touched(monkeypatch):

@@ -1,6 +1,8 @@
 """GPU tests of the library's host-side state (include/gsr.h, 'Conventions'): the count check behind GSR_E_CAPACITY, concurrent
 host threads over distinct buffers and streams (readback slots are leased per call, not per thread), and the timing-ablation
-switches of GSR_DEBUG being inert in the product build."""
+switches of GSR_DEBUG being inert in the product build.  And of the binding's: the image losses' scratch comes from the one grow-only
+cache, _host.workspace -- a call handed a larger buffer than it asked for, or a buffer full of another call's leavings, gives the bits
+of a call with a fresh one; the cache holds one buffer per (kind, stream), whatever the image sizes were; a side stream has its own."""
 import ctypes as C
 import os
 import subprocess
@@ -9,6 +11,7 @@ import threading
 
 import numpy as np
 import pytest
+import torch
 
 import parity
 from conftest import ROOT, lego_camera, pkg, render_kwargs, sub
@@ -119,3 +122,98 @@ def test_debug_ablation_bits_are_inert_in_the_product_build():
     env = dict(os.environ, GSR_DEBUG="15")
     r = subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.smoke()"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "smoke ok" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ---- one workspace cache (_host.workspace) behind the image losses ----
+SIZES = ((5, 9), (33, 15), (97, 61))        # (W, H): under one SSIM window and one normals tile; across a tile edge; a larger buffer
+KINDS = ("sum", "dssim", "weighted_dssim", "depth_corr", "normals")
+
+
+def _dev():
+    return torch.device("cuda", 0)
+
+
+def _inputs(W, H):
+    rng = np.random.default_rng(1000 * W + H)
+    y, x = np.mgrid[0:H, 0:W]
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, np.float32)).to(_dev())      # noqa: E731
+    n = rng.normal(size=(H, W, 3)) + np.array([0.0, 0.0, -2.0])
+    return {"rendered": up(rng.uniform(0, 1, (H, W, 3))), "target": up(rng.uniform(0, 1, (H, W, 3))),
+            "weights": up(rng.uniform(0, 1, (H, W)) * (rng.uniform(size=(H, W)) > 0.2)),          # a fifth of the pixels do not count
+            "depth": up(0.5 + 0.02 * x + 0.03 * y + 0.01 * rng.normal(size=(H, W))), "prior": up(rng.uniform(0.1, 2.0, (H, W))),
+            "final_Ts": up(rng.uniform(0.0, 0.3, (H, W))), "normal": up(n / np.linalg.norm(n, axis=2, keepdims=True)),
+            "camera": {"tan_fovx": 0.5, "tan_fovy": 0.5 * H / W, "width": W, "height": H}}
+
+
+@pytest.fixture(scope="module")
+def inputs():
+    return {size: _inputs(*size) for size in SIZES}
+
+
+def _call(kind, a):
+    """The public call behind a workspace kind; every output tensor of it."""
+    loss = sub("loss")
+    if kind == "sum":
+        out = loss.l1_loss_and_gradients(a["rendered"], a["target"], 0.2, weights=a["weights"])
+    elif kind == "dssim":
+        out = loss.l1_dssim_loss_and_gradients(a["rendered"], a["target"])
+    elif kind == "weighted_dssim":
+        out = loss.l1_dssim_loss_and_gradients(a["rendered"], a["target"], weights=a["weights"])
+    elif kind == "depth_corr":
+        out = loss.depth_corr_loss_and_gradients(a["depth"], a["prior"], a["weights"])
+    else:
+        out = loss.normal_loss_and_gradients(a["depth"], a["final_Ts"], a["normal"], a["camera"], mask=a["weights"])
+    assert all(t is not None for t in out)
+    return out
+
+
+def _needed(kind, W, H):
+    L = sub("_lib").lib()
+    entry = {"sum": L.gsr_weight_total_workspace_bytes, "dssim": L.gsr_dssim_workspace_bytes, "weighted_dssim": L.gsr_weighted_dssim_workspace_bytes,
+             "depth_corr": L.gsr_depth_corr_workspace_bytes, "normals": L.gsr_normals_workspace_bytes}[kind]
+    return int(entry(W, H))
+
+
+def _same_bits(got, want):
+    return all(torch.equal(g.contiguous().view(torch.int32), w.contiguous().view(torch.int32)) for g, w in zip(got, want))
+
+
+def _ours(cache):
+    return {k for k in cache if k[0] in KINDS}
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_one_workspace_per_kind_and_stream_whatever_the_sizes(kind, inputs):
+    host = sub("_host")
+    dev = _dev()
+    before = _ours(host._ws)
+    main = host.raw_stream(dev)
+    # a bare weight image has its total formed in the call, in the "sum" workspace
+    touched = {kind, "sum"} if kind == "weighted_dssim" else {kind}
+    first = {size: _call(kind, inputs[size]) for size in SIZES}                          # ascending: the buffer is made, and grows
+    ws = host._ws[(kind, dev.index, main)]
+    assert ws.numel() >= max(_needed(kind, W, H) for W, H in SIZES)
+    for size in SIZES:
+        for t in first[size]:
+            assert bool(torch.isfinite(t).all()), size
+    for k in touched:
+        host._ws[(k, dev.index, main)].fill_(0xFF)
+    for size in reversed(SIZES):                                                         # descending: a larger buffer than the call asks for, full of NaN
+        assert ws.numel() > _needed(kind, *size), size
+        assert _same_bits(_call(kind, inputs[size]), first[size]), size
+        assert host._ws[(kind, dev.index, main)] is ws, size
+    assert _ours(host._ws) - before <= {(k, dev.index, main) for k in touched}           # one per (kind, stream): none per size
+    # a side stream: a buffer of its own, the same bits
+    mid = _ours(host._ws)
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        key = (kind, dev.index, host.raw_stream(dev))
+        assert key[2] != main
+        again = {size: _call(kind, inputs[size]) for size in SIZES}
+        assert _ours(host._ws) - mid <= {(k,) + key[1:] for k in touched}
+        side_ws = host._ws[key]
+    side.synchronize()
+    assert side_ws is not ws and side_ws.data_ptr() != ws.data_ptr() and host._ws[(kind, dev.index, main)] is ws
+    for size in SIZES:
+        assert _same_bits(again[size], first[size]), size

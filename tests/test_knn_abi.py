@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from abi_helpers import A, compile_c99_probe, declared_names, libpath  # noqa: F401  (libpath: a fixture)
+from abi_helpers import A, OnDevice, compile_c99_probe, declared_names, libpath  # noqa: F401  (libpath: a fixture)
 from conftest import ROOT, sub
 
 HDR = os.path.join(ROOT, "include", "gsr_knn.h")
@@ -104,10 +104,6 @@ def test_knn_arguments_are_checked_in_order_before_any_hip_call(libpath):
     assert call(b=wsb - 1) == call(b=0) == _lib.GSR_E_WORKSPACE
     assert call(i=None, b=wsb - 1) == _lib.GSR_E_WORKSPACE                                # (nn_index may be NULL: not an error)
     assert call(n=1 << 27, b=wsb) == _lib.GSR_E_WORKSPACE                                 # the largest N is a size like any other
-
-
-class OnDevice(torch.Tensor):
-    is_cuda = True
 
 
 def test_python_validators_raise_before_the_library_is_touched(monkeypatch):
