@@ -805,10 +805,11 @@ def recompute_filter(run, it, why):
 
 def train_view(run, it, v, alone, capacity=None):
     """One view of a step: render, the loss terms and their pixel gradients, backward.  Returns (loss, the gradient arena, the SH
-    view payload, frame).  `alone`: v is its rank's only view of the step -- the loss kernel then writes the sums into the curves'
-    slots and `loss` is the L1 sum; otherwise it is the view's mean.  frame: None, and under --capacity (buffers, backward's dict):
-    the frame's D, and for a capacity-mode frame (`capacity` = K) the screen statistics that capacity_views() adds only once the
-    overflow check has passed."""
+    view payload, frame, dL/dxi).  `alone`: v is its rank's only view of the step -- the loss kernel then writes the sums into the
+    curves' slots and `loss` is the L1 sum; otherwise it is the view's mean.  frame: None, and under --capacity (buffers, backward's
+    dict): the frame's D, and for a capacity-mode frame (`capacity` = K) the screen statistics that capacity_views() adds only once
+    the overflow check has passed.  dL/dxi: None, and under --optimize-poses this frame's pose gradient -- the caller takes the pose
+    step (pose_step), once per view and iteration and only from a frame it trusts."""
     args, V, P, bg, mode_kw = run.args, run.views, run.model.params, run.bg, run.mode_kw
     c = V.cams[v]
     if capacity is None:
@@ -851,10 +852,11 @@ def train_view(run, it, v, alone, capacity=None):
         run.model.stats.update(buf["radii"], g, use_abs=args.absgrad)
     if expo is not None:                                                # one single-wave launch; no read-back
         expo.step(v, dE, gsr.scheduler.decayed_lr(args.exposure_lr_init, args.exposure_lr_final, it, args.iterations))
+    dxi = None
     if args.optimize_poses:                                             # 35 floats back: the wait this flag accepts
         gv, gp, gc = torch.cat([g["dL_dviewmatrix"].view(-1), g["dL_dprojmatrix"].view(-1), g["dL_dcampos"]]).cpu().double().split([16, 16, 3])
-        pose_step(run, v, gsr.pose.pose_gradient(V.start_cams[v], run.pose.xi[v], gv.view(4, 4), gp.view(4, 4), gc))
-    return (loss_sum if alone else loss_sum / mean_of), g["_arena"], g["_view_payload"], ((buf, g) if args.capacity else None)
+        dxi = gsr.pose.pose_gradient(V.start_cams[v], run.pose.xi[v], gv.view(4, 4), gp.view(4, 4), gc)
+    return (loss_sum if alone else loss_sum / mean_of), g["_arena"], g["_view_payload"], ((buf, g) if args.capacity else None), dxi
 
 
 def capacity_views(run, it, mine, n):
@@ -864,19 +866,19 @@ def capacity_views(run, it, mine, n):
     sized = cap["K"] is None or cap["n"] != n
     out = []
     for v in mine:
-        l_v, a_v, p_v, (buf, g) = train_view(run, it, v, alone, None if sized else cap["K"])
+        l_v, a_v, p_v, (buf, g), dxi = train_view(run, it, v, alone, None if sized else cap["K"])
         # (sized -- the first iteration, or the point count changed: the host has D, what K is learnt from)
         D, overflowed = (int(buf["point_list"].shape[0]), False) if sized else gsr.forward.rendered_count(buf)
         cap["D_of"][v] = D
         cap["max_D"] = max(cap["max_D"], D)
         if overflowed:                                                  # nothing computed from that frame is trusted
             run.capacity_log.append({"iteration": it, "view": v, "capacity": cap["K"], "D": D})
-            l_v, a_v, p_v, _ = train_view(run, it, v, alone)
+            l_v, a_v, p_v, _, dxi = train_view(run, it, v, alone)
         elif run.screen_stats and not sized:
             run.model.stats.update(buf["radii"], g, use_abs=run.args.absgrad)
         if sized or overflowed:                                         # K = ceil(1.25 x the largest D seen), at most 2^30
             cap["K"] = min(1 << 30, -(-5 * cap["max_D"] // 4))
-        out.append((l_v, a_v, p_v, None))
+        out.append((l_v, a_v, p_v, None, dxi))                           # (dxi: the re-run's, never the overflowed frame's)
     if sized:
         cap["n"] = n
     return out
@@ -964,7 +966,9 @@ def train_step(run, it):
         # then sums them in view order, exactly as the serial loop does
         streams = run.streams_many if (args.view_streams > 1 or (args.view_streams == 0 and n >= (1 << 17))) else run.streams_few
         done = streams.map(lambda v: train_view(run, it, v, alone), mine)
-    for l_v, a_v, p_v, _ in done:
+    for v, (l_v, a_v, p_v, _, dxi) in zip(mine, done):
+        if dxi is not None:                                             # --optimize-poses: one step per view, from the frame that counted
+            pose_step(run, v, dxi)
         if len(mine) > 1:
             loss_acc += l_v
         arena = a_v if arena is None else arena.add_(a_v)
