@@ -245,6 +245,17 @@ FEATURES_EXPORTS = {
 FEATURES_MAX_CHANNELS = 64          # GSR_FEATURES_MAX_CHANNELS
 FEATURES_MAX_SIDE = 32768           # GSR_FEATURES_MAX_SIDE
 
+class GsrDistortionFrame(C.Structure):
+    _fields_ = GsrFeaturesFrame._fields_ + [("inv_depth", vp), ("inv_depth_stride", C.c_int64)]
+
+
+# include/gsr_distortion.h: the depth-distortion regulariser over a frame's lists, and its gradient into the backward's
+# accumulator records (its own header, so its own table)
+DISTORTION_EXPORTS = {
+    "gsr_distortion_forward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp]),
+    "gsr_distortion_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp]),
+}
+
 # include/gsr_normals.h: surface normals from the rendered depth, their gradient back to the inverse-depth and alpha images, and the
 # cosine loss against a normal prior (its own header, so its own table)
 NORMALS_EXPORTS = {
@@ -326,7 +337,7 @@ def lib():
                                   + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
                                   + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
                                   + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
-                                  + list(TSDF_EXPORTS.items())):
+                                  + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -44,6 +44,16 @@ view as a private tag).  dL_dopacity is then rho times the blend stage's gradien
 dL_dscale, dL_drot and, with camera_grad, the camera gradient.  Without a valid tag the call raises: there is nothing to fall back
 to, and classic gradients for an antialiased frame would be silently wrong; an antialiased frame handed to the default
 `rasterize_mode="classic"` raises for the same reason.  It composes with every keyword above and with capacity frames.
+
+`dL_ddistortion=g, distortion_moments=moments` (include/gsr_distortion.h; both or neither) add the gradient of
+sum_p g[p] Dist(p), the depth-distortion term of distortion.render_distortion(), whose second result `moments` is.  The call then
+always runs in three parts: the blend half, the distortion stage -- which ADDS its screen-space gradients into columns 3-4, 6, 7,
+9, 10 and 11 of the accumulator records -- and the AUX per-Gaussian half (gsr_backward_geom_aa), and the result carries
+`dL_dinv_depths`.  `dL_ddistortion` alone is legal (dL_dpixels=None: a zero alpha gradient stands in for the blend half's image).
+It composes with camera_grad (the camera kernels read the same accumulators), the antialiased mode, filter_3d, capacity frames and
+sh_gradient="factored" (the payload is made of the colour columns, which the stage does not touch).  `dL_dmean2D_abs` (columns
+12-13) stays the colour, depth and alpha terms' alone: the distortion term does not enter the densification statistic.  Without
+the two keywords the call is exactly the one above.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -53,6 +63,7 @@ import torch
 
 from . import _host, _lib
 from . import dist as _dist
+from . import distortion as _distortion
 from . import filter3d as _filter3d
 from . import forward as _forward
 
@@ -182,15 +193,40 @@ def _outputs(L, dev, N, need, sh_gradient, cleared):
                            dL_dcolor=acc[:, 0:3], dL_dmean2D=acc[:, 3:6], dL_dconic=acc[:, 6:10])
 
 
-def _launch(L, scene, cam, geom, binning, img, pg, out, flags, aa_scale, aux, on_payload, camera_grad, stream):
+def _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream):
+    """The depth-distortion term's screen-space gradient (include/gsr_distortion.h), added into the accumulator records the blend
+    half has just filled.  The frame is read from the records that half blended with: the forward's own, or the re-packed ones at
+    the head of the workspace (which carry 1 / depth: the caller passed the forward's depths).  On that second path the moments
+    may have been formed from another reciprocal of the same depths (distortion.inv_depth_of divides in torch, the re-pack on the
+    device): the two may differ in the last bit, so m - mu is then taken against a mean one ulp of m away from the forward's -- an
+    error of the size of mu's own rounding, inside the bounds the re-packed case is tested at."""
+    D = int(point_list.numel())
+    if D == 0 or N == 0:
+        return
+    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
+    frame = _distortion.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), rec[:, 9], st.masks)
+    _lib.check(L.gsr_distortion_backward(C.byref(frame), _host.ptr(g_dist), _host.ptr(moments), out.acc.data_ptr(), stream))
+
+
+def _launch(L, scene, cam, geom, binning, img, pg, out, flags, aa_scale, aux, on_payload, camera_grad, stream, distortion=None):
     """One request, whatever the options (gsr_densify_stats.h): with no auxiliary gradient and no flag it runs gsr_backward's
     kernels.  One entry point per stage: `aa` is NULL in the classic mode, and the _aa exports are then the classic calls
-    (csrc/api.hip).  Returns the camera gradient's 36 floats, or None."""
+    (csrc/api.hip).  `distortion`: None, or the stage to run between the two halves (a callable).  Returns the camera gradient's
+    36 floats, or None."""
     head = (C.byref(scene), C.byref(cam), C.byref(geom))
     ws, n_ws, aa = _host.ptr(out.ws), out.ws.numel(), _host.ptr(aa_scale)
     grads = _lib.GsrGrads(_host.ptr(out.dL_dmean3D), _host.ptr(out.dL_dscale), _host.ptr(out.dL_drot), _host.ptr(out.dL_dopacity),
                           _host.ptr(out.dL_dsh), None, None, None, _host.ptr(out.payload))
-    if on_payload is not None and out.payload is not None:
+    if distortion is not None:
+        # three parts: the blend half (with the view payload, which reads the colour columns only), the distortion stage, which adds
+        # to columns 3-4, 6-7 and 9-11 of the accumulators, and the AUX per-Gaussian half, which carries column 11 on to the means
+        _lib.check(L.gsr_backward_blend_flags(*head, C.byref(binning), C.byref(img), C.byref(pg), _host.ptr(out.payload), ws, n_ws, flags, stream))
+        if on_payload is not None and out.payload is not None:
+            on_payload(out.payload)
+        distortion()
+        grads.dL_drgb = None
+        _lib.check(L.gsr_backward_geom_aa(*head, C.byref(grads), None, ws, n_ws, aa, stream))
+    elif on_payload is not None and out.payload is not None:
         # two halves: the view payload is complete after the blend half, so the caller's hook can start its exchange
         # (an asynchronous all-gather) while the per-Gaussian half still runs
         _lib.check(L.gsr_backward_blend_flags(*head, C.byref(binning), C.byref(img), C.byref(pg), _host.ptr(out.payload), ws, n_ws, flags, stream))
@@ -235,8 +271,10 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              viewmatrix=None, projmatrix=None, tan_fovx=0.5, tan_fovy=0.5, image_height=256, image_width=256, campos=None,
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
-             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic", filter_3d=None):
+             dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic", filter_3d=None,
+             dL_ddistortion=None, distortion_moments=None):
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
+    distortion = _distortion.check_gradient_pair(dL_ddistortion, distortion_moments)
     frame_co = conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity")
     # (before anything touches the GPU: a frame rendered without the filter or with another one, raw tensors written since the render)
     if filter_3d is not None:
@@ -251,9 +289,9 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     aa_tag = _aa_scale_of(frame_co, opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
-    aux = dL_ddepth_image is not None or dL_dalpha_image is not None
+    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion
     if dL_dpixels is None and not aux:
-        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image")
+        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments)")
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
     L = _lib.lib()
     dev = _host.device_of(means3D, dL_dpixels, shs, radii)
@@ -263,6 +301,9 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     means = _host.to_dev(means3D, f32, dev, (-1, 3))
     N = means.shape[0]
     dpix, g_depth, g_alpha = opt(dL_dpixels, (H, W, 3)), opt(dL_ddepth_image, (H, W)), opt(dL_dalpha_image, (H, W))
+    g_dist, moments = opt(dL_ddistortion, (H, W)), opt(distortion_moments, (H, W, 4))
+    if distortion and dpix is None and g_depth is None and g_alpha is None:
+        g_alpha = torch.zeros((H, W), dtype=f32, device=dev)   # the blend half wants one image gradient: a zero one clears and adds nothing
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
     rot = _host.to_dev(rotations, f32, dev, (-1, 4))
@@ -288,9 +329,12 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         m2d = _host.to_dev(means2D, f32, dev, (-1, 2))
         con = _host.to_dev(conic_opacity, f32, dev, (-1, 4))
         col = _host.to_dev(rgb, f32, dev, (-1, 3))
-        if g_depth is not None and geom_buffer is not None:
+        if (g_depth is not None or distortion) and geom_buffer is not None:
             # the re-packed records carry 1/depth only from the forward's depths (gsr_aux_grads.h: without them, GSR_E_NULL)
             depths = opt(geom_buffer.get("depths"), (-1,))
+        if distortion and depths is None:
+            raise ValueError("backward(dL_ddistortion=...) on a frame that does not carry the forward's records needs "
+                             "geom_buffer['depths']: the distortion is a function of the Gaussians' inverse depths")
     cl = _host.to_dev(clamped, f32, dev, (-1, 3))
     c3 = None if st.recompute else _host.to_dev(cov3Ds, f32, dev, (-1, 6))
     ranges = _host.to_dev(given["ranges"], i32, dev, (-1, 2))
@@ -313,8 +357,12 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         out = _outputs(L, dev, N, need, sh_gradient, st.cleared)
         binning = _lib.GsrBinning(st.D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(st.masks), _host.ptr(st.order),
                                   _host.ptr(out.ws) if cleared else None, 1 if cleared else 0)
+        stream = _host.raw_stream(dev)
+        stage = None
+        if distortion:
+            stage = lambda: _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
         dcam = _launch(L, scene, cam, geom, binning, img, pg, out, _lib.BWD_ABSGRAD if absgrad else 0, aa_scale, aux, on_payload,
-                       camera_grad, _host.raw_stream(dev))
+                       camera_grad, stream, stage)
         if filt is not None:
             _filter3d.filter_3d_backward(*_filter3d.raw_inputs(filt, raw_scales, raw_opacity, dev, N), filter_3d, out.dL_dscale, out.dL_dopacity)
     return _result(out, N, dev, dcam, aux, absgrad)
@@ -324,7 +372,10 @@ def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
     """backward() of a frame forward.render_view() drew: `buffers` is the dict it returned, regrouped here into the reference's
     arguments (points_xy_image -> means2D, colors -> rgb, clamped_state -> clamped, binning_buffer, img_buffer) -- the key names
     of three dicts, nothing else; the tensors go through as they are.  **kw: sh_gradient, camera_grad, absgrad, dL_ddepth_image,
-    dL_dalpha_image, geom_buffer, rasterize_mode, filter_3d."""
+    dL_dalpha_image, geom_buffer, rasterize_mode, filter_3d, dL_ddistortion with distortion_moments (a frame whose records were
+    written since the render is re-packed from buffers["depths"], handed on here as geom_buffer)."""
+    if _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments")) and "geom_buffer" not in kw and "depths" in buffers:
+        kw["geom_buffer"] = {"depths": buffers["depths"]}
     return backward(background=background, means3D=params["positions"], dL_dpixels=dL_dpixels, opacity=params["opacities"],
                     shs=params["shs"], scales=params["scales"], rotations=params["rotations"], viewmatrix=camera["world_to_camera"],
                     projmatrix=camera["full_proj_matrix"], tan_fovx=camera["tan_fovx"], tan_fovy=camera["tan_fovy"],

@@ -223,6 +223,24 @@ def alpha_loss_and_gradients(final_Ts, target_alpha, mask=None, weight=1.0, want
     return _aux_l1("gsr_alpha_loss_grad", "alpha_loss_and_gradients", final_Ts, target_alpha, mask, weight, want_grad, loss_out)
 
 
+def distortion_loss_and_gradients(dist, mask=None, weight=1.0):
+    """The depth-distortion term of distortion.render_distortion()'s image (include/gsr_distortion.h), normalised by W H:
+    (loss, g) with loss = weight * sum(mask * dist) / (W H), a device tensor [1] for the log, and g = weight * mask / (W H), (H, W):
+    the gradient with respect to `dist`, which goes to backward(dL_ddistortion=g, distortion_moments=...).  mask may be None (all
+    ones).  Plain torch: two elementwise launches, no host sync."""
+    if not (_args.is_dev(dist, torch.float32) and dist.dim() == 2 and dist.numel() > 0):
+        raise ValueError("distortion_loss_and_gradients: dist must be a float32 device tensor of shape (H, W)")
+    w = _args.finite(weight, "distortion_loss_and_gradients: weight")
+    H, W = int(dist.shape[0]), int(dist.shape[1])
+    if mask is None:
+        g = torch.full((H, W), w / (W * H), dtype=torch.float32, device=dist.device)
+    else:
+        if not (isinstance(mask, (torch.Tensor, np.ndarray)) and tuple(np.shape(mask)) == (H, W)):
+            raise ValueError(f"distortion_loss_and_gradients: mask must have shape {(H, W)} (the image's shape)")
+        g = _host.to_dev(mask, torch.float32, dist.device, (H, W)) * (w / (W * H))
+    return (g * dist).sum().reshape(1), g
+
+
 def depth_corr_loss_and_gradients(rendered, target, mask=None, weight=1.0, want_grad=True, loss_out=None, fit_out=None):
     """1 - Pearson correlation between the rendered inverse depth and a relative depth target, with its exact gradient, three
     launches, no host sync (include/gsr_depth_corr.h).  A relative target is one known only up to t -> a t + b per image (a > 0), as

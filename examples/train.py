@@ -33,6 +33,12 @@ else the normals of the hidden scene's own depth.  --normal-noise S (seed --norm
 target once at load, for experiments.  The summary reports the mean angle between the depth normals and the clean targets
 (train_normal_angle_deg_mean) and the share of pixels that have a depth normal (train_normal_valid_share).
 
+Depth distortion (include/gsr_distortion.h, distortion.py): --lambda-dist W adds W times the mean over the pixels of
+Dist(p) = sum_i sum_{j<i} w_i w_j (m_i - m_j)^2, m the inverse view depth -- the regulariser the surface methods (2DGS, GOF, PGSR,
+RaDe-GS) train with before they extract a mesh: it pulls the Gaussians along a ray onto one surface.  It needs no target.
+--dist-from-iter K switches it on at iteration K (the methods above start it once the colours have settled).  With the weight, or
+with --report-distortion alone, the summary has train_distortion_mean: the mean of Dist over pixels and views at the end.
+
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
@@ -329,6 +335,12 @@ def normal_scores(P, cams, normal_targets, normal_rots, bg, mode_kw, alpha_min):
     return {"train_normal_angle_deg_mean": float(np.mean(angles)) if angles else None, "train_normal_valid_share": float(np.mean(shares))}
 
 
+def distortion_score(P, cams, bg, mode_kw):
+    """{"train_distortion_mean": the mean of the depth-distortion image (include/gsr_distortion.h) over pixels and views}"""
+    means = [gsr.distortion.render_distortion(gsr.render_view(P, c, bg, **mode_kw)[2], c["height"], c["width"])[0].mean() for c in cams]
+    return {"train_distortion_mean": float(torch.stack(means).double().mean().item())}
+
+
 def pose_errors(run):
     """--pose-noise-* / --optimize-poses: every view's error against the dataset poses (degrees, scene units) at the start and now"""
     V = run.views
@@ -371,6 +383,8 @@ def finish(run, wall):
         summary["train_alpha_l1_mean"] = a_l1
     if V.clean_normal_targets is not None:                                  # --lambda-normal / --normal-dir / the hidden scene's own
         summary.update(normal_scores(P, cams, V.clean_normal_targets, V.normal_rots, bg, mode_kw, args.normal_alpha_min))
+    if args.lambda_dist > 0.0 or args.report_distortion:
+        summary.update(distortion_score(P, cams, bg, mode_kw))
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
@@ -476,6 +490,11 @@ def parse_args(argv=None):
     ap.add_argument("--lambda-normal", type=float, default=0.0, help="weight of the normal term: the cosine loss between the normals of "
                     "the rendered depth and a normal prior (include/gsr_normals.h), normalised by W H as the depth term; its two "
                     "gradient images are added to those of --lambda-depth and --lambda-alpha")
+    ap.add_argument("--lambda-dist", type=float, default=0.0, metavar="W", help="weight of the depth-distortion term: W times the mean over "
+                    "the pixels of sum_i sum_{j<i} w_i w_j (m_i - m_j)^2, m the inverse view depth (include/gsr_distortion.h); no target needed")
+    ap.add_argument("--dist-from-iter", type=int, default=0, metavar="K", help="--lambda-dist acts from iteration K on")
+    ap.add_argument("--report-distortion", action="store_true", help="the summary reports train_distortion_mean (the mean of the "
+                    "distortion image over pixels and views at the end) also without --lambda-dist")
     ap.add_argument("--normal-dir", default=None, help="with --dataset: one float32 (H, W, 3) normal .npy per frame, named after its "
                     "file_path (without --dataset the normals of the hidden scene's own depth are the targets)")
     ap.add_argument("--normal-space", default="camera", choices=["camera", "world"], help="the space of --normal-dir's vectors: camera "
@@ -589,6 +608,8 @@ def check_args(args):
         (args.mesh_out and not args.mesh_min_weight > 0.0, "--mesh-min-weight must be positive"),
         (not (args.lambda_normal >= 0.0 and finite(args.lambda_normal)), "--lambda-normal must be >= 0 and finite"),
         (not (args.normal_noise >= 0.0 and finite(args.normal_noise)), "--normal-noise must be >= 0 and finite"),
+        (not (args.lambda_dist >= 0.0 and finite(args.lambda_dist)), "--lambda-dist must be >= 0 and finite"),
+        (not args.dist_from_iter >= 0, "--dist-from-iter must be >= 0"),
         (not finite(args.normal_alpha_min), "--normal-alpha-min must be finite"),
         (args.normal_dir and not args.dataset, "--normal-dir needs --dataset (the targets are named after its frames)"),
         (args.lambda_normal > 0.0 and args.dataset and not args.normal_dir, "--lambda-normal with --dataset needs --normal-dir (normal targets)"),
@@ -842,6 +863,12 @@ def train_view(run, it, v, alone, capacity=None):
                                                        V.normal_targets[v], c, None, args.lambda_normal, V.normal_rots[v], args.normal_alpha_min)
         kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in kw else kw["dL_ddepth_image"].reshape(gD.shape) + gD
         kw["dL_dalpha_image"] = gA if "dL_dalpha_image" not in kw else kw["dL_dalpha_image"].reshape(gA.shape) + gA
+    # (under --capacity this frame's overflow check comes later, in capacity_views(): both distortion kernels bound every walk by
+    # the capacity, so an overflowed frame gives wrong numbers, never a fault, and capacity_views() runs that view again, sized)
+    if args.lambda_dist > 0.0 and it >= args.dist_from_iter:            # no image carries this gradient: a stage of the backward
+        dist_image, moments = gsr.distortion.render_distortion(buf, c["height"], c["width"])
+        kw["dL_ddistortion"] = gsr.loss.distortion_loss_and_gradients(dist_image, None, args.lambda_dist)[1]
+        kw["distortion_moments"] = moments
     if expo is not None:                                                # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
         dpix, dE = gsr.exposure.exposure_backward(raw, expo.matrix(v), dpix, out=dpix)
     if run.aux:                                                         # the forward's depths: records re-packed with 1/depth
