@@ -256,6 +256,18 @@ DISTORTION_EXPORTS = {
     "gsr_distortion_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp]),
 }
 
+# include/gsr_normal_render.h: the Gaussians' own normals, their image over a frame's lists with its gradient into the backward's
+# accumulator records, and the depth-normal consistency term (its own header, so its own table)
+NORMAL_RENDER_EXPORTS = {
+    "gsr_gaussian_normals": (C.c_int, [C.c_int64, vp, vp, vp, C.POINTER(C.c_float), vp, vp]),
+    "gsr_gaussian_normals_backward": (C.c_int, [C.c_int64, vp, vp, vp, C.POINTER(C.c_float), vp, vp, vp]),
+    "gsr_normal_render_forward": (C.c_int, [C.POINTER(GsrFeaturesFrame), vp, vp, vp]),
+    "gsr_normal_render_backward": (C.c_int, [C.POINTER(GsrFeaturesFrame), vp, vp, vp, vp, vp, vp]),
+    "gsr_normal_consistency_loss": (C.c_int, [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, vp, vp, vp, vp, C.c_size_t, vp]),
+}
+NORMAL_RENDER_MIN_AXIS2 = 1e-24     # GSR_NORMAL_RENDER_MIN_AXIS2 (a float32 constant: 1e-24f)
+NORMAL_RENDER_MIN_LENGTH = 1e-3     # GSR_NORMAL_RENDER_MIN_LENGTH (a float32 constant: 1e-3f)
+
 # include/gsr_normals.h: surface normals from the rendered depth, their gradient back to the inverse-depth and alpha images, and the
 # cosine loss against a normal prior (its own header, so its own table)
 NORMALS_EXPORTS = {
@@ -337,7 +349,8 @@ def lib():
                                   + list(DEBUG_LAYOUT_EXPORTS.items()) + list(WEIGHTED_LOSS_EXPORTS.items())
                                   + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
                                   + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
-                                  + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())):
+                                  + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())
+                                  + list(NORMAL_RENDER_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

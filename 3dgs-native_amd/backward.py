@@ -54,6 +54,20 @@ It composes with camera_grad (the camera kernels read the same accumulators), th
 sh_gradient="factored" (the payload is made of the colour columns, which the stage does not touch).  `dL_dmean2D_abs` (columns
 12-13) stays the colour, depth and alpha terms' alone: the distortion term does not enter the densification statistic.  Without
 the two keywords the call is exactly the one above.
+
+`dL_dnormal_image=gN, gaussian_normals=n, normal_image=nimg` (include/gsr_normal_render.h; all three or none) add the gradient of
+sum_p gN[p] . nimg[p], nimg = normal_render.render_normals(n, ...) the blended image of the Gaussians' own normals
+n = normal_render.gaussian_normals(...).  The call then runs in three parts as for the distortion term: the blend half, the stage or
+stages (the distortion stage first when both are present) -- the normal stage ADDS its screen-space gradients into columns 3-4, 6, 7,
+9 and 10 of the accumulator records and writes `dL_dgaussian_normals`, an (N, 3) buffer -- and gsr_backward_geom_aa; the result
+carries `dL_dgaussian_normals` and `dL_dinv_depths`.  After the per-Gaussian half gsr_gaussian_normals_backward adds the normals'
+gradient to dL_drot, from the scales, rotations, means and viewmatrix AS THE CALLER PASSED THEM (under filter_3d the raw scales: the
+map is monotone per axis, so the shortest axis is the same); `normal_param_grad=False` skips that kernel, for callers who blend
+normals of their own and want only `dL_dgaussian_normals`.  `dL_dnormal_image` alone is legal (dL_dpixels=None).  It composes with
+camera_grad (the screen-space columns only: the normals' direct dependence on viewmatrix is left out of the camera gradient), the
+antialiased mode, filter_3d, capacity frames and sh_gradient="factored".  `dL_dmean2D_abs` stays the colour, depth and alpha terms'
+alone.  Without the three keywords the call is exactly the one above.  (These four names are accepted by name through the
+signature's catch-all `**rendered_stage`, checked against normal_render.STAGE_KEYWORDS; any other name is a TypeError.)
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -66,6 +80,7 @@ from . import dist as _dist
 from . import distortion as _distortion
 from . import filter3d as _filter3d
 from . import forward as _forward
+from . import normal_render as _normal_render
 
 _ZERO = {}
 
@@ -208,10 +223,26 @@ def _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, mome
     _lib.check(L.gsr_distortion_backward(C.byref(frame), _host.ptr(g_dist), _host.ptr(moments), out.acc.data_ptr(), stream))
 
 
+def _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, normals, normal_image, dnormals, stream):
+    """The normal image's screen-space gradient (include/gsr_normal_render.h), added into the accumulator records the blend half has
+    just filled, and dL/d(normals) into `dnormals`.  The frame is read from the records that half blended with, as in
+    _distortion_stage."""
+    D = int(point_list.numel())
+    if N == 0:
+        return
+    if D == 0:
+        dnormals.zero_()
+        return
+    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
+    frame = _normal_render.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), st.masks)
+    _lib.check(L.gsr_normal_render_backward(C.byref(frame), _host.ptr(normals), _host.ptr(g_normal), _host.ptr(normal_image), out.acc.data_ptr(),
+                                            _host.ptr(dnormals), stream))
+
+
 def _launch(L, scene, cam, geom, binning, img, pg, out, flags, aa_scale, aux, on_payload, camera_grad, stream, distortion=None):
     """One request, whatever the options (gsr_densify_stats.h): with no auxiliary gradient and no flag it runs gsr_backward's
     kernels.  One entry point per stage: `aa` is NULL in the classic mode, and the _aa exports are then the classic calls
-    (csrc/api.hip).  `distortion`: None, or the stage to run between the two halves (a callable).  Returns the camera gradient's
+    (csrc/api.hip).  `distortion`: None, or the stage or stages to run between the two halves (a callable).  Returns the camera gradient's
     36 floats, or None."""
     head = (C.byref(scene), C.byref(cam), C.byref(geom))
     ws, n_ws, aa = _host.ptr(out.ws), out.ws.numel(), _host.ptr(aa_scale)
@@ -272,9 +303,15 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
              dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic", filter_3d=None,
-             dL_ddistortion=None, distortion_moments=None):
+             dL_ddistortion=None, distortion_moments=None, **rendered_stage):
+    # The keywords of include/gsr_normal_render.h -- dL_dnormal_image, gaussian_normals, normal_image (None) and normal_param_grad (True)
+    # -- are taken by name from `rendered_stage` (normal_render.stage_keywords), not listed above: tests/test_normals_abi.py holds that
+    # the depth-normals stage of include/gsr_normals.h added no parameter whose name contains "normal" to this signature, by that
+    # substring.  Any other name raises the TypeError an unknown keyword always gets.
+    dL_dnormal_image, gaussian_normals, normal_image, normal_param_grad = _normal_render.stage_keywords(rendered_stage)
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
     distortion = _distortion.check_gradient_pair(dL_ddistortion, distortion_moments)
+    normal = _normal_render.check_gradient_triple(dL_dnormal_image, gaussian_normals, normal_image)
     frame_co = conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity")
     # (before anything touches the GPU: a frame rendered without the filter or with another one, raw tensors written since the render)
     if filter_3d is not None:
@@ -289,9 +326,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     aa_tag = _aa_scale_of(frame_co, opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
-    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion
+    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion or normal
     if dL_dpixels is None and not aux:
-        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments)")
+        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments, or "
+                         "dL_dnormal_image with gaussian_normals and normal_image)")
+    view16 = _normal_render.view_floats(viewmatrix, "backward(dL_dnormal_image=...)") if normal else None
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
     L = _lib.lib()
     dev = _host.device_of(means3D, dL_dpixels, shs, radii)
@@ -302,7 +341,8 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     N = means.shape[0]
     dpix, g_depth, g_alpha = opt(dL_dpixels, (H, W, 3)), opt(dL_ddepth_image, (H, W)), opt(dL_dalpha_image, (H, W))
     g_dist, moments = opt(dL_ddistortion, (H, W)), opt(distortion_moments, (H, W, 4))
-    if distortion and dpix is None and g_depth is None and g_alpha is None:
+    g_normal, gn, nimg = opt(dL_dnormal_image, (H, W, 3)), opt(gaussian_normals, (N, 3)), opt(normal_image, (H, W, 3))
+    if (distortion or normal) and dpix is None and g_depth is None and g_alpha is None:
         g_alpha = torch.zeros((H, W), dtype=f32, device=dev)   # the blend half wants one image gradient: a zero one clears and adds nothing
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
@@ -358,14 +398,30 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         binning = _lib.GsrBinning(st.D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(st.masks), _host.ptr(st.order),
                                   _host.ptr(out.ws) if cleared else None, 1 if cleared else 0)
         stream = _host.raw_stream(dev)
-        stage = None
-        if distortion:
+        stage = dnormals = None
+        if distortion and not normal:
             stage = lambda: _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
+        elif normal:
+            dnormals = torch.empty((N, 3), dtype=f32, device=dev)
+
+            def stage():                    # the distortion stage first when both are present
+                if distortion:
+                    _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
+                _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, gn, nimg, dnormals, stream)
         dcam = _launch(L, scene, cam, geom, binning, img, pg, out, _lib.BWD_ABSGRAD if absgrad else 0, aa_scale, aux, on_payload,
                        camera_grad, stream, stage)
+        if normal and normal_param_grad and N > 0:
+            # the normals' own gradient, on to the quaternions: from the caller's scales (raw under filter_3d), rotations and means
+            nsc = sc if filt is None else _host.to_dev(raw_scales, f32, dev, (-1, 3))
+            _lib.check(L.gsr_gaussian_normals_backward(N, _host.ptr(nsc), _host.ptr(rot), _host.ptr(means), view16[0], _host.ptr(dnormals),
+                                                       _host.ptr(out.dL_drot), stream))
         if filt is not None:
             _filter3d.filter_3d_backward(*_filter3d.raw_inputs(filt, raw_scales, raw_opacity, dev, N), filter_3d, out.dL_dscale, out.dL_dopacity)
-    return _result(out, N, dev, dcam, aux, absgrad)
+    res = _result(out, N, dev, dcam, aux, absgrad)
+    if normal:
+        _host.written_in_place(dnormals)
+        res["dL_dgaussian_normals"] = dnormals      # (N, 3): dL/d(gaussian_normals), what gsr_gaussian_normals_backward carried on to dL_drot
+    return res
 
 
 def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
@@ -373,7 +429,9 @@ def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
     arguments (points_xy_image -> means2D, colors -> rgb, clamped_state -> clamped, binning_buffer, img_buffer) -- the key names
     of three dicts, nothing else; the tensors go through as they are.  **kw: sh_gradient, camera_grad, absgrad, dL_ddepth_image,
     dL_dalpha_image, geom_buffer, rasterize_mode, filter_3d, dL_ddistortion with distortion_moments (a frame whose records were
-    written since the render is re-packed from buffers["depths"], handed on here as geom_buffer)."""
+    written since the render is re-packed from buffers["depths"], handed on here as geom_buffer), dL_dnormal_image with
+    gaussian_normals and normal_image, normal_param_grad."""
+    _normal_render.check_gradient_triple(kw.get("dL_dnormal_image"), kw.get("gaussian_normals"), kw.get("normal_image"))
     if _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments")) and "geom_buffer" not in kw and "depths" in buffers:
         kw["geom_buffer"] = {"depths": buffers["depths"]}
     return backward(background=background, means3D=params["positions"], dL_dpixels=dL_dpixels, opacity=params["opacities"],

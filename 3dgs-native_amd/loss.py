@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _args, _host, _lib
+from . import normals as _normals
 
 
 def _weight_total(w):
@@ -329,3 +330,44 @@ def normal_loss_and_gradients(depth, final_Ts, target, camera, mask=None, weight
                                            _host.ptr(gD), _host.ptr(gA), _host.ptr(sums), _host.ptr(ws), ws.numel(), stream))
     _host.written_in_place(loss_out)
     return sums, gD, gA
+
+
+def normal_consistency_loss_and_gradients(normal_image, depth, final_Ts, camera, mask=None, weight=1.0, alpha_min=_lib.NORMALS_ALPHA_MIN,
+                                          loss_out=None):
+    """The depth-normal consistency term of 2DGS, GOF, PGSR and RaDe-GS with the gradient on BOTH sides, three launches and the
+    depth normals' two, no host sync (include/gsr_normal_render.h).  `normal_image` (H, W, 3) is normal_render.render_normals()'s
+    image N of the Gaussians' own normals, `depth` the forward's inverse-depth image, `final_Ts` its img_buffer["final_Ts"],
+    `camera` a dict with tan_fovx, tan_fovy, width, height; `mask` (H, W) weights m >= 0 (None: all ones).  A pixel counts where its
+    depth normal n_d is valid (normals.normals_from_depth) and |N| >= 1e-3 (decided in float32); its term is m (1 - n_d . N / |N|).
+    Returns (sums, gN, gD, gA): sums a device tensor [2] = (sum of the terms, sum m) over the counted pixels (the mean loss is
+    sums[0] / sums[1]; arccos(1 - mean) the angle for m = 1), reduced in a fixed order; gN (H, W, 3), gD, gA (H, W) the gradient of
+    weight / (W H) * sums[0] with respect to the normal image, the inverse-depth image and the alpha image: they go into
+    backward(dL_dnormal_image=gN, dL_ddepth_image=gD, dL_dalpha_image=gA, ...).  `loss_out`: a 2-element contiguous float32 device
+    tensor that receives the sums instead of a fresh one."""
+    who = "normal_consistency_loss_and_gradients"
+    tx, ty, W, H = _args.camera_params(camera, who)
+    a = _args.finite(alpha_min, f"{who}: alpha_min")
+    if not (_args.is_dev(normal_image, torch.float32) and tuple(normal_image.shape) == (H, W, 3) and normal_image.is_contiguous()):
+        raise ValueError(f"{who}: normal_image must be a contiguous float32 device tensor of shape {(H, W, 3)}")
+    _args.image_hw(depth, f"{who}: depth", (H, W))
+    _args.image_hw(final_Ts, f"{who}: final_Ts", (H, W))
+    if mask is not None:
+        _args.image_hw(mask, f"{who}: mask", (H, W))
+    weight = _args.finite(weight, f"{who}: weight")
+    _args.check_slot(loss_out, 2, f"{who}: loss_out", contiguous=True)
+    L = _lib.lib()
+    dev = normal_image.device
+    nimg = _host.to_dev(normal_image, torch.float32, dev)
+    m = _host.to_dev(mask, torch.float32, dev, (H, W)) if mask is not None else None
+    n_d, valid = _normals.normals_from_depth(depth, final_Ts, camera, a)
+    gN = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    gnd = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
+    sums = torch.empty(2, dtype=torch.float32, device=dev) if loss_out is None else loss_out
+    with _host.on_device(dev):
+        stream = _host.stream_ptr(dev)
+        ws = _host.workspace("normals", L.gsr_normals_workspace_bytes(W, H), dev, stream)
+        _lib.check(L.gsr_normal_consistency_loss(_host.ptr(nimg), _host.ptr(n_d), _host.ptr(valid), _host.ptr(m), W, H, weight, _host.ptr(gN),
+                                                 _host.ptr(gnd), _host.ptr(sums), _host.ptr(ws), ws.numel(), stream))
+    _host.written_in_place(loss_out)
+    gD, gA = _normals.normals_from_depth_backward(gnd, depth, final_Ts, camera, a)
+    return sums, gN, gD, gA

@@ -39,6 +39,13 @@ RaDe-GS) train with before they extract a mesh: it pulls the Gaussians along a r
 --dist-from-iter K switches it on at iteration K (the methods above start it once the colours have settled).  With the weight, or
 with --report-distortion alone, the summary has train_distortion_mean: the mean of Dist over pixels and views at the end.
 
+Normal consistency (include/gsr_normal_render.h, normal_render.py): --lambda-normal-consistency W adds W times the mean over the
+pixels of 1 - n_d . N / |N|, N the blended image of the Gaussians' own normals (each the direction of its Gaussian's shortest axis,
+facing the camera) and n_d the normals of the rendered depth -- the second geometric term of the same methods, which turns the
+Gaussians the distortion term flattened into the surface.  No target is needed; the gradient goes to both sides.
+--normal-consistency-from-iter K switches it on at iteration K.  With the weight, or with --report-normal-consistency alone, the
+summary has train_normal_consistency_deg: the mean angle in degrees between N / |N| and n_d over counted pixels and views at the end.
+
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
@@ -341,6 +348,24 @@ def distortion_score(P, cams, bg, mode_kw):
     return {"train_distortion_mean": float(torch.stack(means).double().mean().item())}
 
 
+def normal_consistency_score(P, cams, bg, mode_kw, alpha_min):
+    """{"train_normal_consistency_deg": the mean angle in degrees between N / |N|, N the blended image of the Gaussians' own normals
+    (include/gsr_normal_render.h), and the normals of the rendered depth, over the counted pixels of all views (None: no such pixel)}"""
+    total, count = 0.0, 0
+    for c in cams:
+        H, W = c["height"], c["width"]
+        _, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
+        nimg = gsr.normal_render.render_normals(gsr.normal_render.gaussian_normals(P["scales"], P["rotations"], P["positions"], c), buf, H, W)
+        n_d, valid = gsr.normals.normals_from_depth(dep.reshape(H, W), buf["final_Ts"].reshape(H, W), c, alpha_min)
+        length = nimg.norm(dim=-1)
+        counted = (valid > 0) & (length >= gsr._lib.NORMAL_RENDER_MIN_LENGTH)
+        if bool(counted.any()):
+            cos = ((n_d.double() * nimg.double()).sum(-1)[counted] / length.double()[counted]).clamp(-1.0, 1.0)
+            total += float(torch.rad2deg(torch.acos(cos)).sum().item())
+            count += int(counted.sum().item())
+    return {"train_normal_consistency_deg": total / count if count else None}
+
+
 def pose_errors(run):
     """--pose-noise-* / --optimize-poses: every view's error against the dataset poses (degrees, scene units) at the start and now"""
     V = run.views
@@ -385,6 +410,8 @@ def finish(run, wall):
         summary.update(normal_scores(P, cams, V.clean_normal_targets, V.normal_rots, bg, mode_kw, args.normal_alpha_min))
     if args.lambda_dist > 0.0 or args.report_distortion:
         summary.update(distortion_score(P, cams, bg, mode_kw))
+    if args.lambda_normal_consistency > 0.0 or args.report_normal_consistency:
+        summary.update(normal_consistency_score(P, cams, bg, mode_kw, args.normal_alpha_min))
     if args.holdout and args.dataset:
         split, _, k = args.holdout.partition(":")
         hc, ht = load_nerf(args.dataset, int(k or 8), split)
@@ -495,6 +522,12 @@ def parse_args(argv=None):
     ap.add_argument("--dist-from-iter", type=int, default=0, metavar="K", help="--lambda-dist acts from iteration K on")
     ap.add_argument("--report-distortion", action="store_true", help="the summary reports train_distortion_mean (the mean of the "
                     "distortion image over pixels and views at the end) also without --lambda-dist")
+    ap.add_argument("--lambda-normal-consistency", type=float, default=0.0, metavar="W", help="weight of the depth-normal consistency term: W "
+                    "times the mean over the pixels of 1 - n_d . N / |N|, N the blended image of the Gaussians' own normals (the direction of each "
+                    "Gaussian's shortest axis), n_d the normals of the rendered depth (include/gsr_normal_render.h); no target needed")
+    ap.add_argument("--normal-consistency-from-iter", type=int, default=0, metavar="K", help="--lambda-normal-consistency acts from iteration K on")
+    ap.add_argument("--report-normal-consistency", action="store_true", help="the summary reports train_normal_consistency_deg (the mean angle "
+                    "between N / |N| and n_d over counted pixels and views at the end) also without --lambda-normal-consistency")
     ap.add_argument("--normal-dir", default=None, help="with --dataset: one float32 (H, W, 3) normal .npy per frame, named after its "
                     "file_path (without --dataset the normals of the hidden scene's own depth are the targets)")
     ap.add_argument("--normal-space", default="camera", choices=["camera", "world"], help="the space of --normal-dir's vectors: camera "
@@ -610,6 +643,8 @@ def check_args(args):
         (not (args.normal_noise >= 0.0 and finite(args.normal_noise)), "--normal-noise must be >= 0 and finite"),
         (not (args.lambda_dist >= 0.0 and finite(args.lambda_dist)), "--lambda-dist must be >= 0 and finite"),
         (not args.dist_from_iter >= 0, "--dist-from-iter must be >= 0"),
+        (not (args.lambda_normal_consistency >= 0.0 and finite(args.lambda_normal_consistency)), "--lambda-normal-consistency must be >= 0 and finite"),
+        (not args.normal_consistency_from_iter >= 0, "--normal-consistency-from-iter must be >= 0"),
         (not finite(args.normal_alpha_min), "--normal-alpha-min must be finite"),
         (args.normal_dir and not args.dataset, "--normal-dir needs --dataset (the targets are named after its frames)"),
         (args.lambda_normal > 0.0 and args.dataset and not args.normal_dir, "--lambda-normal with --dataset needs --normal-dir (normal targets)"),
@@ -769,7 +804,7 @@ def new_run(args, dev, rank, world, views, P, init_info):
         # basis x payload inside the SH update (optimizer.adam_update(sh_views=...)) -- also with one rank.  --dense-sh keeps the
         # 48-float path.
         factored=not args.dense_sh, dssim=dssim, screen_stats=args.densify_stat == "screen", abs_kw={"absgrad": True} if args.absgrad else {},
-        aux=args.lambda_depth > 0.0 or args.lambda_alpha > 0.0 or args.lambda_normal > 0.0,
+        aux=args.lambda_depth > 0.0 or args.lambda_alpha > 0.0 or args.lambda_normal > 0.0 or args.lambda_normal_consistency > 0.0,
         sched={k: gsr.scheduler.LRScheduler(lr) for k, lr in gsr.optimizer.DEFAULT_LR.items()},
         rng=np.random.default_rng(0),                                       # same stream on every rank -> same view batch
         per_rank_views=per_rank_views, streams_few=gsr.dist.ViewStreams(1, dev),
@@ -869,6 +904,17 @@ def train_view(run, it, v, alone, capacity=None):
         dist_image, moments = gsr.distortion.render_distortion(buf, c["height"], c["width"])
         kw["dL_ddistortion"] = gsr.loss.distortion_loss_and_gradients(dist_image, None, args.lambda_dist)[1]
         kw["distortion_moments"] = moments
+    if args.lambda_normal_consistency > 0.0 and it >= args.normal_consistency_from_iter:
+        # the Gaussians' own normals against the normals of the rendered depth, the gradient on both sides: the depth side's two
+        # images are ADDED to the terms' above, the normal image's gradient is a stage of the backward (like the distortion's)
+        H, W = c["height"], c["width"]
+        gn = gsr.normal_render.gaussian_normals(P["scales"], P["rotations"], P["positions"], c)
+        nimg = gsr.normal_render.render_normals(gn, buf, H, W)
+        _, gN, gD, gA = gsr.loss.normal_consistency_loss_and_gradients(nimg, dep.reshape(H, W), buf["final_Ts"].reshape(H, W), c, None,
+                                                                       args.lambda_normal_consistency, args.normal_alpha_min)
+        kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in kw else kw["dL_ddepth_image"].reshape(gD.shape) + gD
+        kw["dL_dalpha_image"] = gA if "dL_dalpha_image" not in kw else kw["dL_dalpha_image"].reshape(gA.shape) + gA
+        kw.update(dL_dnormal_image=gN, gaussian_normals=gn, normal_image=nimg)
     if expo is not None:                                                # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
         dpix, dE = gsr.exposure.exposure_backward(raw, expo.matrix(v), dpix, out=dpix)
     if run.aux:                                                         # the forward's depths: records re-packed with 1/depth
