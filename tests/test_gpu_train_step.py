@@ -6,7 +6,7 @@ The trainer's stage functions are driven in-process, in main()'s order, at the s
 4 views, two iterations.  gsr.render_view and gsr.backward_view are wrapped to record, per call, the view, what the render
 returned, the three cotangent images as they arrive at the backward and what the backward returned.
 
-For every view of both iterations of the configurations S1-S5 (CONFIGS):
+For every view of both iterations of the configurations S1-S5 and S7-S11 (CONFIGS):
   frame        the captured image / inverse depth / final_T meet the float64 forward of the parameters under the run's modes:
                test_f64_reference.check_forward unchanged in the classic mode; under the antialiased mode or the 3D filter (whose
                per-Gaussian opacity the float64 side does not hold bit for bit) its image criteria against the float64 forward of the
@@ -22,13 +22,31 @@ For every view of both iterations of the configurations S1-S5 (CONFIGS):
                sh_views and sh_scale show.
   S2           the stepped view's exposure row against exposure_reference.adam_f64 of the float64 dE; pose.m / 0.1 after a view's
                first step against the float64 dL/dxi; pose.t = the number of iterations that drew the view.
-  statistics   S2, S4: model.stats.vis_count = the number of batch views with radii > 0, per Gaussian, exactly.
+  statistics   S2, S4, S9: model.stats.vis_count = the number of batch views with radii > 0, per Gaussian, exactly.
+S7-S11 run the depth-distortion (--lambda-dist) and depth-normal consistency (--lambda-normal-consistency) terms, whose gradient is a
+stage of the backward switched on by five keywords (TERM_KW); the recorder also wraps distortion.render_distortion and
+normal_render.render_normals and clones those keywords.  S7: distortion with D-SSIM, two views and poses; S8: consistency with all
+four writers of gD / gA, dense SH; S9: both under the antialiased mode, the 3D filter, poses, exposure and screen statistics; S10:
+both from iteration 1 on (iteration 0 carries none of the keywords and meets the statement without the terms; after the opacity
+reset --normal-alpha-min 0.01 keeps the consistency term alive, and the distortion weight is 1e5 there); S11: both under
+--capacity with a forced overflow.  The weights are those tests/test_step_reference.py settles.  In addition, per view:
+  frame        the captured normal image against the float64 blend of the float64 normals over the frame's lists
+               (parity.assert_image); the captured distortion image against float64 by tests/test_gpu_distortion.py check 1,
+               E_kernel <= 3 E_f32 + floor in units of 1 + mu / sigma, E_f32 of distortion_reference.forward_f32 on the frame.
+  image half   the five keywords present exactly when the statement has the term at that iteration; dL_ddistortion exactly the
+               constant; gN within step_reference.image_half_bounds (pixels within 1e-6 of the length threshold aside); gD / gA
+               within the extended bounds.
+  per view, batch, Adam, pose   as above: the float64 side now includes the terms (their cotangents go to param_half and
+               pose_gradient_f64; the normals are constants of the camera, the library's contract).
+Four deliberate breaks of train_view were run against these on the MI355X, each in a scratch copy: the consistency term's gA
+dropped (S8 fails at image half gA), its gD assigned instead of added (S8, image half gD), --dist-from-iter ignored (S10, the
+keywords at iteration 0), normal_param_grad=False (S8, per-view rotations).
 Paths: three streams against the serial loop, capacity mode and its overflow re-run against the sized path (iteration 0 of each:
-the same parameters exactly), and 17 views per step factored against --dense-sh.  S6: a pose takes one step per iteration and
+the same parameters exactly; once plain and once with both regularisers on), and 17 views per step factored against --dense-sh.  S6: a pose takes one step per iteration and
 view under --capacity, from the frame that did not overflow.
 
 tests/golden/step_margins.json records the worst measured ratio of every assertion against its bound, written on the first device
-run when absent.  It is not the bound: with the file present a ratio above 10 x its recorded value fails even below 1.  Recorded
+run when absent; a configuration with no row on file has its rows appended, a key missing from a configuration on file fails.  It is not the bound: with the file present a ratio above 10 x its recorded value fails even below 1.  Recorded
 values below NOISE count as NOISE there: S6's figure (two runs whose pose steps are lr against the sign of the same gradient) is
 1e-13 of its bound, the float64 rounding of the host's pose arithmetic, which repeats to no factor at all; and a recorded share of
 exactly zero elements outside a band leaves the band's own cap as the check.
@@ -44,10 +62,12 @@ import torch
 
 from conftest import ROOT
 import adam_reference as A
+import distortion_reference as DR
 import exposure_reference as XR
 import parity
 import step_reference as S
 import test_f64_reference as R
+from test_step_reference import LAMBDA_DIST, LAMBDA_NC, S10_ALPHA_MIN, S10_LAMBDA_DIST
 
 pytestmark = pytest.mark.gpu
 MARGINS = os.path.join(ROOT, "tests", "golden", "step_margins.json")
@@ -56,6 +76,7 @@ CAMERA_TRIP = 8.9e-4         # tests/test_gpu_camera_grads.py TRIP: |kernel - f6
 ROUND = 2.0 ** -23
 NOISE = 1e-6                 # recorded ratios below this are rounding noise of float64 host arithmetic, not measurements (module docstring)
 COMMON = ["--size", "44", "--gaussians", "600", "--views", "4", "--init", "random", "--print-interval", "1000", "--iterations", "2"]
+BOTH = ["--lambda-dist", str(LAMBDA_DIST), "--lambda-normal-consistency", str(LAMBDA_NC)]
 CONFIGS = {
     "S1": [],
     "S2": ["--lambda-dssim", "0.2", "--lambda-depth", "0.5", "--lambda-alpha", "0.1", "--lambda-normal", "0.05", "--optimize-exposure",
@@ -66,7 +87,17 @@ CONFIGS = {
     "S4": ["--views-per-step", "4", "--view-streams", "3", "--lambda-dssim", "0.2", "--lambda-alpha", "0.1", "--densify-stat", "screen"],
     "S5": ["--capacity", "--views-per-step", "2", "--lambda-dssim", "0.2"],
     "S5k": ["--capacity", "--capacity-initial", "64", "--views-per-step", "2", "--lambda-dssim", "0.2"],
+    # the distortion and consistency terms (weights: tests/test_step_reference.py, where each term's share of the gradient is held)
+    "S7": ["--lambda-dist", str(LAMBDA_DIST), "--lambda-dssim", "0.2", "--views-per-step", "2", "--optimize-poses", "--pose-noise-deg", "1"],
+    "S8": ["--lambda-normal-consistency", str(LAMBDA_NC), "--lambda-normal", "0.05", "--normal-noise", "0.1", "--lambda-depth", "0.5",
+           "--lambda-alpha", "0.1", "--dense-sh"],
+    "S9": BOTH + ["--rasterize-mode", "antialiased", "--filter-3d", "--optimize-poses", "--pose-noise-deg", "1", "--optimize-exposure",
+                  "--exposure-noise", "0.2", "--densify-stat", "screen", "--absgrad"],
+    "S10": ["--lambda-dist", str(S10_LAMBDA_DIST), "--lambda-normal-consistency", str(LAMBDA_NC), "--dist-from-iter", "1",
+            "--normal-consistency-from-iter", "1", "--normal-alpha-min", str(S10_ALPHA_MIN)],
+    "S11": BOTH + ["--capacity", "--capacity-initial", "64", "--views-per-step", "2"],
 }
+TERM_KW = ("dL_ddistortion", "distortion_moments", "dL_dnormal_image", "gaussian_normals", "normal_image")
 S6 = ["--capacity", "--capacity-initial", "64", "--optimize-poses", "--pose-noise-deg", "1"]
 
 
@@ -77,29 +108,41 @@ def test_the_copied_bounds_are_their_owners():
     import test_gpu_weighted_loss
     assert SPREAD_FLOOR == test_gpu_aux_grads.SPREAD_FLOOR and CAMERA_TRIP == pytest.approx(test_gpu_camera_grads.TRIP, rel=1e-12)
     assert S.DSSIM_GRAD_TOL == test_gpu_dssim.GRAD_TOL and S.WEIGHTED_GRAD_CEILING == test_gpu_weighted_loss.GRAD_CEILING
+    import test_step_reference
+    assert test_step_reference.CAMERA_TRIP == CAMERA_TRIP
 
 
 # ------------------------------------------------------------------------------------------------------------- the margins file
-_CREATED = {}
+def config_of(key):
+    """The configuration a margin row belongs to: its first component, for the path tests the first two."""
+    parts = key.split("/")
+    return "/".join(parts[:2]) if parts[0] == "paths" else parts[0]
 
 
 def settle(worst):
-    """Print the worst ratios of a test and hold them to the record: absent, they are written (merged with what this process wrote
-    before); present, none may exceed 10 x its recorded value."""
+    """Print the worst ratios of a test and hold them to the record.  A configuration with no row at all on file has its rows
+    appended (the file is created when absent); a configuration that is on file must have every key there, and none may exceed
+    10 x its recorded value.  Recorded values are never changed."""
     print("\nworst ratios against the bounds: " + json.dumps({k: float(f"{v:.3g}") for k, v in sorted(worst.items())}))
-    if os.path.exists(MARGINS) and not _CREATED:
+    doc = {"_note": "worst: the largest measured ratio of each assertion of tests/test_gpu_train_step.py against its bound (<= 1 passes), "
+                    "over the views and iterations of the configuration, measured on an MI355X against tests/step_reference.py.  It is "
+                    "a record of what was measured, not the bound; a later run fails above 10 x a value", "worst": {}}
+    if os.path.exists(MARGINS):
         with open(MARGINS) as f:
-            rec = json.load(f)["worst"]
-        for k, v in worst.items():
-            assert k in rec, f"{k} has no recorded margin in {MARGINS}"
-            assert v <= 10.0 * max(rec[k], NOISE) or (rec[k] == 0.0 and v <= 1.0), f"{k}: ratio {v:.3g} against its bound, recorded {rec[k]:.3g}"
-        return
-    _CREATED.update(worst)
-    with open(MARGINS, "w") as f:
-        json.dump({"_note": "worst: the largest measured ratio of each assertion of tests/test_gpu_train_step.py against its bound (<= 1 passes), "
-                            "over the views and iterations of the configuration, measured on an MI355X against tests/step_reference.py.  It is "
-                            "a record of what was measured, not the bound; a later run fails above 10 x a value",
-                   "worst": {k: _CREATED[k] for k in sorted(_CREATED)}}, f, indent=1)
+            doc = json.load(f)
+    rec = doc["worst"]
+    on_file = {config_of(k) for k in rec}
+    new = {k: v for k, v in worst.items() if config_of(k) not in on_file}
+    for k, v in worst.items():
+        if k in new:
+            continue
+        assert k in rec, f"{k} has no recorded margin in {MARGINS}"
+        assert v <= 10.0 * max(rec[k], NOISE) or (rec[k] == 0.0 and v <= 1.0), f"{k}: ratio {v:.3g} against its bound, recorded {rec[k]:.3g}"
+    if new:
+        rec.update(new)
+        doc["worst"] = {k: rec[k] for k in sorted(rec)}
+        with open(MARGINS, "w") as f:
+            json.dump(doc, f, indent=1)
 
 
 def keep(worst, key, ratio):
@@ -128,6 +171,22 @@ class Recorder:
     def __init__(self, T, run, monkeypatch):
         self.calls, self.run = [], run
         render, backward = T.gsr.render_view, T.gsr.backward_view
+        render_distortion, render_normals = T.gsr.distortion.render_distortion, T.gsr.normal_render.render_normals
+        of_frame = lambda buffers: next((c for c in reversed(self.calls) if c["frame_buf"] is buffers), None)
+
+        def distortion(buffers, *args, **kw):
+            out = render_distortion(buffers, *args, **kw)
+            call = of_frame(buffers)
+            if call is not None:
+                call.update(dist=out[0].clone(), moments=out[1].clone())
+            return out
+
+        def normals(gn, buffers, *args, **kw):
+            out = render_normals(gn, buffers, *args, **kw)
+            call = of_frame(buffers)
+            if call is not None:
+                call.update(nimg=out.clone())
+            return out
 
         def render_view(params, camera, background, **kw):
             out = render(params, camera, background, **kw)
@@ -144,7 +203,9 @@ class Recorder:
             if call is None:
                 return backward(params, camera, background, buffers, dL_dpixels, **kw)
             clone = lambda t: None if t is None else t.clone()
-            call.update(dpix=clone(dL_dpixels), gD=clone(kw.get("dL_ddepth_image")), gA=clone(kw.get("dL_dalpha_image")), kw=kw)
+            # (clones: the trainer's tensors are workspace the next view's calls write again)
+            call.update(dpix=clone(dL_dpixels), gD=clone(kw.get("dL_ddepth_image")), gA=clone(kw.get("dL_dalpha_image")),
+                        kw=dict(kw, **{k: clone(kw.get(k)) for k in TERM_KW}))
             g = backward(params, camera, background, buffers, dL_dpixels, **kw)
             call["out"] = {k: g[k].clone() for k in self.OUT if g.get(k) is not None}     # (the arena is summed in place later)
             return g
@@ -159,6 +220,8 @@ class Recorder:
         monkeypatch.setattr(T.gsr, "render_view", render_view)
         monkeypatch.setattr(T.gsr, "backward_view", backward_view)
         monkeypatch.setattr(T.gsr.optimizer, "adam_update", adam_update)
+        monkeypatch.setattr(T.gsr.distortion, "render_distortion", distortion)
+        monkeypatch.setattr(T.gsr.normal_render, "render_normals", normals)
 
     def take(self):
         """The calls since the last take(), as numpy."""
@@ -170,6 +233,12 @@ class Recorder:
                  "buf": {k: to_np(t) for k, t in c["buf"].items()}, "out": {k: to_np(t) for k, t in c["out"].items()}}
             for k, shape in (("dpix", (H, W, 3)), ("gD", (H, W)), ("gA", (H, W))):
                 d[k] = None if c[k] is None else to_np(c[k]).reshape(shape)
+            d["term_kw"] = sorted(k for k in TERM_KW if c["kw"].get(k) is not None)
+            for k, src, shape in (("g_dist", "dL_ddistortion", (H, W)), ("gN", "dL_dnormal_image", (H, W, 3)), ("normals32", "gaussian_normals", (-1, 3)),
+                                  ("kw_nimg", "normal_image", (H, W, 3)), ("kw_moments", "distortion_moments", (H, W, 4))):
+                d[k] = None if c["kw"].get(src) is None else to_np(c["kw"][src]).reshape(shape)
+            for k, shape in (("dist", (H, W)), ("moments", (H, W, 4)), ("nimg", (H, W, 3))):
+                d[k] = None if c.get(k) is None else to_np(c[k]).reshape(shape)
             out.append(d)
         self.calls = []
         return out
@@ -207,7 +276,7 @@ def step(T, run, rec, it):
     return snap, rec.take()
 
 
-def targets_of(run, v, E):
+def targets_of(run, v, E, it):
     V, a = run.views, run.args
     tg = {"target": to_np(V.targets[v]), "weights": to_np(V.weights[v].weights) if V.weights is not None else None, "E": E}
     if a.lambda_depth > 0.0:
@@ -217,7 +286,8 @@ def targets_of(run, v, E):
     if a.lambda_normal > 0.0:
         tg.update(normal_target=to_np(V.normal_targets[v]), normal_rot=V.normal_rots[v])
     cfg = {"lam": a.lambda_dssim, "window": a.ssim_window, "lam_d": a.lambda_depth, "depth_loss": a.depth_loss, "lam_a": a.lambda_alpha,
-           "lam_n": a.lambda_normal, "alpha_min": a.normal_alpha_min}
+           "lam_n": a.lambda_normal, "alpha_min": a.normal_alpha_min, "lam_dist": a.lambda_dist, "lam_nc": a.lambda_normal_consistency,
+           "dist_from_iter": a.dist_from_iter, "nc_from_iter": a.normal_consistency_from_iter, "it": it}
     return tg, cfg
 
 
@@ -243,11 +313,51 @@ def check_frame(call, pre, mode, filtered, worst):
         keep(worst, "frame/" + k + "_outside_tight", (1.0 - rep[k][0]) / (1.0 - 0.999))
 
 
-def check_image_half(run, call, E, worst, alive):
+def check_term_frame(call, snap, pre, mode, worst):
+    """The frame's two further images: the captured normal image against the float64 blend of the float64 normals of the
+    parameters over the frame's lists (parity.assert_image), and the captured distortion image against the float64 Dist on the
+    frame's buffers by tests/test_gpu_distortion.py check 1: E_kernel <= 3 E_f32 + floor in units of 1 + mu / sigma, E_f32 of
+    distortion_reference.forward_f32 on this frame.  What the backward was handed is what those calls returned.  Returns the
+    float64 normals (None without the consistency term)."""
+    H, W = call["dep"].shape
+    normals = None
+    if call["nimg"] is not None:
+        normals, flipped = S.gaussian_normals_f64(snap["P"], call["cam"], captured=call["normals32"])
+        assert np.array_equal(call["kw_nimg"], call["nimg"])
+        n64 = S.regulariser_images_f64(pre, call["buf"]["point_list"], call["buf"]["ranges"], mode, normals)[1]
+        rep = parity.assert_image("normal_image", call["nimg"], n64)
+        keep(worst, "frame/normal_image_flips", rep[2] / max(2, int(parity.IMG_FLIP_FRAC * call["dep"].size)))
+        keep(worst, "frame/normal_image_outside_tight", (1.0 - rep[0]) / (1.0 - 0.999))
+    if call["dist"] is not None:
+        assert np.array_equal(call["kw_moments"], call["moments"])
+        r = DR.moments_f64(call["buf"], W, H)
+        E_k, E_32 = DR.forward_error(call["dist"], r), DR.forward_error(DR.forward_f32(call["buf"], W, H)[0], r)
+        bound = 3.0 * E_32 + DR.golden()["floor"]["forward"]
+        print(f"    view {call['v']}: Dist error {E_k:.3e} (1 + mu / sigma), float32 restatement {E_32:.3e}, max Dist {r['dist'].max():.3e}")
+        keep(worst, "frame/dist", E_k / bound)
+        assert E_k <= bound and r["dist"].max() > 0, (E_k, E_32)
+    return normals
+
+
+def check_image_half(run, call, E, worst, alive, it=0):
     """`alive`: every term that is switched on must be non-zero (iteration 0; the opacity reset that ends it leaves frames too faint
     for a depth normal, and the normal term's images are then zero on both sides)."""
-    tg, cfg = targets_of(run, call["v"], E)
-    res = S.image_half({"img": call["img"], "dinv": call["dep"], "final_T": call["buf"]["final_Ts"], "cam": call["cam"]}, tg, cfg)
+    tg, cfg = targets_of(run, call["v"], E, it)
+    res = S.image_half({"img": call["img"], "dinv": call["dep"], "final_T": call["buf"]["final_Ts"], "cam": call["cam"], "nimg": call["nimg"]}, tg, cfg)
+    # the two regularisers: present exactly from their start iterations on, all five keywords or none of a term's
+    want = (["dL_ddistortion", "distortion_moments"] if res["g_dist"] is not None else []) + \
+           (["dL_dnormal_image", "gaussian_normals", "normal_image"] if res["gN"] is not None else [])
+    assert call["term_kw"] == sorted(want), (it, call["term_kw"], want)
+    if res["g_dist"] is not None:                                                    # one torch.full: exactly the constant
+        assert np.array_equal(call["g_dist"].astype(np.float64), res["g_dist"]) and res["g_dist"].max() > 0
+    if res["gN"] is not None:
+        b = S.image_half_bounds(res, tg, cfg)["gN"]
+        far = ~res["near"]
+        assert res["near"].mean() <= 1e-2 and np.array_equal(call["gN"][far & ~res["counted"]], np.zeros_like(call["gN"][far & ~res["counted"]]))
+        e = np.abs(call["gN"].astype(np.float64) - res["gN"])[far].max()
+        print(f"    view {call['v']}: gN err {e:.3e} (bound {b:.3e}, max {np.abs(res['gN']).max():.3e}, {int(res['counted'].sum())} pixels count)")
+        keep(worst, "image/gN", e / b if b > 0 else float(e > 0))
+        assert e <= b and (np.abs(res["gN"]).max() > 0 or not alive), ("gN", e, b)
     bounds = S.image_half_bounds(res, tg, cfg)
     ties = S.tie_pixels(call["img"], E, tg["target"])
     assert ties.mean() <= 1e-3, f"{ties.sum()} pixels on a sign tie"
@@ -358,13 +468,13 @@ def check_exposure(run, snap, call, res, tg, it, worst):
     assert np.array_equal(to_np(run.expo.E)[others], snap["E"][others])
 
 
-def check_pose(T, run, snap, call, mode, worst):
+def check_pose(T, run, snap, call, mode, worst, normals=None):
     v = call["v"]
     if snap["pose_t"][v] != 0:
         return
     dxi, reach = S.pose_gradient_f64(snap["P"], snap["start_cams"][v], snap["xi"][v], call["buf"]["radii"], call["buf"]["point_list"],
                                      call["buf"]["ranges"], call["dpix"], call["gD"], call["gA"], rasterize_mode=mode, filter_3d=snap["filter"],
-                                     apply_pose_delta=T.gsr.pose.apply_pose_delta)
+                                     apply_pose_delta=T.gsr.pose.apply_pose_delta, g_dist=call["g_dist"], gN=call["gN"], normals=normals)
     got = run.pose.m[v] / 0.1
     r = float((np.abs(got - dxi) / (CAMERA_TRIP * reach)).max())
     print(f"    view {v}: dL/dxi {np.array2string(dxi, precision=3)} err/bound {r:.3g}")
@@ -374,7 +484,7 @@ def check_pose(T, run, snap, call, mode, worst):
 
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_train_step_against_float64(name, monkeypatch):
-    T, run, rec = start(CONFIGS[name], monkeypatch, s2_prepare if name == "S2" else None)
+    T, run, rec = start(CONFIGS[name], monkeypatch, s2_prepare if name in ("S2", "S9") else None)
     a = run.args
     mode, dense, worst = a.rasterize_mode, a.dense_sh, {}
     drawn = [0] * len(run.views.cams)
@@ -393,15 +503,16 @@ def test_train_step_against_float64(name, monkeypatch):
             filt = snap["filter"]
             pre = S.preprocess(snap["P"], call["cam"], mode, filt)
             check_frame(call, pre, mode, filt is not None, worst)
+            normals = check_term_frame(call, snap, pre, mode, worst)
             E = snap["E"][v] if run.expo is not None else None
-            res, tg = check_image_half(run, call, E, worst, alive=it == 0)
+            res, tg = check_image_half(run, call, E, worst, alive=it == 0 or name == "S10", it=it)
             v64 = S.param_half(snap["P"], call["cam"], call["buf"]["point_list"], call["buf"]["ranges"], call["dpix"], call["gD"], call["gA"],
-                               rasterize_mode=mode, filter_3d=filt, pre=pre)
+                               rasterize_mode=mode, filter_3d=filt, pre=pre, g_dist=call["g_dist"], gN=call["gN"], normals=normals)
             check_view_gradients(call, v64, dense, worst)
             if run.expo is not None:
                 check_exposure(run, snap, call, res, tg, it, worst)
             if a.optimize_poses:
-                check_pose(T, run, snap, call, mode, worst)
+                check_pose(T, run, snap, call, mode, worst, normals)
             views64.append(v64)
             batch.append(v)
             drawn[v] += 1
@@ -419,7 +530,7 @@ def test_train_step_against_float64(name, monkeypatch):
             assert list(run.pose.t) == drawn, (run.pose.t, drawn)
     if name == "S5":
         assert run.cap["K"] is not None and not run.capacity_log                # sized iteration 0, capacity-mode iteration 1, no overflow
-    if name == "S5k":
+    if name in ("S5k", "S11"):
         # (K = 64 overflows on the step's first view; the re-run grows K, so the views after it may fit)
         assert (run.capacity_log[0]["iteration"], run.capacity_log[0]["capacity"]) == (0, 64) and all(r["D"] > r["capacity"] for r in run.capacity_log)
     settle({f"{name}/{k}": v for k, v in worst.items()})
@@ -450,17 +561,18 @@ def test_three_streams_give_the_serial_loops_gradients(monkeypatch):
 
 
 def test_capacity_mode_and_its_overflow_rerun_give_the_sized_paths_gradients(monkeypatch):
-    base = ["--views-per-step", "2", "--lambda-dssim", "0.2"]
-    _, sized = first_step_grads(base, monkeypatch)
-    r_cap, cap = first_step_grads(base + ["--capacity", "--capacity-initial", "1000000"], monkeypatch)
-    r_over, over = first_step_grads(base + ["--capacity", "--capacity-initial", "64"], monkeypatch)
-    assert not r_cap.capacity_log and r_over.capacity_log and r_over.capacity_log[0]["capacity"] == 64
-    for r in r_over.capacity_log:                                       # (the re-run grows K: the step's second view may fit)
-        assert r["iteration"] == 0 and r["D"] > r["capacity"]
-    assert r_over.cap["K"] == -(-5 * r_over.capacity_log[-1]["D"] // 4) >= r_over.cap["max_D"]     # K grew at the last overflow, to 1.25 x its D
     worst = {}
-    spread(worst, "paths/capacity", cap, sized)
-    spread(worst, "paths/overflow_rerun", over, sized)
+    # (the second base: both regularisers on -- their stages bound every walk by the capacity, so this is a designed path)
+    for tag, base in (("", ["--views-per-step", "2", "--lambda-dssim", "0.2"]), ("_terms", ["--views-per-step", "2", "--lambda-dssim", "0.2"] + BOTH)):
+        _, sized = first_step_grads(base, monkeypatch)
+        r_cap, cap = first_step_grads(base + ["--capacity", "--capacity-initial", "1000000"], monkeypatch)
+        r_over, over = first_step_grads(base + ["--capacity", "--capacity-initial", "64"], monkeypatch)
+        assert not r_cap.capacity_log and r_over.capacity_log and r_over.capacity_log[0]["capacity"] == 64
+        for r in r_over.capacity_log:                                       # (the re-run grows K: the step's second view may fit)
+            assert r["iteration"] == 0 and r["D"] > r["capacity"]
+        assert r_over.cap["K"] == -(-5 * r_over.capacity_log[-1]["D"] // 4) >= r_over.cap["max_D"]     # K grew at the last overflow, to 1.25 x its D
+        spread(worst, "paths/capacity" + tag, cap, sized)
+        spread(worst, "paths/overflow_rerun" + tag, over, sized)
     settle(worst)
 
 
