@@ -313,6 +313,21 @@ MESH_GROUP_CELLS = 256              # GSR_MESH_GROUP_CELLS
 MESH_SCAN_GROUPS = 1024             # GSR_MESH_SCAN_GROUPS
 MESH_DIRECTIONS = 7                 # GSR_MESH_DIRECTIONS
 
+# include/gsr_mesh_eval.h: points sampled on a triangle mesh by area and the exact nearest neighbour across two point sets, what the
+# accuracy / completeness / F-score of an extracted mesh are made of (its own header, so its own table)
+MESH_EVAL_EXPORTS = {
+    "gsr_nearest_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "gsr_nearest": (C.c_int, [C.c_int64, vp, C.c_int64, vp, C.c_float, vp, vp, vp, C.c_size_t, vp]),
+    "gsr_surface_sample_workspace_bytes": (C.c_size_t, [C.c_int64]),
+    "gsr_surface_sample_count": (C.c_int, [C.c_int64, vp, C.c_float, C.c_uint32, vp, vp, C.c_size_t, vp]),
+    "gsr_surface_sample_emit": (C.c_int, [C.c_int64, vp, vp, C.c_uint32, C.c_int64, vp, vp, vp]),
+}
+NEAREST_BLOCK_POINTS = 256                  # GSR_NEAREST_BLOCK_POINTS
+NEAREST_MAX_POINTS = 1 << 27                # GSR_NEAREST_MAX_POINTS
+SURFACE_SAMPLE_MAX_TRIANGLES = 1 << 27      # GSR_SURFACE_SAMPLE_MAX_TRIANGLES
+SURFACE_SAMPLE_MAX_SAMPLES = 1 << 27        # GSR_SURFACE_SAMPLE_MAX_SAMPLES
+SURFACE_SAMPLE_MAX_PER_TRIANGLE = 1 << 20   # GSR_SURFACE_SAMPLE_MAX_PER_TRIANGLE
+
 # include/gsr_debug_layout.h: where the forward's tile-order tables lie inside the geom workspace, for tests and tools (its own
 # header, so its own table)
 DEBUG_LAYOUT_EXPORTS = {
@@ -350,7 +365,7 @@ def lib():
                                   + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
                                   + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
                                   + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())
-                                  + list(NORMAL_RENDER_EXPORTS.items())):
+                                  + list(NORMAL_RENDER_EXPORTS.items()) + list(MESH_EVAL_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

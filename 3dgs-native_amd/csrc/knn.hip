@@ -16,12 +16,16 @@
 //                                            distance; for each block that passed, every thread tests ITS point against the box with its
 //                                            current third best and the workgroup votes: a block some query needs is staged through
 //                                            LDS, and the threads that need it scan it.
+//   nearest_search_kernel                    the nearest point of ANOTHER set (include/gsr_mesh_eval.h, gsr_nearest): both sets through
+//                                            the same chain under one common box, then the same walk with one best instead of three,
+//                                            seeded by a binary search over the sorted reference codes.
 // Nothing but pruning depends on the Morton order: every distance is the header's float32 expression, every comparison is by (d2, id).
 #include <limits.h>
 #include <math.h>
 
 #include "gsr_internal.h"
 #include "gsr_knn.h"
+#include "gsr_mesh_eval.h"
 
 namespace {
 
@@ -368,6 +372,157 @@ KnnWs carve(void *base, int64_t N)
     return w;
 }
 
+// The Morton items of `points` under *box in item[0], sorted: four 8-bit digits cover the 30 bits of code, and an even count of
+// passes ends in item[0].  One chain for both stages of this file.
+bool sort_by_morton(int64_t N, const float *points, const Box *box, uint64_t *const item[2], int32_t *hist, int32_t *start, int32_t *scan_tmp,
+                    hipStream_t s)
+{
+    const int blocks = (int)gsr_div_up(N, NT), chunks = (int)gsr_div_up(N, SORT_CHUNK);
+    hipLaunchKernelGGL(knn_morton_kernel, dim3(blocks), dim3(NT), 0, s, N, points, box, item[0]);
+    for (int pass = 0; pass < 4; ++pass) {
+        const uint64_t *src = item[pass & 1];
+        hipLaunchKernelGGL(knn_hist_kernel, dim3(chunks), dim3(NT), 0, s, N, src, 8 * pass, hist);
+        if (gsr_launch_exclusive_scan(hist, start, scan_tmp, (int64_t)256 * chunks, s) != hipSuccess) return false;
+        hipLaunchKernelGGL(knn_scatter_kernel, dim3(chunks), dim3(NT), 0, s, N, src, item[(pass & 1) ^ 1], 8 * pass, (const int32_t *)start);
+    }
+    return true;
+}
+
+// ---- the nearest point of ANOTHER set (include/gsr_mesh_eval.h) ----
+// Both sets go through the chain above under one box, so equal codes are equal cells.  One workgroup per block of 256 sorted
+// queries, one query per thread.  The walk over the reference blocks starts where a binary search places the middle query's code
+// among the sorted reference codes and goes outwards, s, s + 1, s - 1, ...: near places of the sorted order first, they shrink the
+// best distance soonest.  The two filters are knn_search_kernel's.  With one neighbour to keep, the best is two registers.
+static_assert(GSR_NEAREST_BLOCK_POINTS == NT, "one query per thread, one staged reference per thread");
+static_assert(GSR_NEAREST_MAX_POINTS == GSR_KNN_MAX_POINTS, "one count check for both stages");
+
+__device__ __forceinline__ void scan_staged_nearest(float &bd, int &bi, float3 q, const float4 *s_pts, int count)
+{
+    int k = 0;
+    for (; k + SCAN_UNROLL <= count; k += SCAN_UNROLL) {
+        float4 p[SCAN_UNROLL];
+#pragma unroll
+        for (int u = 0; u < SCAN_UNROLL; ++u) p[u] = s_pts[k + u];
+#pragma unroll
+        for (int u = 0; u < SCAN_UNROLL; ++u) {
+            const float d = dist2(__fsub_rn(q.x, p[u].x), __fsub_rn(q.y, p[u].y), __fsub_rn(q.z, p[u].z));
+            const int j = __float_as_int(p[u].w);
+            if (before(d, j, bd, bi)) bd = d, bi = j;
+        }
+    }
+    for (; k < count; ++k) {
+        const float4 p = s_pts[k];
+        const float d = dist2(__fsub_rn(q.x, p.x), __fsub_rn(q.y, p.y), __fsub_rn(q.z, p.z));
+        const int j = __float_as_int(p.w);
+        if (before(d, j, bd, bi)) bd = d, bi = j;
+    }
+}
+
+__global__ __launch_bounds__(NT) void nearest_search_kernel(int64_t M, int64_t N, int nbr, const float4 *__restrict__ qsorted, const Box *__restrict__ qboxes,
+                                                            const uint64_t *__restrict__ qitems, const float4 *__restrict__ rsorted,
+                                                            const Box *__restrict__ rboxes, const uint64_t *__restrict__ ritems, float max_dist2,
+                                                            float *__restrict__ dist2_out, int32_t *__restrict__ index_out /* may be NULL */)
+{
+    __shared__ float4 s_pts[NT];
+    __shared__ Box s_cbox[NT];
+    __shared__ int s_cand[NT];
+    __shared__ uint32_t s_kept[NT / 32];
+    const int t = threadIdx.x, b = blockIdx.x;
+    const int64_t slot = (int64_t)b * NT + t;
+    const bool active = slot < M;                              // a thread without a query stays: it serves every barrier and vote below
+    const float4 me = active ? qsorted[slot] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    const float3 q = make_float3(me.x, me.y, me.z);
+    const Box own = qboxes[b];                                 // (of the block's queries only: gather leaves the empty slots out)
+    // the cap is the first best: a candidate enters at d2 <= max_dist2 (INT_MAX is above every index), and it prunes from the start
+    float bd = max_dist2;
+    int bi = INT_MAX;
+
+    // the seed: the first place of the sorted references whose code is not below the middle query's (the same in every thread)
+    const int64_t mid = (int64_t)b * NT + min((int64_t)NT, M - (int64_t)b * NT) / 2;
+    const uint32_t qcode = (uint32_t)(qitems[mid] >> 32);
+    int64_t lo = 0, hi = N;
+    while (lo < hi) {
+        const int64_t m = lo + (hi - lo) / 2;
+        if ((uint32_t)(ritems[m] >> 32) < qcode) lo = m + 1;
+        else hi = m;
+    }
+    const int seed = __builtin_amdgcn_readfirstlane((int)min(lo / NT, (int64_t)nbr - 1));
+
+    // a thread without a query needs nothing: -1 is below every bound
+    float wg_best = block_max(active ? bd : -1.0f);
+    const int reach = max(seed, nbr - 1 - seed);
+    for (int k0 = 0; k0 <= 2 * reach; k0 += NT) {
+        const int k = k0 + t;
+        const int c = seed + ((k & 1) ? (k + 1) / 2 : -(k / 2));
+        int keep = -1;
+        if (k <= 2 * reach && c >= 0 && c < nbr) {
+            const Box cb = rboxes[c];
+            if (!(box_box_bound(own, cb) > wg_best)) keep = c, s_cbox[t] = cb;
+        }
+        s_cand[t] = keep;
+        const unsigned long long kept = __ballot(keep >= 0);
+        if ((t & 63) == 0) s_kept[t >> 5] = (uint32_t)kept, s_kept[(t >> 5) + 1] = (uint32_t)(kept >> 32);
+        __syncthreads();
+        // As in knn_search_kernel: a survivor of the coarse filter is staged only if some query needs it NOW.  The masks are the same
+        // in every thread (made scalar: the loops and their barriers are uniform).
+        for (int w = 0; w < NT / 32; ++w)
+            for (uint32_t m = (uint32_t)__builtin_amdgcn_readfirstlane((int)s_kept[w]); m; m &= m - 1) {   // nearest place first
+                const int i = w * 32 + (__ffs(m) - 1);
+                // skip only on a bound STRICTLY above the best: a reference at that very distance may still win on its index
+                const bool need = active && !(point_box_bound(q, s_cbox[i]) > bd);
+                if (!__syncthreads_or(need)) continue;         // (the barrier: the last staged block has been read)
+                const int64_t first = (int64_t)s_cand[i] * NT;
+                if (first + t < N) s_pts[t] = rsorted[first + t];
+                __syncthreads();
+                if (need) scan_staged_nearest(bd, bi, q, s_pts, (int)min((int64_t)NT, N - first));
+            }
+        wg_best = block_max(active ? bd : -1.0f);
+    }
+    if (!active) return;
+    int64_t id = (int64_t)__float_as_int(me.w);
+    id = id >= 0 && id < M ? id : 0;                           // (a guard: the ids are a permutation of 0 .. M-1)
+    dist2_out[id] = bi == INT_MAX ? INFINITY : bd;
+    if (index_out) index_out[id] = bi == INT_MAX ? -1 : bi;
+}
+
+struct SetWs {
+    uint64_t *item[2];        // [X] each
+    float4 *sorted;           // [X]
+    Box *boxes;               // [ceil(X / 256)]
+};
+struct NearestWs {
+    Box *box_part, *box;      // [2 * BOX_BLOCKS], [1]
+    SetWs q, r;
+    int32_t *hist, *start;    // [256 * chunks(max(M, N))] each
+    int32_t *scan_tmp;
+    size_t bytes;
+};
+NearestWs carve_nearest(void *base, int64_t M, int64_t N)
+{
+    char *p = static_cast<char *>(base);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { char *q = p + off; off += gsr_align(bytes); return q; };
+    auto set = [&](int64_t X) {
+        SetWs w;
+        w.item[0] = reinterpret_cast<uint64_t *>(take(8 * (size_t)X));
+        w.item[1] = reinterpret_cast<uint64_t *>(take(8 * (size_t)X));
+        w.sorted = reinterpret_cast<float4 *>(take(16 * (size_t)X));
+        w.boxes = reinterpret_cast<Box *>(take(sizeof(Box) * (size_t)gsr_div_up(X, NT)));
+        return w;
+    };
+    NearestWs w;
+    w.box_part = reinterpret_cast<Box *>(take(sizeof(Box) * (2 * BOX_BLOCKS + 1)));
+    w.box = w.box_part + 2 * BOX_BLOCKS;
+    w.q = set(M);
+    w.r = set(N);
+    const size_t h = 256 * (size_t)gsr_div_up(M > N ? M : N, SORT_CHUNK);
+    w.hist = reinterpret_cast<int32_t *>(take(4 * h));
+    w.start = reinterpret_cast<int32_t *>(take(4 * h));
+    w.scan_tmp = reinterpret_cast<int32_t *>(take(4 * ((size_t)gsr_div_up((int64_t)h, GSR_SCAN_WAVE_ITEMS) + 4)));
+    w.bytes = off;
+    return w;
+}
+
 } // namespace
 
 extern "C" {
@@ -382,18 +537,39 @@ int gsr_knn(int64_t N, const float *points, float *mean_dist2, int32_t *nn_index
     if (ws_bytes < gsr_knn_workspace_bytes(N)) return GSR_E_WORKSPACE;
     const KnnWs w = carve(ws, N);
     hipStream_t s = (hipStream_t)stream;
-    const int blocks = (int)gsr_div_up(N, NT), chunks = (int)gsr_div_up(N, SORT_CHUNK), box_blocks = blocks < BOX_BLOCKS ? blocks : BOX_BLOCKS;
+    const int blocks = (int)gsr_div_up(N, NT), box_blocks = blocks < BOX_BLOCKS ? blocks : BOX_BLOCKS;
     hipLaunchKernelGGL(knn_box_kernel, dim3(box_blocks), dim3(NT), 0, s, N, points, w.box_part);
     hipLaunchKernelGGL(knn_box_finish_kernel, dim3(1), dim3(NT), 0, s, (const Box *)w.box_part, box_blocks, w.box);
-    hipLaunchKernelGGL(knn_morton_kernel, dim3(blocks), dim3(NT), 0, s, N, points, (const Box *)w.box, w.item[0]);
-    for (int pass = 0; pass < 4; ++pass) {                     // 30 bits of code: four 8-bit digits; an even count ends in item[0]
-        const uint64_t *src = w.item[pass & 1];
-        hipLaunchKernelGGL(knn_hist_kernel, dim3(chunks), dim3(NT), 0, s, N, src, 8 * pass, w.hist);
-        if (gsr_launch_exclusive_scan(w.hist, w.start, w.scan_tmp, (int64_t)256 * chunks, s) != hipSuccess) return GSR_E_HIP;
-        hipLaunchKernelGGL(knn_scatter_kernel, dim3(chunks), dim3(NT), 0, s, N, src, w.item[(pass & 1) ^ 1], 8 * pass, (const int32_t *)w.start);
-    }
+    if (!sort_by_morton(N, points, w.box, w.item, w.hist, w.start, w.scan_tmp, s)) return GSR_E_HIP;
     hipLaunchKernelGGL(knn_gather_kernel, dim3(blocks), dim3(NT), 0, s, N, points, (const uint64_t *)w.item[0], w.sorted, w.boxes);
     hipLaunchKernelGGL(knn_search_kernel, dim3(blocks), dim3(NT), 0, s, N, blocks, (const float4 *)w.sorted, (const Box *)w.boxes, mean_dist2, nn_index);
+    return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP;
+}
+
+size_t gsr_nearest_workspace_bytes(int64_t M, int64_t N) { return count_ok(M) && count_ok(N) ? carve_nearest(nullptr, M, N).bytes : 0; }
+
+int gsr_nearest(int64_t M, const float *queries, int64_t N, const float *refs, float max_dist2, float *dist2, int32_t *index, void *ws, size_t ws_bytes,
+                void *stream)
+{
+    if (!queries || !refs || !dist2 || !ws) return GSR_E_NULL;
+    if (!count_ok(M) || !count_ok(N) || !(max_dist2 >= 0.0f)) return GSR_E_DIMS;          // (a NaN fails the comparison)
+    if (!gsr_aligned16(queries) || !gsr_aligned16(refs) || !gsr_aligned16(dist2) || !gsr_aligned16(index) || !gsr_aligned16(ws)) return GSR_E_ALIGN;
+    if (ws_bytes < gsr_nearest_workspace_bytes(M, N)) return GSR_E_WORKSPACE;
+    const NearestWs w = carve_nearest(ws, M, N);
+    hipStream_t s = (hipStream_t)stream;
+    const int qblocks = (int)gsr_div_up(M, NT), rblocks = (int)gsr_div_up(N, NT);
+    const int qbox = qblocks < BOX_BLOCKS ? qblocks : BOX_BLOCKS, rbox = rblocks < BOX_BLOCKS ? rblocks : BOX_BLOCKS;
+    // one box over both sets: the references' partial records lie behind the queries', and one finish takes them all
+    hipLaunchKernelGGL(knn_box_kernel, dim3(qbox), dim3(NT), 0, s, M, queries, w.box_part);
+    hipLaunchKernelGGL(knn_box_kernel, dim3(rbox), dim3(NT), 0, s, N, refs, w.box_part + qbox);
+    hipLaunchKernelGGL(knn_box_finish_kernel, dim3(1), dim3(NT), 0, s, (const Box *)w.box_part, qbox + rbox, w.box);
+    if (!sort_by_morton(M, queries, w.box, w.q.item, w.hist, w.start, w.scan_tmp, s)) return GSR_E_HIP;
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(qblocks), dim3(NT), 0, s, M, queries, (const uint64_t *)w.q.item[0], w.q.sorted, w.q.boxes);
+    if (!sort_by_morton(N, refs, w.box, w.r.item, w.hist, w.start, w.scan_tmp, s)) return GSR_E_HIP;
+    hipLaunchKernelGGL(knn_gather_kernel, dim3(rblocks), dim3(NT), 0, s, N, refs, (const uint64_t *)w.r.item[0], w.r.sorted, w.r.boxes);
+    hipLaunchKernelGGL(nearest_search_kernel, dim3(qblocks), dim3(NT), 0, s, M, N, rblocks, (const float4 *)w.q.sorted, (const Box *)w.q.boxes,
+                       (const uint64_t *)w.q.item[0], (const float4 *)w.r.sorted, (const Box *)w.r.boxes, (const uint64_t *)w.r.item[0], max_dist2, dist2,
+                       index);
     return hipGetLastError() == hipSuccess ? GSR_OK : GSR_E_HIP;
 }
 

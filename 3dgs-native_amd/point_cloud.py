@@ -248,3 +248,61 @@ def save_mesh_ply(path, verts, faces, colors=None):
         out.write(("\n".join(lines) + "\n").encode("ascii"))
         vr.tofile(out)
         fr.tofile(out)
+
+
+def load_mesh_ply(filepath):
+    """The inverse of save_mesh_ply for binary little-endian files: (verts float32 (V, 3), faces int32 (T, 3), colors float32 (V, 3) in
+    [0, 1] or None).  The vertex element comes first and is read as load_points reads it; the face element follows it directly with
+    one property, `list uchar int` (or uint8 / int32), and every face a triangle.  Anything else -- ASCII, another element between the
+    two, another list type, a polygon, an index outside the vertices, a truncated file -- is refused with ValueError."""
+    with open(filepath, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("not a PLY file")
+        fmt, elements = None, []                               # (name, count, [property tokens])
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("PLY header not terminated")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                if not elements:
+                    raise ValueError("a property in front of the first element")
+                elements[-1][2].append(tok[1:])
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian":
+            raise ValueError(f"expected a binary_little_endian PLY (got {fmt!r}): convert ASCII or big-endian files first")
+        if len(elements) < 2 or elements[0][0] != "vertex" or elements[1][0] != "face":
+            raise ValueError("expected a vertex element followed by a face element")
+        fields = []
+        for p in elements[0][2]:
+            if p[0] == "list" or p[0] not in _PLY_SCALARS:
+                raise ValueError(f"vertex property {p[-1]!r}: only scalar properties are supported (got {p[0]!r})")
+            fields.append((p[1], _PLY_SCALARS[p[0]]))
+        names = [k for k, _ in fields]
+        if len(set(names)) != len(names) or not all(k in names for k in "xyz"):
+            raise ValueError("expected a vertex element with properties x, y, z")
+        props = elements[1][2]
+        if len(props) != 1 or len(props[0]) != 4 or props[0][0] != "list" or props[0][1] not in ("uchar", "uint8") or props[0][2] not in ("int", "int32"):
+            raise ValueError("the face element must have one property, `list uchar int`")
+        n, t = elements[0][1], elements[1][1]
+        v = np.fromfile(f, dtype=np.dtype(fields), count=n)
+        fr = np.fromfile(f, dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]), count=t)
+    if len(v) != n or len(fr) != t:
+        raise ValueError("PLY file is truncated")
+    if t and (fr["n"] != 3).any():
+        raise ValueError("every face must be a triangle")
+    faces = np.ascontiguousarray(fr["i"]).astype(np.int32).reshape(-1, 3)
+    if t and (faces.min() < 0 or faces.max() >= n):
+        raise ValueError("a face index lies outside the vertices")
+    verts = np.stack([v["x"], v["y"], v["z"]], axis=1).astype(np.float32).reshape(-1, 3)
+    colors = None
+    if all(k in names and v.dtype[k] == np.uint8 for k in ("red", "green", "blue")):
+        colors = np.stack([v["red"], v["green"], v["blue"]], axis=1).astype(np.float32) / np.float32(255)
+    return verts, faces, colors

@@ -9,6 +9,7 @@ The cube is centred on the cameras' common look-at point with half of their exte
 --center / --half-side name it.  --voxel-size S or --resolution R (voxels per side; default 256) set the grid, --trunc the
 truncation distance (default 4 voxels), --depth-max drops far depths, --min-weight K keeps only cells all of whose corners were
 observed with weight K.  Extraction is offline: it reads the triangle count back once, and welds on the host.
+--gt G.ply evaluates the mesh right away against a ground truth in the same frame (accuracy, completeness, F-score: eval_mesh.py).
 """
 import argparse
 import importlib
@@ -66,6 +67,11 @@ def main():
     ap.add_argument("--half-side", type=float, default=None, metavar="E")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--record", default=None, metavar="FILE", help="write the run's figures (resolution, triangles, seconds) as one JSON line")
+    ap.add_argument("--gt", default=None, metavar="G.ply", help="evaluate the mesh against this ground truth in the same frame (examples/eval_mesh.py)")
+    ap.add_argument("--gt-points", action="store_true", help="--gt holds points, not a surface to sample")
+    ap.add_argument("--eval-samples", type=int, default=1_000_000, metavar="S", help="--gt: about S samples per mesh")
+    ap.add_argument("--thresholds", type=float, nargs="+", default=[0.01, 0.02, 0.05], metavar="TAU", help="--gt: F-score thresholds")
+    ap.add_argument("--max-dist", type=float, default=None, metavar="X", help="--gt: points without a neighbour within X are outliers")
     args = ap.parse_args()
     if args.voxel_size is not None and not args.voxel_size > 0.0:
         raise SystemExit("--voxel-size must be positive")
@@ -81,6 +87,16 @@ def main():
     cams = load_cameras(gsr, args.dataset, args.views)
     info = mesh_from_model(gsr, P, cams, args.out, voxel_size=args.voxel_size, resolution=args.resolution or 256, centre=args.center,
                            half_side=args.half_side, trunc=args.trunc, depth_max=args.depth_max, min_weight=args.min_weight)
+    if args.gt:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from eval_mesh import evaluate_mesh
+        verts, faces, _ = gsr.point_cloud.load_mesh_ply(args.out)
+        if args.gt_points:
+            gt_verts, gt_faces = gsr.point_cloud.load_points(args.gt)[0], None
+        else:
+            gt_verts, gt_faces, _ = gsr.point_cloud.load_mesh_ply(args.gt)
+        info["eval"] = evaluate_mesh(gsr, verts, faces, gt_verts, gt_faces, samples=args.eval_samples, thresholds=args.thresholds, max_dist=args.max_dist)
+        info["eval"]["gt"] = args.gt
     if args.record:
         with open(args.record, "w") as f:
             f.write(json.dumps(info) + "\n")
