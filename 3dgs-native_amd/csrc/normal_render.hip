@@ -4,15 +4,13 @@
 // gaussian_normals_kernel<BWD>: one thread per Gaussian, the header's steps (a) and (b) word for word; the view matrix travels as a
 // kernel argument.  consistency_kernel: one thread per pixel of a grid-stride walk, elementwise, plus fixed_sum.h's tree for the two sums.
 //
-// normal_render_kernel<BWD> replays the forward blend's weights the way distortion.hip does: one 256-thread workgroup per 16x16
-// tile, each of its four waves owning one 8x8 pixel block (lane = pixel), the tile's list staged through LDS in batches of 256
-// entries (48 bytes each: position, pre-scaled conic, opacity, id, the Gaussian's normal), each wave compacting a batch to the
-// entries its block may see and walking them with blend_forward_kernel's weight expression.
+// normal_render_kernel<BWD> replays the forward blend's weights with frame_walk.h's FrameWalk: the tile's list staged in 48-byte
+// records (position, pre-scaled conic, opacity, id, and the Gaussian's normal in the third word).
 //   - forward: three running registers per lane, one fmaf per channel and applied entry in list order: what features.hip's exact
 //     float32 MFMA computes at C = 3, without filing 32-column weight tiles for a product that uses 3 of its 32 channels.
-//   - backward: distortion.hip's walk with u = G . n, and nine per-(pixel, entry) values instead of seven.  The flush there sums each
-//     row of the value tile with two lanes (32 pixels each, in order, then the two halves), which needs 2 * ROWS <= 64 lanes.  Nine
-//     values at four slots are 36 rows, 72 lanes: over.  The choices were (1) four slots and a second flush round for rows 32-35 --
+//   - backward: distortion.hip's walk with u = G . n, and nine per-(pixel, entry) values instead of seven.  The flush (frame_walk.h,
+//     ValueTile) sums each row of the value tile with two lanes (32 pixels each, in order, then the two halves): 2 * ROWS <= 64
+//     lanes.  Nine values at four slots are 36 rows, 72 lanes: over.  The choices were (1) four slots and a second flush round for rows 32-35 --
 //     two rounds of 32 dependent LDS adds for 8 more rows, and 36 x 65 x 4 B x 4 waves = 37 KB of LDS on top of the 12 KB of staging;
 //     (2) one lane per row, 7 slots = 63 rows -- every lane busy, but 64 dependent adds per flush and 66 KB of LDS, two workgroups
 //     per CU; (3) THREE slots: 27 rows, 54 of 64 lanes busy in the same two-lanes-per-row, 32-add flush, the header's summation
@@ -25,51 +23,21 @@
 //     row-parallel reads over the 64 banks; the walk's column stores (lane = consecutive floats) are conflict-free by construction.
 //     Float atomics: one per (block, applied entry, value), 36 bytes per entry over two cache lines (the record's columns 3-10
 //     and the Gaussian's row of dL_dnormals); -munsafe-fp-atomics makes them the hardware's global_atomic_add_f32, no CAS loop.
-#include <algorithm>
 #include <math.h>
 
-#include "gsr_internal.h"
+#include "frame_walk.h"
 #include "gsr_normal_render.h"
 #include "fixed_sum.h"
 
 namespace {
 
-constexpr int BATCH = 256;   // list entries staged per round
 constexpr int SLOTS = 3;     // entries per flush of the backward (see above)
-constexpr int VALS = 9;      // S1, S2, Sxx, Sxy, Syy, Sop, Snx, Sny, Snz
-constexpr int ROWS = SLOTS * VALS;
-constexpr int PITCH = 65;    // floats per row of the value tile: odd, so the row-parallel reads of the flush spread over the 64 banks
-static_assert(2 * ROWS <= 64, "the flush sums a row with two lanes");
-
-struct FrameK {
-    int W, H, grid_x;
-    long long N, D;
-    const float *xy;
-    long long xy_stride;
-    const float *co;
-    long long co_stride;
-    const int32_t *point_list;
-    const int32_t *ranges;
-    const int32_t *n_contrib;
-    const uint8_t *masks;
-};
+constexpr int VALS = 9;      // S1, S2, Sxx, Sxy, Syy, Sop, Snx, Sny, Snz: the last three are the Gaussian's row of dL_dnormals
+typedef ValueTile<VALS, SLOTS> Tile;
 
 struct ViewK {
     float v[16];
 };
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); } // blend_fwd.hip's
-
-// lanes of one wave exchange data through LDS: in order in hardware, but the compiler must not move the accesses across
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// accumulator column of the k-th value the flush adds (k < 6): dmean2D x y | dconic a b c | dopacity
-__device__ __forceinline__ int acc_column(int k) { return k < 2 ? 3 + k : k < 4 ? 4 + k : k == 4 ? 9 : 10; }
 
 // ---- (a), (b): one thread per Gaussian ----
 // BWD: `g_in` is dL_dnormals [N][3] and `out` dL_drot [N][4] (added to); else `out` is normals [N][3].
@@ -143,128 +111,32 @@ template <bool BWD>
 __global__ __launch_bounds__(256) void normal_render_kernel(FrameK f, const float *__restrict__ normals, const float *__restrict__ g_in, float *img,
                                                             float *__restrict__ acc, float *__restrict__ dnorm)
 {
-    __shared__ float4 s_rec[BATCH][3];    // {x, y, a', b'} {c', opacity, id, -} {n.x, n.y, n.z, -}
-    __shared__ uint8_t s_mask[BATCH];
-    __shared__ uint16_t s_list[4][BATCH + 2]; // per wave: the batch entries its block may see, in list order (+ two the walk reads ahead)
-    __shared__ float s_v[BWD ? 4 : 1][BWD ? ROWS * PITCH : 1]; // per wave: [entry slot][value][pixel]
-    __shared__ float s_red[4][ROWS];      // per wave: the rows' sums
-    __shared__ float4 s_con[4][SLOTS];    // per wave: {a', b', c', id} of each slot
-    __shared__ int s_max;
-
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int tile = blockIdx.x;
-    const int tile_x = tile % f.grid_x, tile_y = tile / f.grid_x;
-    const int bx0 = tile_x * 16 + (wv & 1) * 8, by0 = tile_y * 16 + (wv >> 1) * 8; // this wave's 8x8 block; pixel q of it = (q & 7, q >> 3)
-    const int pix_x = bx0 + (lane & 7), pix_y = by0 + (lane >> 3);
-    const bool inside = pix_x < f.W && pix_y < f.H;
-    const size_t pix = inside ? (size_t)pix_y * f.W + pix_x : 0;
-    const float pixf_x = (float)pix_x, pixf_y = (float)pix_y;
-    const unsigned long long lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    const int my_bits = 5 << ((wv >> 1) * 4 + (wv & 1)); // this wave's 8x8 block = the 8x4 blocks k0 and k0 + 2 (blend_fwd.hip)
-
-    // the walk's bounds: the range clipped to [0, D], n_contrib to the range
-    long long start = f.ranges[2 * tile], end = f.ranges[2 * tile + 1];
-    start = std::min(std::max(start, 0ll), f.D);
-    end = std::min(std::max(end, start), f.D);
-    const int len = (int)(end - start);
-    int nc = 0;
-    if (inside) nc = std::min(std::max(f.n_contrib[pix], 0), len);
-    int wmax = nc;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) wmax = max(wmax, __shfl_xor(wmax, d, 64));
-    wmax = __builtin_amdgcn_readfirstlane(wmax);
-    if (tid == 0) s_max = 0;
-    __syncthreads();
-    if (lane == 0) atomicMax(&s_max, wmax);
-    __syncthreads();
-    const int tmax = s_max;
+    __shared__ Tile::V<BWD> s_v; // the value tile: the backward's alone
+    __shared__ Tile::Red s_red;
+    __shared__ Tile::Con s_con;
+    const FrameWalk walk(f);
+    const bool inside = walk.inside;
+    const size_t pix = walk.pix;
 
     float ox = 0.0f, oy = 0.0f, oz = 0.0f;       // forward: the running image
     float gx = 0.0f, gy = 0.0f, gz = 0.0f, total = 0.0f, P = 0.0f;
-    if (BWD && inside && nc > 0) {
+    if (BWD && inside && walk.nc > 0) {
         gx = g_in[3 * pix]; gy = g_in[3 * pix + 1]; gz = g_in[3 * pix + 2];
         total = (gx * img[3 * pix] + gy * img[3 * pix + 1]) + gz * img[3 * pix + 2];
     }
-    const float half_w = 0.5f * (float)f.W, half_h = 0.5f * (float)f.H;
-
-    // backward: the sums of the wave's value tile, entry slots [0, ns), added to the accumulator records and the normals' rows
-    auto flush = [&](int ns) {
-        wave_lds_sync();
-        float v = 0.0f;
-        if (lane < 2 * ROWS) {
-            const float *row = &s_v[BWD ? wv : 0][(lane % ROWS) * PITCH + (lane / ROWS) * 32];
-#pragma unroll
-            for (int j = 0; j < 32; ++j) v += row[j]; // rows of slots from ns on hold stale values: never added
-        }
-        v += __shfl_down(v, ROWS, 64); // pixels 0-31 + pixels 32-63
-        if (lane < ROWS) s_red[wv][lane] = v;
-        wave_lds_sync();
-        if (lane < ROWS) {
-            const int slot = lane / VALS, k = lane % VALS;
-            if (slot < ns) {
-                const float4 c = s_con[wv][slot];
-                const float *r = &s_red[wv][slot * VALS];
-                const size_t id = (size_t)__float_as_int(c.w); // in [0, N): only a staged, applied entry is filed
-                float out;
-                if (k == 0) out = (2.0f * c.x * r[0] + c.y * r[1]) * half_w;
-                else if (k == 1) out = (2.0f * c.z * r[1] + c.y * r[0]) * half_h;
-                else if (k < 5) out = -0.5f * r[k];
-                else out = r[k];
-                // ONE atomic instruction for the wave's 27 lanes, whichever array a lane's value goes to: an atomic wave-instruction has a
-                // fixed issue price, and one per destination array and column group was five of them per flush
-                float *dst = k < 6 ? &acc[id * 16 + acc_column(k)] : &dnorm[id * 3 + (k - 6)];
-                atomicAdd(dst, out);
-            }
-        }
-        wave_lds_sync();
-    };
+    Tile tile(s_v[BWD ? walk.wv : 0], s_red[walk.wv], s_con[walk.wv], walk, f, acc, dnorm, 3, 0);
 
     float T = 1.0f;
-    int ns = 0;
-    for (int base = 0; base < tmax; base += BATCH) {
-        __syncthreads(); // every wave has walked the last batch
-        const int cnt = min(BATCH, tmax - base);
-        if (tid < cnt) {
-            const long long at = start + base + tid; // < start + tmax <= end <= D
-            const int id = f.point_list[at];
-            float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra, rc = ra; // an id outside [0, N): opacity 0, never applied
-            if (id >= 0 && (long long)id < f.N) {
-                const float *pxy = f.xy + (size_t)id * f.xy_stride, *pco = f.co + (size_t)id * f.co_stride, *pn = normals + (size_t)id * 3;
-                ra = make_float4(pxy[0], pxy[1], -0.5f * pco[0], -pco[1]);
-                rb = make_float4(-0.5f * pco[2], pco[3], __int_as_float(id), 0.f);
-                rc = make_float4(pn[0], pn[1], pn[2], 0.f);
-            }
-            s_rec[tid][0] = ra;
-            s_rec[tid][1] = rb;
-            s_rec[tid][2] = rc;
-            s_mask[tid] = f.masks ? f.masks[at] : (uint8_t)0xFF;
-        }
-        __syncthreads();
-        int n = 0;
-        for (int gb = 0; gb < cnt; gb += 64) {
-            const int e = gb + lane;
-            const bool hit = e < cnt && base + e < wmax && (s_mask[e] & my_bits) != 0;
-            const unsigned long long bits = __ballot(hit);
-            if (hit) s_list[wv][n + __popcll(bits & lt_mask)] = (uint16_t)e;
-            n += __popcll(bits);
-        }
-        if (lane < 2) s_list[wv][n + lane] = 0; // the walk reads two list entries ahead; entry 0 of a batch always exists
-        wave_lds_sync();
-        // one-deep software pipeline: the record of entry k + 1 and the list slot of entry k + 2 are in flight while entry k is weighed
-        int e = s_list[wv][0], e1 = s_list[wv][1];
-        float4 ra = s_rec[e][0], rb = s_rec[e][1], rc = s_rec[e][2];
-        for (int k = 0; k < n; ++k) {
-            const int e2 = s_list[wv][k + 2];
-            const float4 na = s_rec[e1][0], nb = s_rec[e1][1], nn = s_rec[e1][2];
-            const float dx = ra.x - pixf_x, dy = ra.y - pixf_y;
-            const float power = (ra.z * dx * dx + rb.x * dy * dy) + ra.w * dx * dy;
-            const float G = fast_exp(power);
-            const float alpha = fminf(0.99f, rb.y * G);
-            const float t = power > 0.0f ? 0.0f : alpha;
-            const bool applied = base + e < nc && !(t < (1.0f / 255.0f));
+    walk.run<3>(
+        f,
+        [&](int id, float4 &rb, float4 &rc) {
+            const float *pn = normals + (size_t)id * 3;
+            rc = make_float4(pn[0], pn[1], pn[2], 0.f);
+        },
+        [&](const float4 &ra, const float4 &rb, const float4 &rc, float dx, float dy, float G, float t, bool applied) {
             if (BWD) {
                 if (__builtin_amdgcn_ballot_w64(applied) != 0ull) {
-                    float v0 = 0.f, v1 = 0.f, v2 = 0.f, v3 = 0.f, v4 = 0.f, v5 = 0.f, v6 = 0.f, v7 = 0.f, v8 = 0.f;
+                    float v[VALS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
                     if (applied) {
                         const float u = (gx * rc.x + gy * rc.y) + gz * rc.z;
                         const float w = t * T;
@@ -275,18 +147,11 @@ __global__ __launch_bounds__(256) void normal_render_kernel(FrameK f, const floa
                         const float gd = G * q;
                         const float h = rb.y * gd;
                         const float hx = h * dx, hy = h * dy;
-                        v0 = hx; v1 = hy; v2 = hx * dx; v3 = hx * dy; v4 = hy * dy; v5 = gd;
-                        v6 = w * gx; v7 = w * gy; v8 = w * gz;
+                        v[0] = hx; v[1] = hy; v[2] = hx * dx; v[3] = hx * dy; v[4] = hy * dy; v[5] = gd;
+                        v[6] = w * gx; v[7] = w * gy; v[8] = w * gz;
                         T = T * om;
                     }
-                    float *col = &s_v[BWD ? wv : 0][ns * VALS * PITCH + lane];
-                    col[0 * PITCH] = v0; col[1 * PITCH] = v1; col[2 * PITCH] = v2; col[3 * PITCH] = v3; col[4 * PITCH] = v4;
-                    col[5 * PITCH] = v5; col[6 * PITCH] = v6; col[7 * PITCH] = v7; col[8 * PITCH] = v8;
-                    if (lane == 0) s_con[wv][ns] = make_float4(ra.z, ra.w, rb.x, rb.z);
-                    if (++ns == SLOTS) {
-                        flush(SLOTS);
-                        ns = 0;
-                    }
+                    tile.file(v, ra, rb);
                 }
             } else if (applied) {
                 const float w = t * T;
@@ -295,12 +160,9 @@ __global__ __launch_bounds__(256) void normal_render_kernel(FrameK f, const floa
                 oy = __builtin_fmaf(w, rc.y, oy);
                 oz = __builtin_fmaf(w, rc.z, oz);
             }
-            e = e1; e1 = e2;
-            ra = na; rb = nb; rc = nn;
-        }
-    }
+        });
     if (BWD) {
-        if (ns > 0) flush(ns);
+        tile.finish();
     } else if (inside) {
         img[3 * pix] = ox; img[3 * pix + 1] = oy; img[3 * pix + 2] = oz;
     }
@@ -357,14 +219,9 @@ __global__ __launch_bounds__(GSR_SUM_THREADS) void consistency_finish_kernel(con
 // NULL, DIMS, ALIGN, in the header's order; GSR_OK when the call may be enqueued
 int check_frame(const GsrFeaturesFrame *fr, const void *a, const void *b, const void *c, const void *d, const void *e)
 {
-    if (!fr || !fr->xy || !fr->conic_opacity || !fr->ranges || !fr->n_contrib || !a || !b || !c || !d || !e) return GSR_E_NULL;
-    if (!fr->point_list && fr->D > 0) return GSR_E_NULL;
-    if (fr->W < 1 || fr->H < 1 || fr->W > GSR_FEATURES_MAX_SIDE || fr->H > GSR_FEATURES_MAX_SIDE || fr->N < 1 || fr->N > 0x7FFFFFFFll || fr->D < 0 ||
-        fr->D > GSR_MAX_RENDERED || fr->xy_stride < 2 || fr->conic_opacity_stride < 4)
-        return GSR_E_DIMS;
-    if (!gsr_aligned4(fr->xy) || !gsr_aligned4(fr->conic_opacity) || !gsr_aligned4(fr->point_list) || !gsr_aligned4(fr->ranges) ||
-        !gsr_aligned4(fr->n_contrib) || !gsr_aligned16(a) || !gsr_aligned16(b) || !gsr_aligned16(c) || !gsr_aligned16(d) || !gsr_aligned16(e))
-        return GSR_E_ALIGN;
+    if (frame_has_null(fr) || !a || !b || !c || !d || !e) return GSR_E_NULL;
+    if (!frame_dims_ok(fr)) return GSR_E_DIMS;
+    if (!frame_aligned(fr) || !all_aligned16(a, b, c, d, e)) return GSR_E_ALIGN;
     return GSR_OK;
 }
 
@@ -376,17 +233,6 @@ int check_gaussians(int64_t N, const float *scales, const float *rots, const flo
         if (!isfinite(view[k])) return GSR_E_DIMS;
     if (!gsr_aligned16(scales) || !gsr_aligned16(rots) || !gsr_aligned16(means) || !gsr_aligned16(a) || !gsr_aligned16(b)) return GSR_E_ALIGN;
     return GSR_OK;
-}
-
-FrameK frame_k(const GsrFeaturesFrame *fr)
-{
-    FrameK k;
-    k.W = fr->W; k.H = fr->H; k.grid_x = (fr->W + 15) / 16;
-    k.N = fr->N; k.D = fr->point_list ? fr->D : 0;
-    k.xy = fr->xy; k.xy_stride = fr->xy_stride;
-    k.co = fr->conic_opacity; k.co_stride = fr->conic_opacity_stride;
-    k.point_list = fr->point_list; k.ranges = fr->ranges; k.n_contrib = fr->n_contrib; k.masks = fr->block_masks;
-    return k;
 }
 
 ViewK view_k(const float *view)
@@ -423,9 +269,8 @@ extern "C" int gsr_normal_render_forward(const GsrFeaturesFrame *frame, const fl
     const int rc = check_frame(frame, normals, out, out, out, out);
     if (rc != GSR_OK) return rc;
     const FrameK k = frame_k(frame);
-    const int tiles = k.grid_x * ((k.H + 15) / 16);
     // a frame with D = 0 walks nothing: every pixel is written as 0
-    hipLaunchKernelGGL((normal_render_kernel<false>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, k, normals, nullptr, out, nullptr, nullptr);
+    hipLaunchKernelGGL((normal_render_kernel<false>), dim3(frame_tiles(k)), dim3(256), 0, (hipStream_t)stream, k, normals, nullptr, out, nullptr, nullptr);
     return gsr_done();
 }
 
@@ -437,8 +282,7 @@ extern "C" int gsr_normal_render_backward(const GsrFeaturesFrame *frame, const f
     const FrameK k = frame_k(frame);
     if (hipMemsetAsync(dL_dnormals, 0, sizeof(float) * 3 * (size_t)k.N, (hipStream_t)stream) != hipSuccess) return GSR_E_HIP;
     if (k.D == 0) return gsr_done(); // nothing was blended: nothing to add
-    const int tiles = k.grid_x * ((k.H + 15) / 16);
-    hipLaunchKernelGGL((normal_render_kernel<true>), dim3(tiles), dim3(256), 0, (hipStream_t)stream, k, normals, dL_dout, const_cast<float *>(out),
+    hipLaunchKernelGGL((normal_render_kernel<true>), dim3(frame_tiles(k)), dim3(256), 0, (hipStream_t)stream, k, normals, dL_dout, const_cast<float *>(out),
                        accumulators, dL_dnormals);
     return gsr_done();
 }
