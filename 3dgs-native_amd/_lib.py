@@ -256,6 +256,13 @@ DISTORTION_EXPORTS = {
     "gsr_distortion_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp]),
 }
 
+# include/gsr_median_depth.h: the median inverse depth over a frame's lists (the frame struct is gsr_distortion.h's), and its gradient
+# into column 11 of the backward's accumulator records (its own header, so its own table)
+MEDIAN_DEPTH_EXPORTS = {
+    "gsr_median_depth_forward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp]),
+    "gsr_median_depth_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp]),
+}
+
 # include/gsr_normal_render.h: the Gaussians' own normals, their image over a frame's lists with its gradient into the backward's
 # accumulator records, and the depth-normal consistency term (its own header, so its own table)
 NORMAL_RENDER_EXPORTS = {
@@ -365,7 +372,8 @@ def lib():
                                   + list(DEPTH_CORR_EXPORTS.items()) + list(KNN_EXPORTS.items())
                                   + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
                                   + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())
-                                  + list(NORMAL_RENDER_EXPORTS.items()) + list(MESH_EVAL_EXPORTS.items())):
+                                  + list(NORMAL_RENDER_EXPORTS.items()) + list(MESH_EVAL_EXPORTS.items())
+                                  + list(MEDIAN_DEPTH_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -68,6 +68,15 @@ camera_grad (the screen-space columns only: the normals' direct dependence on vi
 antialiased mode, filter_3d, capacity frames and sh_gradient="factored".  `dL_dmean2D_abs` stays the colour, depth and alpha terms'
 alone.  Without the three keywords the call is exactly the one above.  (These four names are accepted by name through the
 signature's catch-all `**rendered_stage`, checked against normal_render.STAGE_KEYWORDS; any other name is a TypeError.)
+
+`dL_dmedian_depth=g, median_contributor=contrib` (include/gsr_median_depth.h; both or neither) add the gradient of
+sum_p g[p] med[p], med and contrib the two results of median_depth.render_median_depth().  The median is piecewise constant in
+everything but the chosen Gaussian's inverse depth, so the stage -- the last of the stages between the two halves, after the
+distortion and normal stages -- ADDS g[p] into column 11 of the accumulator record of the Gaussian pixel p chose and touches nothing
+else; the AUX per-Gaussian half carries it on to the means, and the result carries `dL_dinv_depths`.  `dL_dmedian_depth` alone is
+legal (dL_dpixels=None).  A frame that does not carry the forward's records needs geom_buffer["depths"], as for the distortion term.
+It composes with camera_grad, the antialiased mode, filter_3d, capacity frames and sh_gradient="factored"; `dL_dmean2D_abs` stays
+the colour, depth and alpha terms' alone.  Without the two keywords the call is exactly the one above.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -80,6 +89,7 @@ from . import dist as _dist
 from . import distortion as _distortion
 from . import filter3d as _filter3d
 from . import forward as _forward
+from . import median_depth as _median_depth
 from . import normal_render as _normal_render
 
 _ZERO = {}
@@ -239,6 +249,17 @@ def _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, normal
                                             _host.ptr(dnormals), stream))
 
 
+def _median_stage(L, st, out, N, point_list, ranges, n_contrib, g_med, contrib, stream):
+    """The median inverse depth's gradient (include/gsr_median_depth.h): g[p] added into column 11 of the accumulator record of the
+    Gaussian each pixel chose.  The frame is the one _distortion_stage reads; the kernel reads its lists and ranges only."""
+    D = int(point_list.numel())
+    if D == 0 or N == 0:
+        return
+    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
+    frame = _distortion.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), rec[:, 9], st.masks)
+    _lib.check(L.gsr_median_depth_backward(C.byref(frame), _host.ptr(g_med), _host.ptr(contrib), out.acc.data_ptr(), stream))
+
+
 def _launch(L, scene, cam, geom, binning, img, pg, out, flags, aa_scale, aux, on_payload, camera_grad, stream, distortion=None):
     """One request, whatever the options (gsr_densify_stats.h): with no auxiliary gradient and no flag it runs gsr_backward's
     kernels.  One entry point per stage: `aa` is NULL in the classic mode, and the _aa exports are then the classic calls
@@ -303,7 +324,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
              dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic", filter_3d=None,
-             dL_ddistortion=None, distortion_moments=None, **rendered_stage):
+             dL_ddistortion=None, distortion_moments=None, dL_dmedian_depth=None, median_contributor=None, **rendered_stage):
     # The keywords of include/gsr_normal_render.h -- dL_dnormal_image, gaussian_normals, normal_image (None) and normal_param_grad (True)
     # -- are taken by name from `rendered_stage` (normal_render.stage_keywords), not listed above: tests/test_normals_abi.py holds that
     # the depth-normals stage of include/gsr_normals.h added no parameter whose name contains "normal" to this signature, by that
@@ -312,6 +333,7 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
     distortion = _distortion.check_gradient_pair(dL_ddistortion, distortion_moments)
     normal = _normal_render.check_gradient_triple(dL_dnormal_image, gaussian_normals, normal_image)
+    median = _median_depth.check_gradient_pair(dL_dmedian_depth, median_contributor)
     frame_co = conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity")
     # (before anything touches the GPU: a frame rendered without the filter or with another one, raw tensors written since the render)
     if filter_3d is not None:
@@ -326,10 +348,10 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     aa_tag = _aa_scale_of(frame_co, opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
-    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion or normal
+    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion or normal or median
     if dL_dpixels is None and not aux:
-        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments, or "
-                         "dL_dnormal_image with gaussian_normals and normal_image)")
+        raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments, "
+                         "dL_dnormal_image with gaussian_normals and normal_image, or dL_dmedian_depth with median_contributor)")
     view16 = _normal_render.view_floats(viewmatrix, "backward(dL_dnormal_image=...)") if normal else None
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
     L = _lib.lib()
@@ -342,7 +364,9 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     dpix, g_depth, g_alpha = opt(dL_dpixels, (H, W, 3)), opt(dL_ddepth_image, (H, W)), opt(dL_dalpha_image, (H, W))
     g_dist, moments = opt(dL_ddistortion, (H, W)), opt(distortion_moments, (H, W, 4))
     g_normal, gn, nimg = opt(dL_dnormal_image, (H, W, 3)), opt(gaussian_normals, (N, 3)), opt(normal_image, (H, W, 3))
-    if (distortion or normal) and dpix is None and g_depth is None and g_alpha is None:
+    g_med = opt(dL_dmedian_depth, (H, W))
+    med_contrib = _host.to_dev(median_contributor, torch.int32, dev, (H, W)) if median else None
+    if (distortion or normal or median) and dpix is None and g_depth is None and g_alpha is None:
         g_alpha = torch.zeros((H, W), dtype=f32, device=dev)   # the blend half wants one image gradient: a zero one clears and adds nothing
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
@@ -369,12 +393,15 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         m2d = _host.to_dev(means2D, f32, dev, (-1, 2))
         con = _host.to_dev(conic_opacity, f32, dev, (-1, 4))
         col = _host.to_dev(rgb, f32, dev, (-1, 3))
-        if (g_depth is not None or distortion) and geom_buffer is not None:
+        if (g_depth is not None or distortion or median) and geom_buffer is not None:
             # the re-packed records carry 1/depth only from the forward's depths (gsr_aux_grads.h: without them, GSR_E_NULL)
             depths = opt(geom_buffer.get("depths"), (-1,))
         if distortion and depths is None:
             raise ValueError("backward(dL_ddistortion=...) on a frame that does not carry the forward's records needs "
                              "geom_buffer['depths']: the distortion is a function of the Gaussians' inverse depths")
+        if median and depths is None:
+            raise ValueError("backward(dL_dmedian_depth=...) on a frame that does not carry the forward's records needs "
+                             "geom_buffer['depths']: the per-Gaussian half carries dL/d(1/depth) on through the re-packed records")
     cl = _host.to_dev(clamped, f32, dev, (-1, 3))
     c3 = None if st.recompute else _host.to_dev(cov3Ds, f32, dev, (-1, 6))
     ranges = _host.to_dev(given["ranges"], i32, dev, (-1, 2))
@@ -399,15 +426,16 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
                                   _host.ptr(out.ws) if cleared else None, 1 if cleared else 0)
         stream = _host.raw_stream(dev)
         stage = dnormals = None
-        if distortion and not normal:
-            stage = lambda: _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
-        elif normal:
+        if normal:
             dnormals = torch.empty((N, 3), dtype=f32, device=dev)
-
-            def stage():                    # the distortion stage first when both are present
+        if distortion or normal or median:
+            def stage():                    # in this order when several are present: distortion, normals, median depth
                 if distortion:
                     _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
-                _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, gn, nimg, dnormals, stream)
+                if normal:
+                    _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, gn, nimg, dnormals, stream)
+                if median:
+                    _median_stage(L, st, out, N, point_list, ranges, n_contrib, g_med, med_contrib, stream)
         dcam = _launch(L, scene, cam, geom, binning, img, pg, out, _lib.BWD_ABSGRAD if absgrad else 0, aa_scale, aux, on_payload,
                        camera_grad, stream, stage)
         if normal and normal_param_grad and N > 0:
@@ -430,9 +458,11 @@ def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
     of three dicts, nothing else; the tensors go through as they are.  **kw: sh_gradient, camera_grad, absgrad, dL_ddepth_image,
     dL_dalpha_image, geom_buffer, rasterize_mode, filter_3d, dL_ddistortion with distortion_moments (a frame whose records were
     written since the render is re-packed from buffers["depths"], handed on here as geom_buffer), dL_dnormal_image with
-    gaussian_normals and normal_image, normal_param_grad."""
+    gaussian_normals and normal_image, normal_param_grad, dL_dmedian_depth with median_contributor (re-packed like the distortion term)."""
     _normal_render.check_gradient_triple(kw.get("dL_dnormal_image"), kw.get("gaussian_normals"), kw.get("normal_image"))
-    if _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments")) and "geom_buffer" not in kw and "depths" in buffers:
+    needs_depths = _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments"))
+    needs_depths |= _median_depth.check_gradient_pair(kw.get("dL_dmedian_depth"), kw.get("median_contributor"))
+    if needs_depths and "geom_buffer" not in kw and "depths" in buffers:
         kw["geom_buffer"] = {"depths": buffers["depths"]}
     return backward(background=background, means3D=params["positions"], dL_dpixels=dL_dpixels, opacity=params["opacities"],
                     shs=params["shs"], scales=params["scales"], rotations=params["rotations"], viewmatrix=camera["world_to_camera"],

@@ -5,6 +5,7 @@
 // flush into the accumulator records).
 #pragma once
 #include <algorithm>
+#include <type_traits>
 
 #include "gsr_internal.h"
 #include "gsr_features.h"
@@ -91,6 +92,9 @@ __device__ __forceinline__ float blend_forward_weight(const float4 &ra, const fl
     return power > 0.0f ? 0.0f : alpha;
 }
 
+// run()'s default `open`: no pixel ever closes, the walk runs to the tile's largest n_contrib
+struct AlwaysOpen {};
+
 // One 256-thread workgroup per 16x16 tile, each of its four waves owning one 8x8 pixel block (lane = pixel), as in blend_fwd.hip.
 // The constructor and run() are the workgroup's: both hold workgroup barriers, so both stand outside any divergent path.
 struct FrameWalk {
@@ -154,16 +158,38 @@ struct FrameWalk {
     //                                              transmittance: T *= 1 - t where `applied`, at the point its own arithmetic has it.
     // The words are separate values, not an array, so that each stays one 16-byte LDS access and four registers.
     // A wave with wmax == 0 compacts nothing and still serves every batch's two barriers.
-    template <int WORDS, class Fill, class Entry>
-    __device__ __forceinline__ void run(const FrameK &f, Fill fill, Entry entry) const
+    //   open()                                     optional: "this lane's pixel may still change".  A walk with it is the early-exit
+    //                                              walk: entry() gets one more argument, the entry's 1-based list position; before
+    //                                              every batch but the first a lane counts as open while open() holds and its
+    //                                              n_contrib reaches into the batch; a wave without an open lane compacts nothing,
+    //                                              and the workgroup leaves when no wave has one.  The exit is taken between batches
+    //                                              only, by all 256 threads together (the verdict is read from LDS behind a barrier).
+    template <int WORDS, class Fill, class Entry, class Open = AlwaysOpen>
+    __device__ __forceinline__ void run(const FrameK &f, Fill fill, Entry entry, Open open = Open()) const
     {
         static_assert(WORDS == 2 || WORDS == 3, "two words, or three with the spare one");
+        constexpr bool EXIT = !std::is_same<Open, AlwaysOpen>::value;
+        __shared__ int s_open[EXIT ? 2 : 1]; // batch b's verdict in s_open[b & 1]; written only by an early-exit walk
         __shared__ float4 s_rec[BATCH][WORDS];
         __shared__ uint8_t s_mask[BATCH];
         __shared__ uint16_t s_list[4][BATCH + 2]; // per wave: the batch entries its block may see, in list order (+ two the walk reads ahead)
         const int tid = threadIdx.x;
+        int wlim = wmax; // where this wave's compaction ends: wmax, or 0 once none of its lanes is open
+        if constexpr (EXIT) {
+            if (tid < 2) s_open[tid] = 0; // (ordered before the first write, batch 1's, by batch 0's barriers)
+        }
         for (int base = 0; base < tmax; base += BATCH) {
+            if constexpr (EXIT) {
+                if (base > 0) {
+                    if (__builtin_amdgcn_ballot_w64(base < nc && open()) == 0ull) wlim = 0;
+                    else if (lane == 0) s_open[(base / BATCH) & 1] = 1;
+                }
+            }
             __syncthreads(); // every wave has walked the last batch
+            if constexpr (EXIT) {
+                if (base > 0 && s_open[(base / BATCH) & 1] == 0) break; // the same word for all 256 threads: a uniform exit
+                if (tid == 0) s_open[(base / BATCH + 1) & 1] = 0;         // last read two barriers ago, next written behind the one below
+            }
             const int cnt = min(BATCH, tmax - base);
             if (tid < cnt) {
                 const long long at = start + base + tid; // < start + tmax <= end <= D
@@ -185,7 +211,7 @@ struct FrameWalk {
             int n = 0;
             for (int gb = 0; gb < cnt; gb += 64) {
                 const int e = gb + lane;
-                const bool hit = e < cnt && base + e < wmax && (s_mask[e] & my_bits) != 0;
+                const bool hit = e < cnt && base + e < wlim && (s_mask[e] & my_bits) != 0;
                 const unsigned long long bits = __ballot(hit);
                 if (hit) s_list[wv][n + __popcll(bits & lt_mask)] = (uint16_t)e;
                 n += __popcll(bits);
@@ -203,7 +229,10 @@ struct FrameWalk {
                 float dx, dy, G;
                 const float t = blend_forward_weight(ra, rb, pixf_x, pixf_y, dx, dy, G);
                 const bool applied = base + e < nc && !(t < (1.0f / 255.0f));
-                if constexpr (WORDS == 3) entry(ra, rb, rc, dx, dy, G, t, applied);
+                if constexpr (EXIT) {
+                    if constexpr (WORDS == 3) entry(ra, rb, rc, dx, dy, G, t, applied, base + e + 1);
+                    else entry(ra, rb, dx, dy, G, t, applied, base + e + 1);
+                } else if constexpr (WORDS == 3) entry(ra, rb, rc, dx, dy, G, t, applied);
                 else entry(ra, rb, dx, dy, G, t, applied);
                 e = e1; e1 = e2;
                 ra = na; rb = nb;

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _args, _host, _lib
+from . import median_depth as _median_depth
 
 
 def check_volume(origin, voxel_size, dims, who="TSDFVolume"):
@@ -191,6 +192,9 @@ def weld(vertices, keys, colors=None):
     return verts, faces, cols
 
 
+DEPTH_MODES = ("expected", "median")     # fuse_views(depth_mode=...)
+
+
 def scene_bounds(cameras):
     """(centre (3,), half_side) of the cube the workflow fuses into when the caller names none: the centre is the point nearest to all
     optical axes (the cameras' common look-at point; their centroid when the axes are parallel), the half side is half of
@@ -206,10 +210,14 @@ def scene_bounds(cameras):
 
 
 def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, half_side=None, trunc=None, depth_max=float("inf"), min_weight=1.0,
-               alpha_min=_lib.NORMALS_ALPHA_MIN, w_max=float("inf"), device=None):
+               alpha_min=_lib.NORMALS_ALPHA_MIN, w_max=float("inf"), device=None, depth_mode="expected"):
     """The workflow behind examples/extract_mesh.py and train.py --mesh-out: render every camera (`render(camera)` returns the
     forward's (image, depth, buffers)), fuse depth_from_buffers' depth and the image into a cube of `resolution` voxels per side
-    (or of `voxel_size`) around scene_bounds (or `centre`, `half_side`), extract and weld.  Returns (verts, faces, colors, info)."""
+    (or of `voxel_size`) around scene_bounds (or `centre`, `half_side`), extract and weld.  Returns (verts, faces, colors, info).
+    depth_mode="median" fuses median_depth.view_depth of median_depth.render_median_depth instead: the depth of the Gaussian at which
+    the transmittance falls through one half, where "expected" is the blended inverse depth over the coverage."""
+    if depth_mode not in DEPTH_MODES:
+        raise ValueError(f"fuse_views: depth_mode must be one of {DEPTH_MODES} (got {depth_mode!r})")
     cameras = list(cameras)
     if not cameras:
         raise ValueError("fuse_views: needs at least one camera")
@@ -230,11 +238,17 @@ def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, ha
         for c in batch:
             image, depth, buffers = render(c)
             H, W = c["height"], c["width"]
-            depths.append(depth_from_buffers(depth.reshape(H, W), buffers["final_Ts"].reshape(H, W), alpha_min))
+            if depth_mode == "median":
+                med, _ = _median_depth.render_median_depth(buffers, H, W)
+                depths.append(_median_depth.view_depth(med, buffers["final_Ts"].reshape(H, W), alpha_min))
+            else:
+                depths.append(depth_from_buffers(depth.reshape(H, W), buffers["final_Ts"].reshape(H, W), alpha_min))
             colors.append(image.reshape(H, W, 3))
         vol.integrate_views(depths, batch, colors, depth_max=depth_max)
     vertices, vcolors, keys = vol.extract_mesh(min_weight)
     verts, faces, cols = weld(vertices, keys, vcolors)
     info = {"resolution": G, "voxel_size": float(voxel_size), "trunc": vol.trunc, "centre": [float(x) for x in centre], "half_side": half,
             "views": len(cameras), "triangles": int(len(faces)), "vertices": int(len(verts))}
+    if depth_mode != "expected":
+        info["depth_mode"] = depth_mode
     return verts, faces, cols, info

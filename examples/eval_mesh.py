@@ -13,7 +13,8 @@ within X aside as outliers (the DTU convention); --crop keeps the points inside 
 
 --demo torus needs no file: it samples a parametric torus, starts Gaussians at the samples (point_cloud.gaussians_from_points),
 renders them from orbiting cameras, fuses the depth into a TSDF volume of --resolution voxels per side, extracts the mesh and
-evaluates it against the torus: the bias of render -> TSDF -> mesh, reported in voxels.
+evaluates it against the torus: the bias of render -> TSDF -> mesh, reported in voxels.  --depth-mode median fuses the median depth
+(median_depth.py: the Gaussian at which the transmittance falls through one half) instead of the expected inverse depth.
 """
 import argparse
 import importlib
@@ -74,7 +75,7 @@ def orbit_cameras(gsr, views, distance, size, angle_x):
     return cams
 
 
-def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print):
+def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print, depth_mode="expected"):
     import torch
     me = gsr.mesh_eval
     R, r, half = 0.6, 0.25, 1.0
@@ -83,15 +84,16 @@ def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print):
     P = gsr.point_cloud.gaussians_from_points(start.cpu().numpy(), opacity=0.9, device="cuda")
     cams = orbit_cameras(gsr, views, 3.0, image_size, 0.6911112070083618)
     bg = np.zeros(3, np.float32)
-    mverts, mfaces, _, info = gsr.tsdf.fuse_views(lambda c: gsr.render_view(P, c, bg), cams, resolution=resolution, centre=(0.0, 0.0, 0.0), half_side=half)
+    mverts, mfaces, _, info = gsr.tsdf.fuse_views(lambda c: gsr.render_view(P, c, bg), cams, resolution=resolution, centre=(0.0, 0.0, 0.0), half_side=half,
+                                                  depth_mode=depth_mode)
     torch.cuda.synchronize()
     if info["triangles"] < 1:
         raise SystemExit("--demo torus: the extraction gave no triangle (more --views or a lower --resolution)")
     h = info["voxel_size"]
     m = evaluate_mesh(gsr, mverts, mfaces, verts, faces, samples=200_000, seed=seed + 1, thresholds=(h, 2 * h, 4 * h), log=log)
-    m.update(demo="torus", resolution=info["resolution"], views=views, voxel_size=h, triangles=info["triangles"], vertices=info["vertices"],
+    m.update(demo="torus", depth_mode=depth_mode, resolution=info["resolution"], views=views, voxel_size=h, triangles=info["triangles"], vertices=info["vertices"],
              gaussians=int(start.shape[0]), image_size=image_size, accuracy_voxels=m["accuracy"] / h, completeness_voxels=m["completeness"] / h)
-    log(f"demo torus: {m['gaussians']} Gaussians, {views} views of {image_size}^2 into {m['resolution']}^3 voxels of {h:.5f}: accuracy "
+    log(f"demo torus ({depth_mode} depth): {m['gaussians']} Gaussians, {views} views of {image_size}^2 into {m['resolution']}^3 voxels of {h:.5f}: accuracy "
         f"{m['accuracy_voxels']:.3f} voxels, completeness {m['completeness_voxels']:.3f} voxels, {m['triangles']} triangles")
     return m
 
@@ -114,6 +116,7 @@ def main():
     ap.add_argument("--views", type=int, default=32, metavar="V", help="--demo: orbit views")
     ap.add_argument("--demo-points", type=int, default=100_000, metavar="N", help="--demo: Gaussians on the torus")
     ap.add_argument("--demo-image", type=int, default=256, metavar="PX", help="--demo: image side")
+    ap.add_argument("--depth-mode", choices=["expected", "median"], default="expected", help="--demo: the depth the volume is fused from")
     args = ap.parse_args()
     if args.demo is None and (args.mesh is None or args.gt is None):
         ap.error("--mesh and --gt are required (or --demo torus)")
@@ -121,7 +124,7 @@ def main():
         ap.error("--demo: --resolution must be in 2 .. 2048, --views >= 1, --demo-points >= 4, --demo-image >= 8")
     gsr = importlib.import_module("3dgs-native_amd")
     if args.demo:
-        m = demo_torus(gsr, args.resolution, args.views, args.demo_points, args.demo_image, seed=args.seed)
+        m = demo_torus(gsr, args.resolution, args.views, args.demo_points, args.demo_image, seed=args.seed, depth_mode=args.depth_mode)
     else:
         try:
             verts, faces, _ = gsr.point_cloud.load_mesh_ply(args.mesh)

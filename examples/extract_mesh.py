@@ -9,6 +9,8 @@ The cube is centred on the cameras' common look-at point with half of their exte
 --center / --half-side name it.  --voxel-size S or --resolution R (voxels per side; default 256) set the grid, --trunc the
 truncation distance (default 4 voxels), --depth-max drops far depths, --min-weight K keeps only cells all of whose corners were
 observed with weight K.  Extraction is offline: it reads the triangle count back once, and welds on the host.
+--depth-mode median fuses the median depth (median_depth.py: the depth of the Gaussian at which the transmittance falls through one
+half, what the surface methods fuse bounded scenes from) instead of the expected inverse depth over the coverage.
 --gt G.ply evaluates the mesh right away against a ground truth in the same frame (accuracy, completeness, F-score: eval_mesh.py).
 """
 import argparse
@@ -65,6 +67,7 @@ def main():
     ap.add_argument("--min-weight", type=float, default=1.0, metavar="K")
     ap.add_argument("--center", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--half-side", type=float, default=None, metavar="E")
+    ap.add_argument("--depth-mode", choices=["expected", "median"], default="expected", help="the depth the volume is fused from")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--record", default=None, metavar="FILE", help="write the run's figures (resolution, triangles, seconds) as one JSON line")
     ap.add_argument("--gt", default=None, metavar="G.ply", help="evaluate the mesh against this ground truth in the same frame (examples/eval_mesh.py)")
@@ -86,7 +89,7 @@ def main():
          "shs": torch.as_tensor(ply["shs"]).to(dev)}
     cams = load_cameras(gsr, args.dataset, args.views)
     info = mesh_from_model(gsr, P, cams, args.out, voxel_size=args.voxel_size, resolution=args.resolution or 256, centre=args.center,
-                           half_side=args.half_side, trunc=args.trunc, depth_max=args.depth_max, min_weight=args.min_weight)
+                           half_side=args.half_side, trunc=args.trunc, depth_max=args.depth_max, min_weight=args.min_weight, depth_mode=args.depth_mode)
     if args.gt:
         sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
         from eval_mesh import evaluate_mesh

@@ -46,6 +46,12 @@ Gaussians the distortion term flattened into the surface.  No target is needed; 
 --normal-consistency-from-iter K switches it on at iteration K.  With the weight, or with --report-normal-consistency alone, the
 summary has train_normal_consistency_deg: the mean angle in degrees between N / |N| and n_d over counted pixels and views at the end.
 
+Median depth (include/gsr_median_depth.h, median_depth.py): --depth-render median takes --lambda-depth's L1 on the median inverse depth
+(the inverse depth of the Gaussian at which the transmittance falls through one half) instead of the expected inverse depth, masked
+to the target's mask and to the pixels that have a median; its gradient reaches only the chosen Gaussian's depth, through a stage of
+the backward.  The summary then has train_median_depth_l1_mean beside train_depth_l1_mean.  --mesh-depth median makes --mesh-out fuse
+the median depth.  Both default to "expected": today's behaviour.
+
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
@@ -294,12 +300,13 @@ def perturb_depth_targets(depth_targets, noise, seed):
     return out
 
 
-def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None):
+def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None, median=False):
     """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets.
     Third: with depth targets, {"train_depth_corr_mean": the mean Pearson correlation rho of the rendered inverse depth with the
     targets as given, "train_depth_fit": each view's (s, b) of render ~ s target + b (include/gsr_depth_corr.h)}, and with
-    clean_depth_targets (--depth-noise) "train_depth_l1_clean_mean", the first score against the unperturbed targets."""
-    dl, al, dc = [], [], []
+    clean_depth_targets (--depth-noise) "train_depth_l1_clean_mean", the first score against the unperturbed targets; with `median`
+    (--depth-render median) "train_median_depth_l1_mean", the first score of the median inverse depth over the pixels that have one."""
+    dl, al, dc, dm = [], [], [], []
     fits = torch.zeros((len(cams), 4), device=P["positions"].device) if depth_targets is not None else None
     for k, c in enumerate(cams):
         _, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
@@ -307,6 +314,10 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_t
             t = depth_targets[k]
             dl.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
             gsr.loss.depth_corr_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False, fit_out=fits[k])
+            if median:
+                med, contrib = gsr.median_depth.render_median_depth(buf, c["height"], c["width"])
+                mask = ((t > 0) & (contrib > 0).reshape(t.shape)).float()
+                dm.append(float(gsr.loss.depth_loss_and_gradients(med.reshape(t.shape), t, mask, want_grad=False)[0].item()) / t.numel())
             if clean_depth_targets is not None:
                 t = clean_depth_targets[k]
                 dc.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
@@ -319,6 +330,8 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_t
         extra = {"train_depth_corr_mean": float(f[:, 0].mean()), "train_depth_fit": [[float(s), float(b)] for s, b in f[:, 1:3]]}
         if dc:
             extra["train_depth_l1_clean_mean"] = float(np.mean(dc))
+        if dm:
+            extra["train_median_depth_l1_mean"] = float(np.mean(dm))
     return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None), extra
 
 
@@ -400,7 +413,9 @@ def finish(run, wall):
         summary["exposure_applied"] = {"train_views": True, "train_eval_scales": True, "holdout_views": False, "holdout_eval_scales": False}
         summary["exposure_final"] = expo.state_dict()["E"]
         summary["exposure_steps"] = list(expo.steps)
-    d_l1, a_l1, d_extra = aux_scores(P, cams, V.depth_targets, V.alpha_targets, bg, mode_kw, V.clean_depth_targets)
+    d_l1, a_l1, d_extra = aux_scores(P, cams, V.depth_targets, V.alpha_targets, bg, mode_kw, V.clean_depth_targets, median=args.depth_render == "median")
+    if args.depth_render != "expected":
+        summary["depth_render"] = args.depth_render
     if d_l1 is not None:
         summary["train_depth_l1_mean"] = d_l1
     summary.update(d_extra)
@@ -506,6 +521,10 @@ def parse_args(argv=None):
                     "own units.  pearson: 1 - the Pearson correlation of the rendered inverse depth with the target over the mask "
                     "(include/gsr_depth_corr.h), for relative targets: inverse depth known only up to an unknown scale a > 0 and shift b "
                     "per image (t -> a t + b), as monocular depth networks give it.  Needs --lambda-depth > 0; not divided by W H")
+    ap.add_argument("--depth-render", default="expected", choices=["expected", "median"], help="the rendered inverse depth --lambda-depth's "
+                    "L1 is taken on: the forward's expected inverse depth, or the median inverse depth (include/gsr_median_depth.h: the "
+                    "Gaussian at which the transmittance falls through one half), masked to the pixels that have one; its gradient is a "
+                    "stage of the backward.  Needs --depth-loss l1")
     ap.add_argument("--depth-noise", type=float, default=0.0, metavar="S", help="make every depth target relative once, at load: "
                     "a_v t + b_v on its masked pixels, a_v = exp(U(-S, S)), b_v = U(0, S) * mean(t over the mask) per view; the summary "
                     "then also scores the depth against the clean targets (train_depth_l1_clean_mean)")
@@ -540,6 +559,8 @@ def parse_args(argv=None):
     ap.add_argument("--mesh-out", default=None, metavar="FILE", help="after the last iteration, fuse depth and colour renders of the training "
                     "views into a TSDF volume and write the extracted triangle mesh (include/gsr_tsdf.h; what examples/extract_mesh.py does). "
                     "Off by default; training itself is unchanged")
+    ap.add_argument("--mesh-depth", default="expected", choices=["expected", "median"], help="the depth --mesh-out fuses: the expected "
+                    "inverse depth over the coverage, or the median depth (include/gsr_median_depth.h)")
     ap.add_argument("--mesh-resolution", type=int, default=256, metavar="R", help="voxels per side of --mesh-out's volume")
     ap.add_argument("--mesh-min-weight", type=float, default=1.0, metavar="K", help="--mesh-out keeps cells whose corners all have weight K")
     ap.add_argument("--optimize-poses", action="store_true", help="refine each view's pose with Adam on the camera gradients "
@@ -649,6 +670,7 @@ def check_args(args):
         (args.normal_dir and not args.dataset, "--normal-dir needs --dataset (the targets are named after its frames)"),
         (args.lambda_normal > 0.0 and args.dataset and not args.normal_dir, "--lambda-normal with --dataset needs --normal-dir (normal targets)"),
         (args.depth_loss == "pearson" and not args.lambda_depth > 0.0, "--depth-loss pearson needs --lambda-depth > 0 (its weight)"),
+        (args.depth_render == "median" and args.depth_loss != "l1", "--depth-render median needs --depth-loss l1"),
         (not (args.depth_noise >= 0.0 and finite(args.depth_noise)), "--depth-noise must be >= 0 and finite"),
         (args.depth_noise > 0.0 and args.dataset and not args.depth_dir,
          "--depth-noise with --dataset needs --depth-dir (there is no depth target to perturb)"),
@@ -889,6 +911,12 @@ def train_view(run, it, v, alone, capacity=None):
     kw = {}
     if args.lambda_depth > 0.0 and args.depth_loss == "pearson":        # lambda_d (1 - rho): blind to the target's scale and shift
         kw["dL_ddepth_image"] = gsr.loss.depth_corr_loss_and_gradients(dep, V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
+    elif args.lambda_depth > 0.0 and args.depth_render == "median":     # the same L1 on the median inverse depth, where a pixel has one
+        med, contrib = gsr.median_depth.render_median_depth(buf, c["height"], c["width"])
+        t = V.depth_targets[v]
+        mask = V.depth_masks[v] * (contrib > 0).reshape(t.shape)         # the target's mask and "this pixel has a median"
+        kw["dL_dmedian_depth"] = gsr.loss.depth_loss_and_gradients(med.reshape(t.shape), t, mask, args.lambda_depth)[1]
+        kw["median_contributor"] = contrib
     elif args.lambda_depth > 0.0:                                       # (the curve keeps the colour loss: the terms are in the summary)
         kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
     if args.lambda_alpha > 0.0:
@@ -1100,7 +1128,7 @@ def main(argv=None):
         if args.mesh_out:                                               # the model's surface from its training views (extract_mesh.py)
             from extract_mesh import mesh_from_model
             mesh_from_model(gsr, run.model.params, run.views.cams, args.mesh_out, bg=run.bg, mode_kw=run.mode_kw, resolution=args.mesh_resolution,
-                            min_weight=args.mesh_min_weight, alpha_min=args.normal_alpha_min)
+                            min_weight=args.mesh_min_weight, alpha_min=args.normal_alpha_min, depth_mode=args.mesh_depth)
 
 
 if __name__ == "__main__":
