@@ -12,6 +12,6 @@ pointers.  There is no fallback implementation.
 """
 from .forward import render_gaussians, render_view  # noqa: F401
 from .backward import backward, backward_view  # noqa: F401
-from . import cameras, scenes, config, dist, loss, optimizer, scheduler, densify, point_cloud, pose, filter3d, exposure, knn, features, normals, tsdf, distortion, normal_render, mesh_eval, median_depth  # noqa: F401
+from . import cameras, scenes, config, dist, loss, optimizer, scheduler, densify, point_cloud, pose, filter3d, exposure, knn, features, normals, tsdf, distortion, normal_render, mesh_eval, median_depth, plane_depth  # noqa: F401
 
-__all__ = ["render_gaussians", "render_view", "backward", "backward_view", "cameras", "scenes", "config", "dist", "loss", "optimizer", "scheduler", "densify", "point_cloud", "pose", "filter3d", "exposure", "knn", "features", "normals", "tsdf", "distortion", "normal_render", "mesh_eval", "median_depth"]
+__all__ = ["render_gaussians", "render_view", "backward", "backward_view", "cameras", "scenes", "config", "dist", "loss", "optimizer", "scheduler", "densify", "point_cloud", "pose", "filter3d", "exposure", "knn", "features", "normals", "tsdf", "distortion", "normal_render", "mesh_eval", "median_depth", "plane_depth"]

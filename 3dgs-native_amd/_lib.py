@@ -263,6 +263,19 @@ MEDIAN_DEPTH_EXPORTS = {
     "gsr_median_depth_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp]),
 }
 
+# include/gsr_plane_depth.h: the ray-plane intersection depth over a frame's lists (the frame struct is gsr_distortion.h's), the
+# per-Gaussian slopes it blends, and the gradients of both (its own header, so its own table)
+PLANE_DEPTH_EXPORTS = {
+    "gsr_plane_slopes": (C.c_int, [C.c_int64, vp, vp, vp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, C.c_int32, vp, vp]),
+    "gsr_plane_slopes_backward": (C.c_int, [C.c_int64, vp, vp, vp, C.POINTER(C.c_float), C.c_float, C.c_float, C.c_int32, C.c_int32, vp, vp, vp, vp]),
+    "gsr_plane_depth_forward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp]),
+    "gsr_plane_depth_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp, vp, vp]),
+}
+PLANE_DEPTH_MIN_COS = 0.1           # GSR_PLANE_DEPTH_MIN_COS (a float32 constant: 0.1f)
+PLANE_DEPTH_MAX_FLATNESS = 0.5      # GSR_PLANE_DEPTH_MAX_FLATNESS
+PLANE_DEPTH_NEAR = 0.2              # GSR_PLANE_DEPTH_NEAR (a float32 constant: 0.2f)
+PLANE_DEPTH_MAX_RATIO = 4.0         # GSR_PLANE_DEPTH_MAX_RATIO
+
 # include/gsr_normal_render.h: the Gaussians' own normals, their image over a frame's lists with its gradient into the backward's
 # accumulator records, and the depth-normal consistency term (its own header, so its own table)
 NORMAL_RENDER_EXPORTS = {
@@ -373,7 +386,7 @@ def lib():
                                   + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
                                   + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())
                                   + list(NORMAL_RENDER_EXPORTS.items()) + list(MESH_EVAL_EXPORTS.items())
-                                  + list(MEDIAN_DEPTH_EXPORTS.items())):
+                                  + list(MEDIAN_DEPTH_EXPORTS.items()) + list(PLANE_DEPTH_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -77,6 +77,22 @@ else; the AUX per-Gaussian half carries it on to the means, and the result carri
 legal (dL_dpixels=None).  A frame that does not carry the forward's records needs geom_buffer["depths"], as for the distortion term.
 It composes with camera_grad, the antialiased mode, filter_3d, capacity frames and sh_gradient="factored"; `dL_dmean2D_abs` stays
 the colour, depth and alpha terms' alone.  Without the two keywords the call is exactly the one above.
+
+`dL_dplane_depth=g, plane_slopes=s, plane_depth_image=pd` (include/gsr_plane_depth.h; all three or none, and with them
+`gaussian_normals=n`, the normals s = plane_depth.plane_slopes(n, ...) was made from) add the gradient of sum_p g[p] pd[p],
+pd = plane_depth.render_plane_depth(s, ...) the blended ray-plane intersection inverse depth.  The stage runs between the two halves,
+after the distortion and normal stages and before the median one: it ADDS its screen-space gradients into columns 3-4, 6, 7, 9 and 10
+of the accumulator records -- never column 11, which stays the centre-depth terms' alone -- and writes `dL_dplane_moments`, an (N, 3)
+buffer (sum w g, sum w g (p.x - x_k), sum w g (p.y - y_k)) that the result carries, with `dL_dinv_depths`.  After the per-Gaussian half
+gsr_plane_slopes_backward turns the moments into the means' share, ADDED to dL_dmean3D, and dL/d(normals), which
+gsr_gaussian_normals_backward carries on to dL_drot (a second call of it when the normal image's stage is present too: it adds), from
+the scales (raw under filter_3d, as for the normals), rotations, means and viewmatrix AS THE CALLER PASSED THEM;
+`plane_param_grad=False` skips both kernels, for callers who want only the moments.  `gaussian_normals` alone with these three keywords
+belongs to this stage; with `dL_dnormal_image` and `normal_image` as well it serves both.  `dL_dplane_depth` alone is legal
+(dL_dpixels=None).  A frame that does not carry the forward's records needs geom_buffer["depths"], as for the distortion term.  It
+composes with camera_grad (the screen-space columns only), the antialiased mode, filter_3d, capacity frames and
+sh_gradient="factored"; `dL_dmean2D_abs` stays the colour, depth and alpha terms' alone.  Without the three keywords the call is
+exactly the one above.
 """
 import ctypes as C
 from types import SimpleNamespace
@@ -91,6 +107,7 @@ from . import filter3d as _filter3d
 from . import forward as _forward
 from . import median_depth as _median_depth
 from . import normal_render as _normal_render
+from . import plane_depth as _plane_depth
 
 _ZERO = {}
 
@@ -249,6 +266,21 @@ def _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, normal
                                             _host.ptr(dnormals), stream))
 
 
+def _plane_stage(L, st, out, N, point_list, ranges, n_contrib, g_plane, slopes, plane_image, dmoments, stream):
+    """The plane-depth image's screen-space gradient (include/gsr_plane_depth.h), added into the accumulator records the blend half
+    has just filled, and the three moments per Gaussian into `dmoments`.  The frame is the one _distortion_stage reads."""
+    D = int(point_list.numel())
+    if N == 0:
+        return
+    if D == 0:
+        dmoments.zero_()
+        return
+    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
+    frame = _distortion.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), rec[:, 9], st.masks)
+    _lib.check(L.gsr_plane_depth_backward(C.byref(frame), _host.ptr(slopes), _host.ptr(g_plane), _host.ptr(plane_image), out.acc.data_ptr(),
+                                          _host.ptr(dmoments), stream))
+
+
 def _median_stage(L, st, out, N, point_list, ranges, n_contrib, g_med, contrib, stream):
     """The median inverse depth's gradient (include/gsr_median_depth.h): g[p] added into column 11 of the accumulator record of the
     Gaussian each pixel chose.  The frame is the one _distortion_stage reads; the kernel reads its lists and ranges only."""
@@ -324,7 +356,8 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
              radii=None, means2D=None, conic_opacity=None, rgb=None, clamped=None, cov3Ds=None, geom_buffer=None,
              binning_buffer=None, img_buffer=None, degree=3, debug=False, *, sh_gradient="dense", on_payload=None,
              dL_ddepth_image=None, dL_dalpha_image=None, camera_grad=False, absgrad=False, rasterize_mode="classic", filter_3d=None,
-             dL_ddistortion=None, distortion_moments=None, dL_dmedian_depth=None, median_contributor=None, **rendered_stage):
+             dL_ddistortion=None, distortion_moments=None, dL_dmedian_depth=None, median_contributor=None,
+             dL_dplane_depth=None, plane_slopes=None, plane_depth_image=None, plane_param_grad=True, **rendered_stage):
     # The keywords of include/gsr_normal_render.h -- dL_dnormal_image, gaussian_normals, normal_image (None) and normal_param_grad (True)
     # -- are taken by name from `rendered_stage` (normal_render.stage_keywords), not listed above: tests/test_normals_abi.py holds that
     # the depth-normals stage of include/gsr_normals.h added no parameter whose name contains "normal" to this signature, by that
@@ -332,7 +365,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     dL_dnormal_image, gaussian_normals, normal_image, normal_param_grad = _normal_render.stage_keywords(rendered_stage)
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
     distortion = _distortion.check_gradient_pair(dL_ddistortion, distortion_moments)
-    normal = _normal_render.check_gradient_triple(dL_dnormal_image, gaussian_normals, normal_image)
+    plane = _plane_depth.check_gradient_triple(dL_dplane_depth, plane_slopes, plane_depth_image, gaussian_normals)
+    if plane and dL_dnormal_image is None and normal_image is None:
+        normal = False      # gaussian_normals is the plane stage's alone
+    else:
+        normal = _normal_render.check_gradient_triple(dL_dnormal_image, gaussian_normals, normal_image)
     median = _median_depth.check_gradient_pair(dL_dmedian_depth, median_contributor)
     frame_co = conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity")
     # (before anything touches the GPU: a frame rendered without the filter or with another one, raw tensors written since the render)
@@ -348,11 +385,12 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     aa_tag = _aa_scale_of(frame_co, opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
-    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion or normal or median
+    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion or normal or median or plane
     if dL_dpixels is None and not aux:
         raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments, "
-                         "dL_dnormal_image with gaussian_normals and normal_image, or dL_dmedian_depth with median_contributor)")
-    view16 = _normal_render.view_floats(viewmatrix, "backward(dL_dnormal_image=...)") if normal else None
+                         "dL_dnormal_image with gaussian_normals and normal_image, or dL_dmedian_depth with median_contributor, or "
+                         "dL_dplane_depth with plane_slopes, plane_depth_image and gaussian_normals)")
+    view16 = _normal_render.view_floats(viewmatrix, "backward(dL_dnormal_image=...)") if normal or plane else None
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
     L = _lib.lib()
     dev = _host.device_of(means3D, dL_dpixels, shs, radii)
@@ -365,8 +403,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     g_dist, moments = opt(dL_ddistortion, (H, W)), opt(distortion_moments, (H, W, 4))
     g_normal, gn, nimg = opt(dL_dnormal_image, (H, W, 3)), opt(gaussian_normals, (N, 3)), opt(normal_image, (H, W, 3))
     g_med = opt(dL_dmedian_depth, (H, W))
+    g_plane, pd_img = opt(dL_dplane_depth, (H, W)), opt(plane_depth_image, (H, W))
+    if plane:
+        _plane_depth.check_slopes(plane_slopes, N)
     med_contrib = _host.to_dev(median_contributor, torch.int32, dev, (H, W)) if median else None
-    if (distortion or normal or median) and dpix is None and g_depth is None and g_alpha is None:
+    if (distortion or normal or median or plane) and dpix is None and g_depth is None and g_alpha is None:
         g_alpha = torch.zeros((H, W), dtype=f32, device=dev)   # the blend half wants one image gradient: a zero one clears and adds nothing
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
@@ -393,12 +434,15 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         m2d = _host.to_dev(means2D, f32, dev, (-1, 2))
         con = _host.to_dev(conic_opacity, f32, dev, (-1, 4))
         col = _host.to_dev(rgb, f32, dev, (-1, 3))
-        if (g_depth is not None or distortion or median) and geom_buffer is not None:
+        if (g_depth is not None or distortion or median or plane) and geom_buffer is not None:
             # the re-packed records carry 1/depth only from the forward's depths (gsr_aux_grads.h: without them, GSR_E_NULL)
             depths = opt(geom_buffer.get("depths"), (-1,))
         if distortion and depths is None:
             raise ValueError("backward(dL_ddistortion=...) on a frame that does not carry the forward's records needs "
                              "geom_buffer['depths']: the distortion is a function of the Gaussians' inverse depths")
+        if plane and depths is None:
+            raise ValueError("backward(dL_dplane_depth=...) on a frame that does not carry the forward's records needs "
+                             "geom_buffer['depths']: the plane depth is a function of the Gaussians' inverse depths")
         if median and depths is None:
             raise ValueError("backward(dL_dmedian_depth=...) on a frame that does not carry the forward's records needs "
                              "geom_buffer['depths']: the per-Gaussian half carries dL/d(1/depth) on through the re-packed records")
@@ -425,22 +469,36 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         binning = _lib.GsrBinning(st.D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(st.masks), _host.ptr(st.order),
                                   _host.ptr(out.ws) if cleared else None, 1 if cleared else 0)
         stream = _host.raw_stream(dev)
-        stage = dnormals = None
+        stage = dnormals = dmoments = None
         if normal:
             dnormals = torch.empty((N, 3), dtype=f32, device=dev)
-        if distortion or normal or median:
-            def stage():                    # in this order when several are present: distortion, normals, median depth
+        if plane:
+            dmoments = torch.empty((N, 3), dtype=f32, device=dev)
+        if distortion or normal or median or plane:
+            def stage():                    # in this order when several are present: distortion, normals, plane depth, median depth
                 if distortion:
                     _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
                 if normal:
                     _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, gn, nimg, dnormals, stream)
+                if plane:
+                    _plane_stage(L, st, out, N, point_list, ranges, n_contrib, g_plane, plane_slopes, pd_img, dmoments, stream)
                 if median:
                     _median_stage(L, st, out, N, point_list, ranges, n_contrib, g_med, med_contrib, stream)
         dcam = _launch(L, scene, cam, geom, binning, img, pg, out, _lib.BWD_ABSGRAD if absgrad else 0, aa_scale, aux, on_payload,
                        camera_grad, stream, stage)
+        nsc = sc
+        if (normal or plane) and filt is not None:
+            nsc = _host.to_dev(raw_scales, f32, dev, (-1, 3))
+        if plane and plane_param_grad and N > 0:
+            # the moments on to the means (added) and, through the normals, to the quaternions: from the caller's scales (raw under
+            # filter_3d), rotations and means
+            dplane_n = torch.empty((N, 3), dtype=f32, device=dev)
+            _lib.check(L.gsr_plane_slopes_backward(N, _host.ptr(gn), _host.ptr(nsc), _host.ptr(means), view16[0], float(tan_fovx), float(tan_fovy),
+                                                   W, H, _host.ptr(dmoments), _host.ptr(out.dL_dmean3D), _host.ptr(dplane_n), stream))
+            _lib.check(L.gsr_gaussian_normals_backward(N, _host.ptr(nsc), _host.ptr(rot), _host.ptr(means), view16[0], _host.ptr(dplane_n),
+                                                       _host.ptr(out.dL_drot), stream))
         if normal and normal_param_grad and N > 0:
             # the normals' own gradient, on to the quaternions: from the caller's scales (raw under filter_3d), rotations and means
-            nsc = sc if filt is None else _host.to_dev(raw_scales, f32, dev, (-1, 3))
             _lib.check(L.gsr_gaussian_normals_backward(N, _host.ptr(nsc), _host.ptr(rot), _host.ptr(means), view16[0], _host.ptr(dnormals),
                                                        _host.ptr(out.dL_drot), stream))
         if filt is not None:
@@ -449,6 +507,9 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     if normal:
         _host.written_in_place(dnormals)
         res["dL_dgaussian_normals"] = dnormals      # (N, 3): dL/d(gaussian_normals), what gsr_gaussian_normals_backward carried on to dL_drot
+    if plane:
+        _host.written_in_place(dmoments)
+        res["dL_dplane_moments"] = dmoments         # (N, 3): what gsr_plane_slopes_backward carried on to dL_dmean3D and dL_drot
     return res
 
 
@@ -458,9 +519,14 @@ def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
     of three dicts, nothing else; the tensors go through as they are.  **kw: sh_gradient, camera_grad, absgrad, dL_ddepth_image,
     dL_dalpha_image, geom_buffer, rasterize_mode, filter_3d, dL_ddistortion with distortion_moments (a frame whose records were
     written since the render is re-packed from buffers["depths"], handed on here as geom_buffer), dL_dnormal_image with
-    gaussian_normals and normal_image, normal_param_grad, dL_dmedian_depth with median_contributor (re-packed like the distortion term)."""
-    _normal_render.check_gradient_triple(kw.get("dL_dnormal_image"), kw.get("gaussian_normals"), kw.get("normal_image"))
-    needs_depths = _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments"))
+    gaussian_normals and normal_image, normal_param_grad, dL_dmedian_depth with median_contributor (re-packed like the distortion term),
+    dL_dplane_depth with plane_slopes, plane_depth_image and gaussian_normals (re-packed likewise), plane_param_grad."""
+    plane = _plane_depth.check_gradient_triple(kw.get("dL_dplane_depth"), kw.get("plane_slopes"), kw.get("plane_depth_image"),
+                                               kw.get("gaussian_normals"))
+    if not (plane and kw.get("dL_dnormal_image") is None and kw.get("normal_image") is None):
+        _normal_render.check_gradient_triple(kw.get("dL_dnormal_image"), kw.get("gaussian_normals"), kw.get("normal_image"))
+    needs_depths = plane
+    needs_depths |= _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments"))
     needs_depths |= _median_depth.check_gradient_pair(kw.get("dL_dmedian_depth"), kw.get("median_contributor"))
     if needs_depths and "geom_buffer" not in kw and "depths" in buffers:
         kw["geom_buffer"] = {"depths": buffers["depths"]}

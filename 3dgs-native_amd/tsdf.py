@@ -23,6 +23,7 @@ import torch
 
 from . import _args, _host, _lib
 from . import median_depth as _median_depth
+from . import plane_depth as _plane_depth
 
 
 def check_volume(origin, voxel_size, dims, who="TSDFVolume"):
@@ -210,14 +211,23 @@ def scene_bounds(cameras):
 
 
 def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, half_side=None, trunc=None, depth_max=float("inf"), min_weight=1.0,
-               alpha_min=_lib.NORMALS_ALPHA_MIN, w_max=float("inf"), device=None, depth_mode="expected"):
+               alpha_min=_lib.NORMALS_ALPHA_MIN, w_max=float("inf"), device=None, depth_mode="expected", plane_depth=False, params=None):
     """The workflow behind examples/extract_mesh.py and train.py --mesh-out: render every camera (`render(camera)` returns the
     forward's (image, depth, buffers)), fuse depth_from_buffers' depth and the image into a cube of `resolution` voxels per side
     (or of `voxel_size`) around scene_bounds (or `centre`, `half_side`), extract and weld.  Returns (verts, faces, colors, info).
     depth_mode="median" fuses median_depth.view_depth of median_depth.render_median_depth instead: the depth of the Gaussian at which
-    the transmittance falls through one half, where "expected" is the blended inverse depth over the coverage."""
+    the transmittance falls through one half, where "expected" is the blended inverse depth over the coverage.
+    plane_depth=True is another axis, the depth MODEL under the expected blend: every view fuses depth_from_buffers of
+    plane_depth.render_plane_depth (include/gsr_plane_depth.h: a flat Gaussian contributes the depth at which the pixel's ray meets its
+    plane, not the depth of its centre).  It needs `params`, the dict `render` draws from (positions, scales, rotations), and raises
+    with depth_mode="median": the plane depth under the median rule is not built."""
     if depth_mode not in DEPTH_MODES:
         raise ValueError(f"fuse_views: depth_mode must be one of {DEPTH_MODES} (got {depth_mode!r})")
+    if plane_depth and depth_mode != "expected":
+        raise ValueError("fuse_views: plane_depth=True blends the plane depth under the expected rule: it does not combine with "
+                         f"depth_mode={depth_mode!r}")
+    if plane_depth and not (isinstance(params, dict) and all(k in params for k in ("positions", "scales", "rotations"))):
+        raise ValueError("fuse_views: plane_depth=True needs params, the dict with positions, scales and rotations that render() draws from")
     cameras = list(cameras)
     if not cameras:
         raise ValueError("fuse_views: needs at least one camera")
@@ -238,7 +248,10 @@ def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, ha
         for c in batch:
             image, depth, buffers = render(c)
             H, W = c["height"], c["width"]
-            if depth_mode == "median":
+            if plane_depth:
+                pd = _plane_depth.render_view_plane_depth(params, c, buffers)[0]
+                depths.append(depth_from_buffers(pd, buffers["final_Ts"].reshape(H, W), alpha_min))
+            elif depth_mode == "median":
                 med, _ = _median_depth.render_median_depth(buffers, H, W)
                 depths.append(_median_depth.view_depth(med, buffers["final_Ts"].reshape(H, W), alpha_min))
             else:
@@ -251,4 +264,6 @@ def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, ha
             "views": len(cameras), "triangles": int(len(faces)), "vertices": int(len(verts))}
     if depth_mode != "expected":
         info["depth_mode"] = depth_mode
+    if plane_depth:
+        info["plane_depth"] = True
     return verts, faces, cols, info

@@ -14,7 +14,9 @@ within X aside as outliers (the DTU convention); --crop keeps the points inside 
 --demo torus needs no file: it samples a parametric torus, starts Gaussians at the samples (point_cloud.gaussians_from_points),
 renders them from orbiting cameras, fuses the depth into a TSDF volume of --resolution voxels per side, extracts the mesh and
 evaluates it against the torus: the bias of render -> TSDF -> mesh, reported in voxels.  --depth-mode median fuses the median depth
-(median_depth.py: the Gaussian at which the transmittance falls through one half) instead of the expected inverse depth.
+(median_depth.py: the Gaussian at which the transmittance falls through one half) instead of the expected inverse depth;
+--depth-mode plane fuses the ray-plane intersection depth (plane_depth.py), and --demo-flat RATIO makes the demo's Gaussians discs on
+the torus, which that depth needs: an isotropic Gaussian has no plane and keeps its centre depth.
 """
 import argparse
 import importlib
@@ -75,24 +77,45 @@ def orbit_cameras(gsr, views, distance, size, angle_x):
     return cams
 
 
-def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print, depth_mode="expected"):
+def flat_discs(P, R, ratio):
+    """The demo's isotropic Gaussians turned into discs on the torus: the shortest axis (z of the local frame) along the torus's
+    analytic normal at the Gaussian's centre, the in-plane scales the kNN scale the Gaussian had, the thickness `ratio` times it."""
+    import torch
+    p = P["positions"]
+    rho = torch.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2).clamp_min(1e-12)
+    ring = torch.stack([R * p[:, 0] / rho, R * p[:, 1] / rho, torch.zeros_like(rho)], 1)          # the nearest point of the centre circle
+    n = torch.nn.functional.normalize(p - ring, dim=1)
+    # the shortest rotation that takes e_z to n: q = (e_z x n, 1 + e_z . n), normalised, as (x, y, z, w)
+    q = torch.stack([-n[:, 1], n[:, 0], torch.zeros_like(rho), 1.0 + n[:, 2]], 1)
+    q = torch.where((q.norm(dim=1, keepdim=True) > 1e-6), q, torch.tensor([1.0, 0.0, 0.0, 0.0], device=p.device).expand_as(q))
+    P["rotations"] = torch.nn.functional.normalize(q, dim=1).contiguous()
+    s = P["scales"].clone()
+    s[:, 2] = float(ratio) * s[:, :2].min(dim=1).values
+    P["scales"] = s.contiguous()
+    return P
+
+
+def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print, depth_mode="expected", flat=None):
     import torch
     me = gsr.mesh_eval
     R, r, half = 0.6, 0.25, 1.0
     verts, faces = torus_mesh(R, r, 256, 128)
     start, _ = me.sample_mesh(me.soup(verts, faces), samples=points, seed=seed)
     P = gsr.point_cloud.gaussians_from_points(start.cpu().numpy(), opacity=0.9, device="cuda")
+    if flat is not None:
+        P = flat_discs(P, R, flat)
+    plane = depth_mode == "plane"
     cams = orbit_cameras(gsr, views, 3.0, image_size, 0.6911112070083618)
     bg = np.zeros(3, np.float32)
     mverts, mfaces, _, info = gsr.tsdf.fuse_views(lambda c: gsr.render_view(P, c, bg), cams, resolution=resolution, centre=(0.0, 0.0, 0.0), half_side=half,
-                                                  depth_mode=depth_mode)
+                                                  depth_mode="expected" if plane else depth_mode, plane_depth=plane, params=P if plane else None)
     torch.cuda.synchronize()
     if info["triangles"] < 1:
         raise SystemExit("--demo torus: the extraction gave no triangle (more --views or a lower --resolution)")
     h = info["voxel_size"]
     m = evaluate_mesh(gsr, mverts, mfaces, verts, faces, samples=200_000, seed=seed + 1, thresholds=(h, 2 * h, 4 * h), log=log)
     m.update(demo="torus", depth_mode=depth_mode, resolution=info["resolution"], views=views, voxel_size=h, triangles=info["triangles"], vertices=info["vertices"],
-             gaussians=int(start.shape[0]), image_size=image_size, accuracy_voxels=m["accuracy"] / h, completeness_voxels=m["completeness"] / h)
+             gaussians=int(start.shape[0]), image_size=image_size, flat=flat, accuracy_voxels=m["accuracy"] / h, completeness_voxels=m["completeness"] / h)
     log(f"demo torus ({depth_mode} depth): {m['gaussians']} Gaussians, {views} views of {image_size}^2 into {m['resolution']}^3 voxels of {h:.5f}: accuracy "
         f"{m['accuracy_voxels']:.3f} voxels, completeness {m['completeness_voxels']:.3f} voxels, {m['triangles']} triangles")
     return m
@@ -116,15 +139,21 @@ def main():
     ap.add_argument("--views", type=int, default=32, metavar="V", help="--demo: orbit views")
     ap.add_argument("--demo-points", type=int, default=100_000, metavar="N", help="--demo: Gaussians on the torus")
     ap.add_argument("--demo-image", type=int, default=256, metavar="PX", help="--demo: image side")
-    ap.add_argument("--depth-mode", choices=["expected", "median"], default="expected", help="--demo: the depth the volume is fused from")
+    ap.add_argument("--depth-mode", choices=["expected", "median", "plane"], default="expected", help="--demo: the depth the volume is fused "
+                    "from (plane: the ray-plane intersection depth under the expected blend, plane_depth.py)")
+    ap.add_argument("--demo-flat", type=float, default=None, metavar="RATIO", help="--demo: turn the Gaussians into discs on the torus: normal = "
+                    "the torus's analytic normal, in-plane scales = the kNN scale, thickness = RATIO times it.  Without it the demo's "
+                    "isotropic Gaussians all fall back to their centre depth and --depth-mode plane measures nothing")
     args = ap.parse_args()
     if args.demo is None and (args.mesh is None or args.gt is None):
         ap.error("--mesh and --gt are required (or --demo torus)")
     if args.demo is not None and not (2 <= args.resolution <= 2048 and args.views >= 1 and args.demo_points >= 4 and args.demo_image >= 8):
         ap.error("--demo: --resolution must be in 2 .. 2048, --views >= 1, --demo-points >= 4, --demo-image >= 8")
+    if args.demo_flat is not None and not 0.0 < args.demo_flat <= 1.0:
+        ap.error("--demo-flat must lie in (0, 1]")
     gsr = importlib.import_module("3dgs-native_amd")
     if args.demo:
-        m = demo_torus(gsr, args.resolution, args.views, args.demo_points, args.demo_image, seed=args.seed, depth_mode=args.depth_mode)
+        m = demo_torus(gsr, args.resolution, args.views, args.demo_points, args.demo_image, seed=args.seed, depth_mode=args.depth_mode, flat=args.demo_flat)
     else:
         try:
             verts, faces, _ = gsr.point_cloud.load_mesh_ply(args.mesh)

@@ -52,6 +52,12 @@ to the target's mask and to the pixels that have a median; its gradient reaches 
 the backward.  The summary then has train_median_depth_l1_mean beside train_depth_l1_mean.  --mesh-depth median makes --mesh-out fuse
 the median depth.  Both default to "expected": today's behaviour.
 
+Plane depth (include/gsr_plane_depth.h, plane_depth.py): --depth-render plane takes --lambda-depth's L1 on the blended ray-plane
+intersection inverse depth -- each flat Gaussian contributes the depth at which the pixel's ray meets its plane, not its centre's -- and,
+with --lambda-normal-consistency, takes that term's depth normals from it too; the gradient reaches positions, rotations, shapes and
+opacities through a stage of the backward.  The summary then has train_plane_depth_l1_mean.  --mesh-depth plane makes --mesh-out fuse
+the plane depth.
+
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
@@ -300,13 +306,14 @@ def perturb_depth_targets(depth_targets, noise, seed):
     return out
 
 
-def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None, median=False):
+def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None, median=False, plane=False):
     """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets.
     Third: with depth targets, {"train_depth_corr_mean": the mean Pearson correlation rho of the rendered inverse depth with the
     targets as given, "train_depth_fit": each view's (s, b) of render ~ s target + b (include/gsr_depth_corr.h)}, and with
     clean_depth_targets (--depth-noise) "train_depth_l1_clean_mean", the first score against the unperturbed targets; with `median`
-    (--depth-render median) "train_median_depth_l1_mean", the first score of the median inverse depth over the pixels that have one."""
-    dl, al, dc, dm = [], [], [], []
+    (--depth-render median) "train_median_depth_l1_mean", the first score of the median inverse depth over the pixels that have one;
+    with `plane` (--depth-render plane) "train_plane_depth_l1_mean", the first score of the plane-depth image."""
+    dl, al, dc, dm, dp = [], [], [], [], []
     fits = torch.zeros((len(cams), 4), device=P["positions"].device) if depth_targets is not None else None
     for k, c in enumerate(cams):
         _, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
@@ -318,6 +325,9 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_t
                 med, contrib = gsr.median_depth.render_median_depth(buf, c["height"], c["width"])
                 mask = ((t > 0) & (contrib > 0).reshape(t.shape)).float()
                 dm.append(float(gsr.loss.depth_loss_and_gradients(med.reshape(t.shape), t, mask, want_grad=False)[0].item()) / t.numel())
+            if plane:
+                pd = gsr.plane_depth.render_view_plane_depth(P, c, buf)[0]
+                dp.append(float(gsr.loss.depth_loss_and_gradients(pd.reshape(t.shape), t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
             if clean_depth_targets is not None:
                 t = clean_depth_targets[k]
                 dc.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
@@ -332,6 +342,8 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_t
             extra["train_depth_l1_clean_mean"] = float(np.mean(dc))
         if dm:
             extra["train_median_depth_l1_mean"] = float(np.mean(dm))
+        if dp:
+            extra["train_plane_depth_l1_mean"] = float(np.mean(dp))
     return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None), extra
 
 
@@ -413,7 +425,8 @@ def finish(run, wall):
         summary["exposure_applied"] = {"train_views": True, "train_eval_scales": True, "holdout_views": False, "holdout_eval_scales": False}
         summary["exposure_final"] = expo.state_dict()["E"]
         summary["exposure_steps"] = list(expo.steps)
-    d_l1, a_l1, d_extra = aux_scores(P, cams, V.depth_targets, V.alpha_targets, bg, mode_kw, V.clean_depth_targets, median=args.depth_render == "median")
+    d_l1, a_l1, d_extra = aux_scores(P, cams, V.depth_targets, V.alpha_targets, bg, mode_kw, V.clean_depth_targets, median=args.depth_render == "median",
+                                      plane=args.depth_render == "plane")
     if args.depth_render != "expected":
         summary["depth_render"] = args.depth_render
     if d_l1 is not None:
@@ -521,10 +534,11 @@ def parse_args(argv=None):
                     "own units.  pearson: 1 - the Pearson correlation of the rendered inverse depth with the target over the mask "
                     "(include/gsr_depth_corr.h), for relative targets: inverse depth known only up to an unknown scale a > 0 and shift b "
                     "per image (t -> a t + b), as monocular depth networks give it.  Needs --lambda-depth > 0; not divided by W H")
-    ap.add_argument("--depth-render", default="expected", choices=["expected", "median"], help="the rendered inverse depth --lambda-depth's "
+    ap.add_argument("--depth-render", default="expected", choices=["expected", "median", "plane"], help="the rendered inverse depth --lambda-depth's "
                     "L1 is taken on: the forward's expected inverse depth, or the median inverse depth (include/gsr_median_depth.h: the "
                     "Gaussian at which the transmittance falls through one half), masked to the pixels that have one; its gradient is a "
-                    "stage of the backward.  Needs --depth-loss l1")
+                    "stage of the backward; or the plane depth (include/gsr_plane_depth.h: every flat Gaussian contributes the depth at which the "
+                    "pixel's ray meets its plane), which --lambda-normal-consistency then takes its depth normals from too.  Needs --depth-loss l1")
     ap.add_argument("--depth-noise", type=float, default=0.0, metavar="S", help="make every depth target relative once, at load: "
                     "a_v t + b_v on its masked pixels, a_v = exp(U(-S, S)), b_v = U(0, S) * mean(t over the mask) per view; the summary "
                     "then also scores the depth against the clean targets (train_depth_l1_clean_mean)")
@@ -559,7 +573,7 @@ def parse_args(argv=None):
     ap.add_argument("--mesh-out", default=None, metavar="FILE", help="after the last iteration, fuse depth and colour renders of the training "
                     "views into a TSDF volume and write the extracted triangle mesh (include/gsr_tsdf.h; what examples/extract_mesh.py does). "
                     "Off by default; training itself is unchanged")
-    ap.add_argument("--mesh-depth", default="expected", choices=["expected", "median"], help="the depth --mesh-out fuses: the expected "
+    ap.add_argument("--mesh-depth", default="expected", choices=["expected", "median", "plane"], help="the depth --mesh-out fuses: the expected "
                     "inverse depth over the coverage, or the median depth (include/gsr_median_depth.h)")
     ap.add_argument("--mesh-resolution", type=int, default=256, metavar="R", help="voxels per side of --mesh-out's volume")
     ap.add_argument("--mesh-min-weight", type=float, default=1.0, metavar="K", help="--mesh-out keeps cells whose corners all have weight K")
@@ -671,6 +685,7 @@ def check_args(args):
         (args.lambda_normal > 0.0 and args.dataset and not args.normal_dir, "--lambda-normal with --dataset needs --normal-dir (normal targets)"),
         (args.depth_loss == "pearson" and not args.lambda_depth > 0.0, "--depth-loss pearson needs --lambda-depth > 0 (its weight)"),
         (args.depth_render == "median" and args.depth_loss != "l1", "--depth-render median needs --depth-loss l1"),
+        (args.depth_render == "plane" and args.depth_loss != "l1", "--depth-render plane needs --depth-loss l1"),
         (not (args.depth_noise >= 0.0 and finite(args.depth_noise)), "--depth-noise must be >= 0 and finite"),
         (args.depth_noise > 0.0 and args.dataset and not args.depth_dir,
          "--depth-noise with --dataset needs --depth-dir (there is no depth target to perturb)"),
@@ -917,6 +932,10 @@ def train_view(run, it, v, alone, capacity=None):
         mask = V.depth_masks[v] * (contrib > 0).reshape(t.shape)         # the target's mask and "this pixel has a median"
         kw["dL_dmedian_depth"] = gsr.loss.depth_loss_and_gradients(med.reshape(t.shape), t, mask, args.lambda_depth)[1]
         kw["median_contributor"] = contrib
+    elif args.lambda_depth > 0.0 and args.depth_render == "plane":      # the same L1 on the plane-depth image; its gradient is a stage of the backward
+        plane_img, plane_s, plane_n = gsr.plane_depth.render_view_plane_depth(P, c, buf)
+        g_plane = gsr.loss.depth_loss_and_gradients(plane_img.reshape(V.depth_targets[v].shape), V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
+        kw.update(dL_dplane_depth=g_plane.reshape(c["height"], c["width"]), plane_slopes=plane_s, plane_depth_image=plane_img, gaussian_normals=plane_n)
     elif args.lambda_depth > 0.0:                                       # (the curve keeps the colour loss: the terms are in the summary)
         kw["dL_ddepth_image"] = gsr.loss.depth_loss_and_gradients(dep, V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
     if args.lambda_alpha > 0.0:
@@ -936,11 +955,19 @@ def train_view(run, it, v, alone, capacity=None):
         # the Gaussians' own normals against the normals of the rendered depth, the gradient on both sides: the depth side's two
         # images are ADDED to the terms' above, the normal image's gradient is a stage of the backward (like the distortion's)
         H, W = c["height"], c["width"]
-        gn = gsr.normal_render.gaussian_normals(P["scales"], P["rotations"], P["positions"], c)
+        if args.depth_render == "plane" and "plane_depth_image" not in kw:     # (no --lambda-depth: the plane depth serves this term alone)
+            plane_img, plane_s, plane_n = gsr.plane_depth.render_view_plane_depth(P, c, buf)
+            kw.update(dL_dplane_depth=torch.zeros_like(plane_img), plane_slopes=plane_s, plane_depth_image=plane_img, gaussian_normals=plane_n)
+        gn = kw["gaussian_normals"] if "gaussian_normals" in kw else gsr.normal_render.gaussian_normals(P["scales"], P["rotations"], P["positions"], c)
         nimg = gsr.normal_render.render_normals(gn, buf, H, W)
-        _, gN, gD, gA = gsr.loss.normal_consistency_loss_and_gradients(nimg, dep.reshape(H, W), buf["final_Ts"].reshape(H, W), c, None,
+        on_plane = "plane_depth_image" in kw                            # --depth-render plane: the depth normals come from the plane depth
+        _, gN, gD, gA = gsr.loss.normal_consistency_loss_and_gradients(nimg, (kw["plane_depth_image"] if on_plane else dep).reshape(H, W),
+                                                                       buf["final_Ts"].reshape(H, W), c, None,
                                                                        args.lambda_normal_consistency, args.normal_alpha_min)
-        kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in kw else kw["dL_ddepth_image"].reshape(gD.shape) + gD
+        if on_plane:                                                    # ... and their depth-side gradient goes back to it
+            kw["dL_dplane_depth"] = kw["dL_dplane_depth"] + gD.reshape(H, W)
+        else:
+            kw["dL_ddepth_image"] = gD if "dL_ddepth_image" not in kw else kw["dL_ddepth_image"].reshape(gD.shape) + gD
         kw["dL_dalpha_image"] = gA if "dL_dalpha_image" not in kw else kw["dL_dalpha_image"].reshape(gA.shape) + gA
         kw.update(dL_dnormal_image=gN, gaussian_normals=gn, normal_image=nimg)
     if expo is not None:                                                # dL/d(corrected) -> dL/d(render) in place, and this view's dL/dE
