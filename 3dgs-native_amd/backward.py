@@ -93,14 +93,17 @@ belongs to this stage; with `dL_dnormal_image` and `normal_image` as well it ser
 composes with camera_grad (the screen-space columns only), the antialiased mode, filter_3d, capacity frames and
 sh_gradient="factored"; `dL_dmean2D_abs` stays the colour, depth and alpha terms' alone.  Without the three keywords the call is
 exactly the one above.
+
+The four stages between the two halves are described once each, in the order they run, in the table STAGES below.
 """
 import ctypes as C
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
 import torch
 
-from . import _host, _lib
+from . import _frame, _host, _lib
 from . import dist as _dist
 from . import distortion as _distortion
 from . import filter3d as _filter3d
@@ -235,61 +238,124 @@ def _outputs(L, dev, N, need, sh_gradient, cleared):
                            dL_dcolor=acc[:, 0:3], dL_dmean2D=acc[:, 3:6], dL_dconic=acc[:, 6:10])
 
 
-def _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream):
-    """The depth-distortion term's screen-space gradient (include/gsr_distortion.h), added into the accumulator records the blend
-    half has just filled.  The frame is read from the records that half blended with: the forward's own, or the re-packed ones at
-    the head of the workspace (which carry 1 / depth: the caller passed the forward's depths).  On that second path the moments
-    may have been formed from another reciprocal of the same depths (distortion.inv_depth_of divides in torch, the re-pack on the
-    device): the two may differ in the last bit, so m - mu is then taken against a mean one ulp of m away from the forward's -- an
-    error of the size of mu's own rounding, inside the bounds the re-packed case is tested at."""
-    D = int(point_list.numel())
-    if D == 0 or N == 0:
-        return
-    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
-    frame = _distortion.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), rec[:, 9], st.masks)
-    _lib.check(L.gsr_distortion_backward(C.byref(frame), _host.ptr(g_dist), _host.ptr(moments), out.acc.data_ptr(), stream))
+def _normals_to_rotations(L, N, normals, scales, rot, means, cam, dnormals, out, dev, stream):
+    """dL/d(normals) on to the quaternions (added): from the caller's scales (raw under filter_3d), rotations and means."""
+    _lib.check(L.gsr_gaussian_normals_backward(N, _host.ptr(scales), _host.ptr(rot), _host.ptr(means), cam[0], _host.ptr(dnormals),
+                                               _host.ptr(out.dL_drot), stream))
 
 
-def _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, normals, normal_image, dnormals, stream):
-    """The normal image's screen-space gradient (include/gsr_normal_render.h), added into the accumulator records the blend half has
-    just filled, and dL/d(normals) into `dnormals`.  The frame is read from the records that half blended with, as in
-    _distortion_stage."""
-    D = int(point_list.numel())
+def _plane_moments_to_parameters(L, N, normals, scales, rot, means, cam, dmoments, out, dev, stream):
+    """The plane stage's moments on to the means (added) and, through the normals, to the quaternions.  `cam`: the view matrix's
+    floats, tan_fovx, tan_fovy, W, H."""
+    dplane_n = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    _lib.check(L.gsr_plane_slopes_backward(N, _host.ptr(normals), _host.ptr(scales), _host.ptr(means), *cam, _host.ptr(dmoments),
+                                           _host.ptr(out.dL_dmean3D), _host.ptr(dplane_n), stream))
+    _normals_to_rotations(L, N, normals, scales, rot, means, cam, dplane_n, out, dev, stream)
+
+
+# What _host.to_dev brings to the device for each stage: its keywords' values (in the order its check takes them) as the entry
+# point's arrays after the frame, in the entry point's order.  `normals`: gaussian_normals, converted once for both stages it serves.
+_F32, _I32, _to = torch.float32, torch.int32, _host.to_dev
+
+
+def _distortion_inputs(dev, N, H, W, normals, dL_ddistortion, distortion_moments):
+    return _to(dL_ddistortion, _F32, dev, (H, W)), _to(distortion_moments, _F32, dev, (H, W, 4))
+
+
+def _normal_inputs(dev, N, H, W, normals, dL_dnormal_image, gaussian_normals, normal_image):
+    return normals, _to(dL_dnormal_image, _F32, dev, (H, W, 3)), _to(normal_image, _F32, dev, (H, W, 3))
+
+
+def _plane_inputs(dev, N, H, W, normals, dL_dplane_depth, plane_slopes, plane_depth_image, gaussian_normals):
+    _plane_depth.check_slopes(plane_slopes, N)
+    return _to(plane_slopes, _F32, dev, (N, 2)), _to(dL_dplane_depth, _F32, dev, (H, W)), _to(plane_depth_image, _F32, dev, (H, W))
+
+
+def _median_inputs(dev, N, H, W, normals, dL_dmedian_depth, median_contributor):
+    return _to(dL_dmedian_depth, _F32, dev, (H, W)), _to(median_contributor, _I32, dev, (H, W))
+
+
+# A stage between the two halves, described once:
+#   check, keywords   the all-or-none check of its keyword group, and the group in the order the check takes it
+#   inputs            the function above: name, dtype and shape of every array it hands to the entry point
+#   depths_reason     why a frame that does not carry the forward's records needs geom_buffer["depths"] for it (None: it does not; the
+#                     entry point then takes the frame without 1 / depth, a GsrFeaturesFrame)
+#   entry, result     the entry point -- (frame, *inputs, accumulator records[, result], stream) -- and the key of its (N, 3)
+#                     per-Gaussian result, or None
+#   param_grad, follow_up   after the per-Gaussian half, under this keyword
+Stage = namedtuple("Stage", "name check keywords inputs depths_reason entry result param_grad follow_up")
+
+# ... listed in the order they run
+STAGES = (
+    Stage("distortion", _distortion.check_gradient_pair, ("dL_ddistortion", "distortion_moments"), _distortion_inputs,
+          "the distortion is a function of the Gaussians' inverse depths", "gsr_distortion_backward", None, None, None),
+    Stage("normal", _normal_render.check_gradient_triple, ("dL_dnormal_image", "gaussian_normals", "normal_image"), _normal_inputs,
+          None, "gsr_normal_render_backward", "dL_dgaussian_normals", "normal_param_grad", _normals_to_rotations),
+    Stage("plane", _plane_depth.check_gradient_triple, ("dL_dplane_depth", "plane_slopes", "plane_depth_image", "gaussian_normals"), _plane_inputs,
+          "the plane depth is a function of the Gaussians' inverse depths", "gsr_plane_depth_backward", "dL_dplane_moments", "plane_param_grad",
+          _plane_moments_to_parameters),
+    Stage("median", _median_depth.check_gradient_pair, ("dL_dmedian_depth", "median_contributor"), _median_inputs,
+          "the per-Gaussian half carries dL/d(1/depth) on through the re-packed records", "gsr_median_depth_backward", None, None, None),
+)
+# the follow-ups add to dL_drot in this order, whatever the table's: the plane stage's, then the normal image's
+FOLLOW_UP_ORDER = ("plane", "normal")
+
+
+def _stages_present(dL_ddistortion, distortion_moments, dL_dnormal_image, gaussian_normals, normal_image, dL_dplane_depth, plane_slopes,
+                    plane_depth_image, dL_dmedian_depth, median_contributor):
+    """The stages a call's keywords ask for, in STAGES' order, each with its keywords' values: ((stage, values), ...).  The plain
+    call: four checks and the empty tuple.  A group given in part is refused."""
+    distortion, normal, plane, median = STAGES
+    has_distortion = distortion.check(dL_ddistortion, distortion_moments)
+    has_plane = plane.check(dL_dplane_depth, plane_slopes, plane_depth_image, gaussian_normals)
+    # gaussian_normals alone with the three plane keywords belongs to the plane stage: the normal stage is then absent, not given in part
+    has_normal = (not (has_plane and dL_dnormal_image is None and normal_image is None)
+                  and normal.check(dL_dnormal_image, gaussian_normals, normal_image))
+    has_median = median.check(dL_dmedian_depth, median_contributor)
+    if not (has_distortion or has_normal or has_plane or has_median):
+        return ()
+    on = []
+    if has_distortion:
+        on.append((distortion, (dL_ddistortion, distortion_moments)))
+    if has_normal:
+        on.append((normal, (dL_dnormal_image, gaussian_normals, normal_image)))
+    if has_plane:
+        on.append((plane, (dL_dplane_depth, plane_slopes, plane_depth_image, gaussian_normals)))
+    if has_median:
+        on.append((median, (dL_dmedian_depth, median_contributor)))
+    return tuple(on)
+
+
+def _needs_depths(stage):
+    return ValueError(f"backward({stage.keywords[0]}=...) on a frame that does not carry the forward's records needs "
+                      f"geom_buffer['depths']: {stage.depths_reason}")
+
+
+def _run_stages(L, stages, inputs, results, st, out, N, point_list, ranges, n_contrib, stream):
+    """The stages' screen-space gradients (include/gsr_distortion.h, gsr_normal_render.h, gsr_plane_depth.h, gsr_median_depth.h), added
+    into the accumulator records the blend half has just filled, and their per-Gaussian `results`.  The frame is read from the
+    records that half blended with: the forward's own, or the re-packed ones at the head of the workspace (which carry 1 / depth:
+    the caller passed the forward's depths).  On that second path the distortion's moments may have been formed from another
+    reciprocal of the same depths (_frame.inv_depth_of divides in torch, the re-pack on the device): the two may differ in the last
+    bit, so m - mu is then taken against a mean one ulp of m away from the forward's -- an error of the size of mu's own rounding,
+    inside the bounds the re-packed case is tested at.  (The median stage's kernel reads the frame's lists and ranges only.)"""
     if N == 0:
         return
-    if D == 0:
-        dnormals.zero_()
+    if point_list.numel() == 0:
+        for t in results.values():
+            t.zero_()
         return
     rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
-    frame = _normal_render.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), st.masks)
-    _lib.check(L.gsr_normal_render_backward(C.byref(frame), _host.ptr(normals), _host.ptr(g_normal), _host.ptr(normal_image), out.acc.data_ptr(),
-                                            _host.ptr(dnormals), stream))
-
-
-def _plane_stage(L, st, out, N, point_list, ranges, n_contrib, g_plane, slopes, plane_image, dmoments, stream):
-    """The plane-depth image's screen-space gradient (include/gsr_plane_depth.h), added into the accumulator records the blend half
-    has just filled, and the three moments per Gaussian into `dmoments`.  The frame is the one _distortion_stage reads."""
-    D = int(point_list.numel())
-    if N == 0:
-        return
-    if D == 0:
-        dmoments.zero_()
-        return
-    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
-    frame = _distortion.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), rec[:, 9], st.masks)
-    _lib.check(L.gsr_plane_depth_backward(C.byref(frame), _host.ptr(slopes), _host.ptr(g_plane), _host.ptr(plane_image), out.acc.data_ptr(),
-                                          _host.ptr(dmoments), stream))
-
-
-def _median_stage(L, st, out, N, point_list, ranges, n_contrib, g_med, contrib, stream):
-    """The median inverse depth's gradient (include/gsr_median_depth.h): g[p] added into column 11 of the accumulator record of the
-    Gaussian each pixel chose.  The frame is the one _distortion_stage reads; the kernel reads its lists and ranges only."""
-    D = int(point_list.numel())
-    if D == 0 or N == 0:
-        return
-    rec = st.records if st.records is not None else out.ws[:64 * N].view(torch.float32).view(N, 16)
-    frame = _distortion.frame_struct((N, D, rec[:, 0:2], rec[:, 2:6], point_list, ranges, n_contrib), rec[:, 9], st.masks)
-    _lib.check(L.gsr_median_depth_backward(C.byref(frame), _host.ptr(g_med), _host.ptr(contrib), out.acc.data_ptr(), stream))
+    frame = _frame.Frame.from_records(rec, point_list, ranges, n_contrib, st.masks)
+    structs = {}                # at most two per call: with 1 / depth and without
+    acc = out.acc.data_ptr()
+    for (s, _), arrays in zip(stages, inputs):
+        reads_depth = s.depths_reason is not None
+        fs = structs.get(reads_depth)
+        if fs is None:
+            fs = structs[reads_depth] = C.byref(frame.struct(inv_depth=reads_depth))
+        tail = (acc, stream) if s.result is None else (acc, _host.ptr(results[s.result]), stream)
+        _lib.check(getattr(L, s.entry)(fs, *[_host.ptr(t) for t in arrays], *tail))
 
 
 def _launch(L, scene, cam, geom, binning, img, pg, out, flags, aa_scale, aux, on_payload, camera_grad, stream, distortion=None):
@@ -364,13 +430,8 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     # substring.  Any other name raises the TypeError an unknown keyword always gets.
     dL_dnormal_image, gaussian_normals, normal_image, normal_param_grad = _normal_render.stage_keywords(rendered_stage)
     antialiased = _lib.check_rasterize_mode(rasterize_mode)
-    distortion = _distortion.check_gradient_pair(dL_ddistortion, distortion_moments)
-    plane = _plane_depth.check_gradient_triple(dL_dplane_depth, plane_slopes, plane_depth_image, gaussian_normals)
-    if plane and dL_dnormal_image is None and normal_image is None:
-        normal = False      # gaussian_normals is the plane stage's alone
-    else:
-        normal = _normal_render.check_gradient_triple(dL_dnormal_image, gaussian_normals, normal_image)
-    median = _median_depth.check_gradient_pair(dL_dmedian_depth, median_contributor)
+    stages = _stages_present(dL_ddistortion, distortion_moments, dL_dnormal_image, gaussian_normals, normal_image, dL_dplane_depth, plane_slopes,
+                             plane_depth_image, dL_dmedian_depth, median_contributor)
     frame_co = conic_opacity if conic_opacity is not None or geom_buffer is None else geom_buffer.get("conic_opacity")
     # (before anything touches the GPU: a frame rendered without the filter or with another one, raw tensors written since the render)
     if filter_3d is not None:
@@ -385,12 +446,13 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     aa_tag = _aa_scale_of(frame_co, opacity, antialiased)
     if sh_gradient not in ("dense", "factored", "both"):
         raise ValueError("sh_gradient must be 'dense', 'factored' or 'both'")
-    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or distortion or normal or median or plane
+    aux = dL_ddepth_image is not None or dL_dalpha_image is not None or stages != ()
     if dL_dpixels is None and not aux:
         raise ValueError("backward() needs dL_dpixels, dL_ddepth_image or dL_dalpha_image (or dL_ddistortion with distortion_moments, "
                          "dL_dnormal_image with gaussian_normals and normal_image, or dL_dmedian_depth with median_contributor, or "
                          "dL_dplane_depth with plane_slopes, plane_depth_image and gaussian_normals)")
-    view16 = _normal_render.view_floats(viewmatrix, "backward(dL_dnormal_image=...)") if normal or plane else None
+    follow_ups = stages and [s for name in FOLLOW_UP_ORDER for s, _ in stages if s.name == name]      # (the plain call: () and nothing walked)
+    view16 = _normal_render.view_floats(viewmatrix, "backward(dL_dnormal_image=...)") if follow_ups else None
     _forward._backward_seen = True     # from now on this process's forwards pre-clear the backward workspace (forward.PRECLEAR_BACKWARD)
     L = _lib.lib()
     dev = _host.device_of(means3D, dL_dpixels, shs, radii)
@@ -400,15 +462,18 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
     means = _host.to_dev(means3D, f32, dev, (-1, 3))
     N = means.shape[0]
     dpix, g_depth, g_alpha = opt(dL_dpixels, (H, W, 3)), opt(dL_ddepth_image, (H, W)), opt(dL_dalpha_image, (H, W))
-    g_dist, moments = opt(dL_ddistortion, (H, W)), opt(distortion_moments, (H, W, 4))
-    g_normal, gn, nimg = opt(dL_dnormal_image, (H, W, 3)), opt(gaussian_normals, (N, 3)), opt(normal_image, (H, W, 3))
-    g_med = opt(dL_dmedian_depth, (H, W))
-    g_plane, pd_img = opt(dL_dplane_depth, (H, W)), opt(plane_depth_image, (H, W))
-    if plane:
-        _plane_depth.check_slopes(plane_slopes, N)
-    med_contrib = _host.to_dev(median_contributor, torch.int32, dev, (H, W)) if median else None
-    if (distortion or normal or median or plane) and dpix is None and g_depth is None and g_alpha is None:
-        g_alpha = torch.zeros((H, W), dtype=f32, device=dev)   # the blend half wants one image gradient: a zero one clears and adds nothing
+    stage_in, stage_depths = None, None
+    if stages:
+        gn = opt(gaussian_normals, (N, 3))
+        stage_in = [s.inputs(dev, N, H, W, gn, *values) for s, values in stages]
+        for s, _ in stages:
+            if s.depths_reason is not None:
+                stage_depths = s        # the first stage that needs 1 / depth on a re-packed frame: the one a refusal names
+                break
+        param_grad = {"normal_param_grad": normal_param_grad, "plane_param_grad": plane_param_grad}
+        follow_ups = [s for s in follow_ups if param_grad[s.param_grad] and N > 0]
+        if dpix is None and g_depth is None and g_alpha is None:
+            g_alpha = torch.zeros((H, W), dtype=f32, device=dev)   # the blend half wants one image gradient: a zero one clears and adds nothing
     sh = _host.to_dev(shs, f32, dev, (-1, 3))
     sc = _host.to_dev(scales, f32, dev, (-1, 3))
     rot = _host.to_dev(rotations, f32, dev, (-1, 4))
@@ -434,18 +499,11 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         m2d = _host.to_dev(means2D, f32, dev, (-1, 2))
         con = _host.to_dev(conic_opacity, f32, dev, (-1, 4))
         col = _host.to_dev(rgb, f32, dev, (-1, 3))
-        if (g_depth is not None or distortion or median or plane) and geom_buffer is not None:
+        if (g_depth is not None or stage_depths is not None) and geom_buffer is not None:
             # the re-packed records carry 1/depth only from the forward's depths (gsr_aux_grads.h: without them, GSR_E_NULL)
             depths = opt(geom_buffer.get("depths"), (-1,))
-        if distortion and depths is None:
-            raise ValueError("backward(dL_ddistortion=...) on a frame that does not carry the forward's records needs "
-                             "geom_buffer['depths']: the distortion is a function of the Gaussians' inverse depths")
-        if plane and depths is None:
-            raise ValueError("backward(dL_dplane_depth=...) on a frame that does not carry the forward's records needs "
-                             "geom_buffer['depths']: the plane depth is a function of the Gaussians' inverse depths")
-        if median and depths is None:
-            raise ValueError("backward(dL_dmedian_depth=...) on a frame that does not carry the forward's records needs "
-                             "geom_buffer['depths']: the per-Gaussian half carries dL/d(1/depth) on through the re-packed records")
+        if stage_depths is not None and depths is None:
+            raise _needs_depths(stage_depths)
     cl = _host.to_dev(clamped, f32, dev, (-1, 3))
     c3 = None if st.recompute else _host.to_dev(cov3Ds, f32, dev, (-1, 6))
     ranges = _host.to_dev(given["ranges"], i32, dev, (-1, 2))
@@ -469,47 +527,27 @@ def backward(background, means3D, dL_dpixels, opacity=None, shs=None, scales=Non
         binning = _lib.GsrBinning(st.D_bin, _host.ptr(point_list), _host.ptr(ranges), _host.ptr(st.masks), _host.ptr(st.order),
                                   _host.ptr(out.ws) if cleared else None, 1 if cleared else 0)
         stream = _host.raw_stream(dev)
-        stage = dnormals = dmoments = None
-        if normal:
-            dnormals = torch.empty((N, 3), dtype=f32, device=dev)
-        if plane:
-            dmoments = torch.empty((N, 3), dtype=f32, device=dev)
-        if distortion or normal or median or plane:
-            def stage():                    # in this order when several are present: distortion, normals, plane depth, median depth
-                if distortion:
-                    _distortion_stage(L, st, out, N, point_list, ranges, n_contrib, g_dist, moments, stream)
-                if normal:
-                    _normal_stage(L, st, out, N, point_list, ranges, n_contrib, g_normal, gn, nimg, dnormals, stream)
-                if plane:
-                    _plane_stage(L, st, out, N, point_list, ranges, n_contrib, g_plane, plane_slopes, pd_img, dmoments, stream)
-                if median:
-                    _median_stage(L, st, out, N, point_list, ranges, n_contrib, g_med, med_contrib, stream)
+        run_stages = stage_out = None
+        if stages:
+            # dL_dgaussian_normals: dL/d(gaussian_normals), what gsr_gaussian_normals_backward carries on to dL_drot; dL_dplane_moments:
+            # what gsr_plane_slopes_backward carries on to dL_dmean3D and dL_drot
+            stage_out = {s.result: torch.empty((N, 3), dtype=f32, device=dev) for s, _ in stages if s.result is not None}
+
+            def run_stages():
+                _run_stages(L, stages, stage_in, stage_out, st, out, N, point_list, ranges, n_contrib, stream)
         dcam = _launch(L, scene, cam, geom, binning, img, pg, out, _lib.BWD_ABSGRAD if absgrad else 0, aa_scale, aux, on_payload,
-                       camera_grad, stream, stage)
-        nsc = sc
-        if (normal or plane) and filt is not None:
-            nsc = _host.to_dev(raw_scales, f32, dev, (-1, 3))
-        if plane and plane_param_grad and N > 0:
-            # the moments on to the means (added) and, through the normals, to the quaternions: from the caller's scales (raw under
-            # filter_3d), rotations and means
-            dplane_n = torch.empty((N, 3), dtype=f32, device=dev)
-            _lib.check(L.gsr_plane_slopes_backward(N, _host.ptr(gn), _host.ptr(nsc), _host.ptr(means), view16[0], float(tan_fovx), float(tan_fovy),
-                                                   W, H, _host.ptr(dmoments), _host.ptr(out.dL_dmean3D), _host.ptr(dplane_n), stream))
-            _lib.check(L.gsr_gaussian_normals_backward(N, _host.ptr(nsc), _host.ptr(rot), _host.ptr(means), view16[0], _host.ptr(dplane_n),
-                                                       _host.ptr(out.dL_drot), stream))
-        if normal and normal_param_grad and N > 0:
-            # the normals' own gradient, on to the quaternions: from the caller's scales (raw under filter_3d), rotations and means
-            _lib.check(L.gsr_gaussian_normals_backward(N, _host.ptr(nsc), _host.ptr(rot), _host.ptr(means), view16[0], _host.ptr(dnormals),
-                                                       _host.ptr(out.dL_drot), stream))
+                       camera_grad, stream, run_stages)
+        if follow_ups:
+            nsc = sc if filt is None else _host.to_dev(raw_scales, f32, dev, (-1, 3))      # the raw scales under filter_3d
+            view_cam = (view16[0], float(tan_fovx), float(tan_fovy), W, H)
+            for s in follow_ups:
+                s.follow_up(L, N, gn, nsc, rot, means, view_cam, stage_out[s.result], out, dev, stream)
         if filt is not None:
             _filter3d.filter_3d_backward(*_filter3d.raw_inputs(filt, raw_scales, raw_opacity, dev, N), filter_3d, out.dL_dscale, out.dL_dopacity)
     res = _result(out, N, dev, dcam, aux, absgrad)
-    if normal:
-        _host.written_in_place(dnormals)
-        res["dL_dgaussian_normals"] = dnormals      # (N, 3): dL/d(gaussian_normals), what gsr_gaussian_normals_backward carried on to dL_drot
-    if plane:
-        _host.written_in_place(dmoments)
-        res["dL_dplane_moments"] = dmoments         # (N, 3): what gsr_plane_slopes_backward carried on to dL_dmean3D and dL_drot
+    if stage_out:
+        _host.written_in_place(*stage_out.values())
+        res.update(stage_out)
     return res
 
 
@@ -521,14 +559,10 @@ def backward_view(params, camera, background, buffers, dL_dpixels, **kw):
     written since the render is re-packed from buffers["depths"], handed on here as geom_buffer), dL_dnormal_image with
     gaussian_normals and normal_image, normal_param_grad, dL_dmedian_depth with median_contributor (re-packed like the distortion term),
     dL_dplane_depth with plane_slopes, plane_depth_image and gaussian_normals (re-packed likewise), plane_param_grad."""
-    plane = _plane_depth.check_gradient_triple(kw.get("dL_dplane_depth"), kw.get("plane_slopes"), kw.get("plane_depth_image"),
-                                               kw.get("gaussian_normals"))
-    if not (plane and kw.get("dL_dnormal_image") is None and kw.get("normal_image") is None):
-        _normal_render.check_gradient_triple(kw.get("dL_dnormal_image"), kw.get("gaussian_normals"), kw.get("normal_image"))
-    needs_depths = plane
-    needs_depths |= _distortion.check_gradient_pair(kw.get("dL_ddistortion"), kw.get("distortion_moments"))
-    needs_depths |= _median_depth.check_gradient_pair(kw.get("dL_dmedian_depth"), kw.get("median_contributor"))
-    if needs_depths and "geom_buffer" not in kw and "depths" in buffers:
+    get = kw.get
+    stages = _stages_present(get("dL_ddistortion"), get("distortion_moments"), get("dL_dnormal_image"), get("gaussian_normals"), get("normal_image"),
+                             get("dL_dplane_depth"), get("plane_slopes"), get("plane_depth_image"), get("dL_dmedian_depth"), get("median_contributor"))
+    if any(s.depths_reason is not None for s, _ in stages) and "geom_buffer" not in kw and "depths" in buffers:
         kw["geom_buffer"] = {"depths": buffers["depths"]}
     return backward(background=background, means3D=params["positions"], dL_dpixels=dL_dpixels, opacity=params["opacities"],
                     shs=params["shs"], scales=params["scales"], rotations=params["rotations"], viewmatrix=camera["world_to_camera"],

@@ -13,13 +13,9 @@ so its gradient is a scatter of g to that Gaussian, a stage of backward() betwee
 (backward.py).  A capacity-mode frame is to be used only once rendered_count(buffers) has said that it did not overflow.  Everything
 is enqueued on the current stream; nothing is read back.
 """
-import ctypes as C
-
 import torch
 
-from . import _args, _host, _lib
-from . import distortion as _distortion
-from . import features as _features
+from . import _frame, _host, _lib
 
 
 def render_median_depth(buffers, image_height, image_width, out=None, use_block_masks=True):
@@ -27,30 +23,11 @@ def render_median_depth(buffers, image_height, image_width, out=None, use_block_
     position in the tile's list (n_contrib's convention; 0 and a value of 0 where no entry was applied).  `out`: a caller-owned pair
     to write into (every element is written).  use_block_masks=False walks without the forward's block masks (the same bits either
     way)."""
-    fr = _features._check_frame(buffers, image_height, image_width)
-    H, W = int(image_height), int(image_width)
-    if out is not None:
-        if not (isinstance(out, (tuple, list)) and len(out) == 2):
-            raise ValueError("out must be a (median_inv_depth, median_contrib) pair")
-        _args.check_out(out[0], (H, W), "out[0]")
-        _args.check_out(out[1], (H, W), "out[1]", dtype=torch.int32)
-        med, contrib = out
-    N, D, xy = fr[0], fr[1], fr[2]
-    dev = xy.device
-    if out is None:
-        med = torch.empty((H, W), dtype=torch.float32, device=dev)
-        contrib = torch.empty((H, W), dtype=torch.int32, device=dev)
-    if N == 0:
+    fr = _frame.Frame.from_buffers(buffers, image_height, image_width, use_block_masks, inv_depth=True)
+    med, contrib = fr.outputs(out, [(fr.H, fr.W), (fr.H, fr.W)], pair="(median_inv_depth, median_contrib)", dtypes=(torch.float32, torch.int32))
+    if fr.N == 0:
         return med.zero_(), contrib.zero_()
-    inv_depth = _distortion.inv_depth_of(buffers, N, dev)
-    _args.check_one_device(*fr[2:], med, contrib)
-    masks = _features._masks_of(buffers, D, dev) if use_block_masks else None
-    L = _lib.lib()
-    frame = _distortion.frame_struct(fr, inv_depth, masks)
-    with _host.on_device(dev):
-        _lib.check(L.gsr_median_depth_forward(C.byref(frame), _host.ptr(med), _host.ptr(contrib), _host.raw_stream(dev)))
-    _host.written_in_place(med)
-    _host.written_in_place(contrib)
+    fr.launch("gsr_median_depth_forward", _host.ptr(med), _host.ptr(contrib), written=(med, contrib))
     return med, contrib
 
 

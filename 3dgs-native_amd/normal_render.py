@@ -20,8 +20,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _args, _host, _lib
-from . import features as _features
+from . import _args, _frame, _host, _lib
 
 
 def view_floats(viewmatrix, who):
@@ -102,39 +101,19 @@ def gaussian_normals_backward(dL_dnormals, scales, rotations, means, camera, dL_
     return dL_drot
 
 
-def frame_struct(fr, masks):
-    """GsrFeaturesFrame over the checked frame arrays of features._check_frame."""
-    N, D, xy, co, pl, rg, nc = fr
-    H, W = int(nc.shape[0]), int(nc.shape[1])
-    return _lib.GsrFeaturesFrame(W, H, N, D, xy.data_ptr(), int(xy.stride(0)), co.data_ptr(), int(co.stride(0)), _host.ptr(pl), _host.ptr(rg),
-                                 _host.ptr(nc), _host.ptr(masks))
-
-
 def render_normals(normals, buffers, image_height, image_width, out=None, use_block_masks=True):
     """(H, W, 3) float32: out[y, x] = sum over the pixel's contributing list entries of w_k * normals[i_k], front to back, one fused
     multiply-add per term: bit for bit features.render_features(normals, ...).  No background is added, and the image is not
     normalised (its length is at most the coverage 1 - final_Ts).  `out`: a caller-owned tensor to write into (every element is
     written).  use_block_masks=False walks without the forward's block masks (the same bits either way)."""
-    fr = _features._check_frame(buffers, image_height, image_width)
-    N, D = fr[0], fr[1]
-    H, W = int(image_height), int(image_width)
-    if not (_args.is_dev(normals, torch.float32) and tuple(normals.shape) == (N, 3) and normals.is_contiguous()):
+    fr = _frame.Frame.from_buffers(buffers, image_height, image_width, use_block_masks)
+    if not (_args.is_dev(normals, torch.float32) and tuple(normals.shape) == (fr.N, 3) and normals.is_contiguous()):
         raise ValueError("normals must be a contiguous float32 device tensor of shape (N, 3) with N the frame's number of Gaussians")
-    if out is not None:
-        _args.check_out(out, (H, W, 3), "out")
-    dev = normals.device
-    _args.check_one_device(normals, *fr[2:], out)
-    if out is None:
-        out = torch.empty((H, W, 3), dtype=torch.float32, device=dev)
-    if N == 0:
+    out, = fr.outputs(out, [(fr.H, fr.W, 3)], (normals,))
+    if fr.N == 0:
         return out.zero_()
-    masks = _features._masks_of(buffers, D, dev) if use_block_masks else None
-    L = _lib.lib()
-    n = _host.to_dev(normals, torch.float32, dev)
-    frame = frame_struct(fr, masks)
-    with _host.on_device(dev):
-        _lib.check(L.gsr_normal_render_forward(C.byref(frame), _host.ptr(n), _host.ptr(out), _host.raw_stream(dev)))
-    _host.written_in_place(out)
+    n = _host.to_dev(normals, torch.float32, fr.device)
+    fr.launch("gsr_normal_render_forward", _host.ptr(n), _host.ptr(out), written=(out,))
     return out
 
 

@@ -19,13 +19,9 @@ dict with world_to_camera (4 x 4, row-vector convention), tan_fovx, tan_fovy, wi
 only once rendered_count(buffers) has said that it did not overflow.  Everything is enqueued on the current stream; nothing is read
 back.
 """
-import ctypes as C
-
 import torch
 
-from . import _args, _host, _lib
-from . import distortion as _distortion
-from . import features as _features
+from . import _args, _frame, _host, _lib
 from . import normal_render as _normal_render
 
 
@@ -108,25 +104,12 @@ def render_plane_depth(slopes, buffers, image_height, image_width, out=None, use
     what the forward's depth image is for centre depths.  At slopes 0 it is bit for bit features.render_features(invd[:, None]).  `out`:
     a caller-owned tensor to write into (every element is written).  use_block_masks=False walks without the forward's block masks
     (the same bits either way)."""
-    fr = _features._check_frame(buffers, image_height, image_width)
-    N, D, xy = fr[0], fr[1], fr[2]
-    H, W = int(image_height), int(image_width)
-    check_slopes(slopes, N)
-    if out is not None:
-        _args.check_out(out, (H, W), "out")
-    dev = slopes.device
-    _args.check_one_device(slopes, *fr[2:], out)
-    if out is None:
-        out = torch.empty((H, W), dtype=torch.float32, device=dev)
-    if N == 0:
+    fr = _frame.Frame.from_buffers(buffers, image_height, image_width, use_block_masks, inv_depth=True)
+    check_slopes(slopes, fr.N)
+    out, = fr.outputs(out, [(fr.H, fr.W)], (slopes,))
+    if fr.N == 0:
         return out.zero_()
-    inv_depth = _distortion.inv_depth_of(buffers, N, dev)
-    masks = _features._masks_of(buffers, D, dev) if use_block_masks else None
-    L = _lib.lib()
-    frame = _distortion.frame_struct(fr, inv_depth, masks)
-    with _host.on_device(dev):
-        _lib.check(L.gsr_plane_depth_forward(C.byref(frame), _host.ptr(slopes), _host.ptr(out), _host.raw_stream(dev)))
-    _host.written_in_place(out)
+    fr.launch("gsr_plane_depth_forward", _host.ptr(slopes), _host.ptr(out), written=(out,))
     return out
 
 

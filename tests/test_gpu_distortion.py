@@ -75,7 +75,7 @@ def frame(name):
             assert not over and 0 < D < extra["capacity"]
             nb["point_list"] = nb["point_list"][:D]
         N = sc["means"].shape[0]
-        m32 = parity.to_np(sub("distortion").inv_depth_of(buf, N, image.device)).astype(np.float32)   # what the kernel reads
+        m32 = parity.to_np(sub("_frame").inv_depth_of(buf, N, image.device)).astype(np.float32)   # what the kernel reads
         r = DR.yardstick(nb, W, H, DR.draw_g(H, W), m=m32.astype(np.float64))
         print(f"\n{name}: D {nb['point_list'].shape[0]}, {int(r['mask'].sum())} of {r['mask'].size} pixels masked")
         assert r["mask"].sum() <= FR.MAX_MASKED * r["mask"].size
@@ -135,7 +135,7 @@ def test_forward_is_deterministic_and_writes_every_pixel(name):
     else:
         f = frame(name)
         buf, H, W = f["buf"], f["H"], f["W"]
-        assert feat._masks_of(buf, int(buf["point_list"].shape[0]), buf["ranges"].device) is not None   # the masks are this forward's
+        assert sub("_frame").masks_of(buf, int(buf["point_list"].shape[0]), buf["ranges"].device) is not None   # the masks are this forward's
     a = dist_mod.render_distortion(buf, H, W)
     b = dist_mod.render_distortion(buf, H, W)
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])

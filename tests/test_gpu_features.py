@@ -177,7 +177,7 @@ def test_forward_is_deterministic_and_writes_every_pixel(name):
     else:
         f = frame(name)
         buf, H, W, Fd = f["buf"], f["H"], f["W"], f["Fd"][:, :17].contiguous()
-        assert feat._masks_of(buf, int(buf["point_list"].shape[0]), Fd.device) is not None        # the masks are this forward's
+        assert sub("_frame").masks_of(buf, int(buf["point_list"].shape[0]), Fd.device) is not None        # the masks are this forward's
     a = feat.render_features(Fd, buf, H, W)
     b = feat.render_features(Fd, buf, H, W)
     assert torch.equal(a, b)

@@ -184,7 +184,7 @@ def rendered():
         N = sc["means"].shape[0]
         nb = {k: parity.to_np(buf[k]) for k in ("points_xy_image", "conic_opacity", "point_list", "ranges", "n_contrib")}
         fr = dict(W=W, H=H, N=N, D=int(nb["point_list"].shape[0]), xy=nb["points_xy_image"].reshape(-1, 2).astype(np.float32),
-                  co=nb["conic_opacity"].reshape(-1, 4).astype(np.float32), invd=parity.to_np(sub("distortion").inv_depth_of(buf, N, image.device)).astype(np.float32),
+                  co=nb["conic_opacity"].reshape(-1, 4).astype(np.float32), invd=parity.to_np(sub("_frame").inv_depth_of(buf, N, image.device)).astype(np.float32),
                   point_list=nb["point_list"].reshape(-1), ranges=nb["ranges"].reshape(-1, 2), n_contrib=nb["n_contrib"].reshape(H, W))
         ref = M.median_f64(fr)
         g = M.draw_g(H, W) / (H * W)

@@ -165,7 +165,7 @@ def test_forward_is_features_at_c3_deterministic_and_writes_every_pixel(name):
         f = frame(name)
         buf, H, W, n, dev = f["buf"], f["H"], f["W"], f["n"], f["dev"]
         if "capacity" not in f["extra"]:
-            assert feat._masks_of(buf, int(buf["point_list"].shape[0]), dev) is not None   # the masks are this forward's
+            assert sub("_frame").masks_of(buf, int(buf["point_list"].shape[0]), dev) is not None   # the masks are this forward's
     a = nr.render_normals(n, buf, H, W)
     assert tuple(a.shape) == (H, W, 3) and bool(torch.isfinite(a).all())
     assert torch.equal(a, feat.render_features(n, buf, H, W))          # bit for bit gsr_features_forward at C = 3

@@ -207,7 +207,7 @@ def frame(name):
         sl32, fb = PD.slopes_f32(parity.to_np(n), ps, sc["means"], view, kw["tan_fovx"], kw["tan_fovy"], W, H)
         k = parity.to_np(slopes)
         assert np.array_equal(k != 0, sl32 != 0) or np.abs(k - sl32).max() <= 8 * EPS32 * np.abs(sl32).max()
-        invd = parity.to_np(dist.inv_depth_of(buf, N, dev)).astype(f32)
+        invd = parity.to_np(sub("_frame").inv_depth_of(buf, N, dev)).astype(f32)
         r = PD.yardstick(nb, W, H, invd, k, PD.draw_g(H, W))
         print(f"\n{name}: D {nb['point_list'].shape[0]}, {int(r['mask'].sum())} of {r['mask'].size} pixels masked, plane branch {float((k != 0).any(1).mean()):.2f}, "
               f"clamped pairs {r['clamped']}")
@@ -370,7 +370,7 @@ def test_closed_form_plane_through_the_real_forward():
     off = np.abs(centre[sel] / cover[sel] / want[sel] - 1.0)
     sigma_px = 0.2 / pv[:, 2].mean() / (2.0 * tx / W)
     slope = float(np.abs(parity.to_np(slopes).astype(np.float64)).max())
-    margin = 0.25 * slope * sigma_px / float(parity.to_np(sub("distortion").inv_depth_of(buf, len(pv), dev)).max())
+    margin = 0.25 * slope * sigma_px / float(parity.to_np(sub("_frame").inv_depth_of(buf, len(pv), dev)).max())
     _row(test="closed_form", covered=int(sel.sum()), plane_eps32=float(rel.max() / EPS32), centre_off=float(off.max()), margin=margin)
     assert rel.max() <= 16 * EPS32
     assert off.max() >= margin > 1000 * EPS32
