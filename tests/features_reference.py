@@ -10,7 +10,7 @@ or a float64 n_contrib other than the forward's).  From those weights
     dL_dF[i][c] = sum_p w_i(p) G[p][c]            (float64; G is zeroed at the masked pixels, so both sides lose them)
     mag[i][c]   = sum_p w_i(p) |G[p][c]|          (the unit a row's error is measured in)
 
-The float32 restatement (numpy) takes nothing from float64: it replays the header's definition on the same buffers -- the float32
+The float32 restatement (numpy) takes nothing from float64: it replays the header's definition on the same buffers (frame_walk_reference.weights_f32) -- the float32
 power expression with the pre-scaled conic, alpha = min(0.99, o exp(power)), the two skip tests, w = alpha T, T <- T (1 - alpha),
 up to the FORWARD's n_contrib -- and sums out in list order and dL_dF in pixel order, one float32 multiply and one float32 add per
 term.  `drops` removes terms from its backward sum only (a list entry, or one 8x4 block of a list entry), for the tests that show
@@ -19,54 +19,27 @@ the criterion sees them.
 Errors: forward, max |out - out64| over the unmasked pixels in units of max |F|; backward, per Gaussian row, |dF - dF64| / mag,
 worst channel (a channel whose mag is 0 must be exactly 0: inf otherwise).
 """
-import json
-import os
-
 import numpy as np
 
 import blend_grad_reference as B
-
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "features_margins.json")
+import frame_walk_reference as FWR
 
 TILE = 16
 MAX_MASKED = 0.01
 f32 = np.float32
+_np = FWR.to_np
 
 
 def golden():
     """tests/golden/features_margins.json: "floor", the smallest float32-restatement error of the CPU matrix, and "E_kernel", what an
     MI355X run measured per frame (tools/record_features_margins.py)."""
-    with open(GOLDEN) as f:
-        return json.load(f)
-
-
-def _np(a, dtype=None):
-    a = a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a)
-    return a if dtype is None else a.astype(dtype)
+    return FWR.golden("features_margins")
 
 
 def weights_f32(buf, W, H, tile, xs, ys):
     """(P, L) float32 weights of one tile by the header's definition, bounded by the forward's n_contrib."""
-    xy = _np(buf["points_xy_image"], f32).reshape(-1, 2)
-    co = _np(buf["conic_opacity"], f32).reshape(-1, 4)
-    pl = _np(buf["point_list"]).reshape(-1).astype(np.int64)
-    s, e = (int(v) for v in _np(buf["ranges"]).reshape(-1, 2)[tile])
-    nc = np.minimum(_np(buf["n_contrib"]).reshape(H, W)[ys, xs].astype(np.int64), e - s)
-    idx = pl[s:e]
-    P, L = len(xs), len(idx)
-    w = np.zeros((P, L), f32)
-    T = np.ones(P, f32)
-    px, py = xs.astype(f32), ys.astype(f32)
-    a_, b_, c_ = f32(-0.5) * co[idx, 0], -co[idx, 1], f32(-0.5) * co[idx, 2]
-    for k in range(int(nc.max()) if P else 0):
-        dx, dy = xy[idx[k], 0] - px, xy[idx[k], 1] - py
-        power = (a_[k] * dx * dx + c_[k] * dy * dy) + b_[k] * dx * dy
-        with np.errstate(under="ignore", over="ignore"):
-            alpha = np.minimum(f32(0.99), co[idx[k], 3] * np.exp(power, dtype=f32))
-        applied = (k < nc) & ~(power > 0) & ~(alpha < f32(1.0 / 255.0))
-        w[:, k] = np.where(applied, alpha * T, f32(0))
-        T = np.where(applied, T * (f32(1) - alpha), T)
-    return w
+    fr = FWR.frame_of_buffers(buf, W, H)
+    return FWR.weights_f32(fr, FWR.tile_range(fr, tile), xs, ys)
 
 
 def _row_f32(wb, g32, C):
@@ -87,6 +60,7 @@ def render(buf, W, H, F, G, drops=()):
     N, C = F64.shape
     ranges = _np(buf["ranges"]).reshape(-1, 2)
     nb = {k: _np(v) for k, v in buf.items() if k in ("points_xy_image", "conic_opacity", "colors", "depths", "point_list", "ranges", "n_contrib")}
+    fr = FWR.frame_of_buffers(nb, W, H)
     out64, out32 = np.zeros((H, W, C)), np.zeros((H, W, C), f32)
     dF64, mag = np.zeros((N, C)), np.zeros((N, C))
     sums32 = [np.zeros((N, C), f32) for _ in range(1 + len(drops))]      # the intact sum, then one per drop
@@ -99,7 +73,7 @@ def render(buf, W, H, F, G, drops=()):
         out64[ys, xs] = w @ F64[idx]
         np.add.at(dF64, idx, w.T @ g)
         np.add.at(mag, idx, w.T @ np.abs(g))
-        w32 = weights_f32(nb, W, H, tile, xs, ys)
+        w32 = FWR.weights_f32(fr, FWR.tile_range(fr, tile), xs, ys)
         acc = np.zeros((len(xs), C), f32)
         for k in range(w32.shape[1]):                                # list order
             if w32[:, k].any():

@@ -28,14 +28,11 @@ at random do not keep that promise (a wave would pass over entries its pixels ap
 alpha reaches HALF the 1/255 threshold within its n_contrib -- looser than `applied`, so that a float32 decision at the threshold
 cannot fall outside it.
 """
-import json
-import os
-
 import numpy as np
 
 import frame_walk_frames as FW
+import frame_walk_reference as FWR
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "median_depth_margins.json")
 TIE = 2e-4
 MAX_TIES = 0.01              # the largest share of a frame's pixels the tie mask may cover
 ALPHA_MIN = float(np.float32(1.0 / 255.0))
@@ -46,15 +43,7 @@ N_GAUSS = 700
 def golden():
     """tests/golden/median_depth_margins.json: "tie_share" per frame (CPU, from the reference alone), "E_backward" per frame, what an
     MI355X run measured (tools/record_median_depth_margins.py), and "mesh_gap_min" (null until every README row shows a gap)."""
-    with open(GOLDEN) as f:
-        return json.load(f)
-
-
-def tile_pixels(fr, tile):
-    gx = (fr["W"] + 15) // 16
-    tx, ty = tile % gx, tile // gx
-    ys, xs = np.meshgrid(np.arange(ty * 16, min(fr["H"], ty * 16 + 16)), np.arange(tx * 16, min(fr["W"], tx * 16 + 16)), indexing="ij")
-    return xs.ravel(), ys.ravel()
+    return FWR.golden("median_depth_margins")
 
 
 def median_f64(fr, n_contrib=None):
@@ -69,11 +58,9 @@ def median_f64(fr, n_contrib=None):
     T_final, applied_n = np.ones((H, W)), np.zeros((H, W), np.int64)
     power_skips = 0
     need = np.zeros(fr["D"], np.uint8)
-    for tile, (s, e) in enumerate(fr["ranges"]):
-        s, e = min(max(int(s), 0), fr["D"]), min(max(int(e), 0), fr["D"])
-        if e <= s:
-            continue
-        xs, ys = tile_pixels(fr, tile)
+    for tile, s, e, xs, ys in FWR.tiles(fr):
+        on_image = (xs < W) & (ys < H)
+        xs, ys = xs[on_image], ys[on_image]
         idx = pl[s:e]
         L = len(idx)
         valid = (idx >= 0) & (idx < N)
@@ -148,7 +135,9 @@ def _wall(fr, rng, gid, opacity, sigma):
 def _full_lists(fr, rng, share):
     """n_contrib = the whole list at `share` of each tile's pixels (build_frame's once_per_tile keeps n_contrib short of the end)."""
     for tile, ln in enumerate(fr["tile_len"]):
-        xs, ys = tile_pixels(fr, tile)
+        xs, ys = FWR.tile_grid(fr["W"], tile)
+        on_image = (xs < fr["W"]) & (ys < fr["H"])
+        xs, ys = xs[on_image], ys[on_image]
         sel = rng.random(len(xs)) < share
         fr["n_contrib"][ys[sel], xs[sel]] = ln
 

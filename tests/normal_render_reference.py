@@ -16,21 +16,17 @@ Test helper, not a test file.
             are marked: the count decision is a float32 one there.
 
 The float32 restatement (numpy) takes nothing from float64: normals_f32 / normals_backward_f32 replay (a) and (b), render_f32 and
-render_backward_f32 replay (c) and (d) on the same buffers with distortion_reference's walk -- one fused multiply-add per term (in
-float64 arithmetic rounded once, which is what an fma is) and the block sums in the header's order -- and consistency_f32 replays (e).
+render_backward_f32 replay (c) and (d) on the same buffers with frame_walk_reference's walk, fma32 (one fused multiply-add per term)
+and backward_block (the block sums in the header's order), with this stage's u = G . n and tail w G -- and consistency_f32 replays (e).
 """
-import json
-import os
-
 import numpy as np
 import torch
 
 import blend_grad_reference as B
-import distortion_reference as DR
+import frame_walk_reference as FWR
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "normal_render_margins.json")
 f32 = np.float32
-EPS32 = float(np.finfo(np.float32).eps)
+EPS32 = FWR.EPS32
 UNDECIDED = 1e-4
 LENGTH_NEAR = 1e-6
 MIN_LENGTH = f32(1e-3)
@@ -39,14 +35,13 @@ OUTPUTS = ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dnormals")
 COLUMNS = {"dL_dmean2D": (3, 4), "dL_dconic": (6, 7, 8, 9), "dL_dopacity": (10,)}
 TOUCHED = (3, 4, 6, 7, 9, 10)
 UNTOUCHED = (0, 1, 2, 5, 8, 11, 12, 13, 14, 15)
-_np = DR._np
+_np, criterion, rows_error = FWR.to_np, FWR.criterion, FWR.rows_error
 
 
 def golden():
     """tests/golden/normal_render_margins.json: "E_f32" {frame: {output: the restatement's error on the CPU oracle's buffers}},
     "floor" (the smallest of them), "E_kernel" (what an MI355X run measured per frame, tools/record_normal_render_margins.py)."""
-    with open(GOLDEN) as f:
-        return json.load(f)
+    return FWR.golden("normal_render_margins")
 
 
 # ---- (a), (b) ----
@@ -175,7 +170,7 @@ def yardstick(buf, W, H, normals, G):
     """One pass.  normals (N, 3), G (H, W, 3) dL/d(image); G is zeroed at the masked pixels on this side (the caller zeroes it there
     too).  Returns dict: image (H, W, 3) float64, mask (H, W) bool, G (the zeroed one), and one {"signed", "abs", "scale"} dict
     per OUTPUTS key."""
-    xy, co, pl, rg = DR._arrays(buf)
+    xy, co, pl, rg = FWR.arrays(buf)
     n64 = _np(normals, np.float64)
     image = np.zeros((H, W, 3))
     ones = np.ones((H, W, 3))
@@ -194,26 +189,20 @@ def yardstick(buf, W, H, normals, G):
     return r
 
 
-def _fma32(a, b, c):
-    """fma(a, b, c) of float32 arrays: the float32 product is exact in float64, and one rounding of the float64 sum to float32 is the
-    fused result except where that sum is itself inexact within half a float32 ulp -- double rounding, rarer than 2^-29 per term."""
-    return (a.astype(np.float64) * b.astype(np.float64) + c.astype(np.float64)).astype(f32)
-
-
 def render_f32(buf, W, H, normals):
     """(H, W, 3) float32 by the header's (c)."""
     n32 = _np(normals, f32)
+    fr = FWR.frame_of_buffers(buf, W, H)
     out = np.zeros((H, W, 3), f32)
-    zero = np.zeros(len(n32), f32)
-    for tile, xs, ys in DR._tiles(buf, W, H):
+    for tile, s, e, xs, ys in FWR.tiles(fr):
         inside = (xs < W) & (ys < H)
         xs_, ys_ = xs[inside], ys[inside]
         acc, T = np.zeros((len(xs_), 3), f32), np.ones(len(xs_), f32)
-        for applied, alpha, G, dx, dy, i, con, o, mk in DR._walk_f32(buf, W, H, tile, xs_, ys_, zero):
+        for applied, alpha, G, dx, dy, i, *_ in FWR.walk_f32(fr, s, e, xs_, ys_, np.ones(len(xs_), bool)):
             w = alpha * T
             T = np.where(applied, T * (f32(1) - alpha), T)
             for c in range(3):
-                acc[:, c] = np.where(applied, _fma32(w, np.full_like(w, n32[i, c]), acc[:, c]), acc[:, c])
+                acc[:, c] = np.where(applied, FWR.fma32(w, n32[i, c], acc[:, c]), acc[:, c])
         out[ys_, xs_] = acc
     return out
 
@@ -222,89 +211,40 @@ def render_backward_f32(buf, W, H, normals, G, image, drop_suffix=False):
     """(acc (N, 16), dnormals (N, 3)) float32 by the header's (d) (only the six columns it adds to are non-zero).  drop_suffix: a
     WRONG backward that forgets the suffix term of dL/dalpha, for the test that shows the criterion sees it."""
     n32, G32, img = _np(normals, f32), _np(G, f32).reshape(H, W, 3), _np(image, f32).reshape(H, W, 3)
-    N = len(n32)
-    acc, dn = np.zeros((N, 16), f32), np.zeros((N, 3), f32)
-    zero = np.zeros(N, f32)
-    half_w, half_h = f32(0.5) * f32(W), f32(0.5) * f32(H)
-    for tile, xs, ys in DR._tiles(buf, W, H):
-        for blk in range(4):
-            sel = ((xs % 16) // 8 == blk % 2) & ((ys % 16) // 8 == blk // 2)
-            bx, by = xs[sel], ys[sel]
-            inside = (bx < W) & (by < H)
-            cx, cy = np.where(inside, bx, 0), np.where(inside, by, 0)
-            g = np.where(inside[:, None], G32[cy, cx], f32(0))
-            im = np.where(inside[:, None], img[cy, cx], f32(0))
+    fr = FWR.frame_of_buffers(buf, W, H)
+    acc, dn = np.zeros((fr["N"], 16), f32), np.zeros((fr["N"], 3), f32)
+    for tile, s, e, xs, ys in FWR.tiles(fr):
+        for bx, by, inside in FWR.blocks(xs, ys, W, H):
+            g, im = FWR.block_values(G32, bx, by, inside), FWR.block_values(img, bx, by, inside)
             total = (g[:, 0] * im[:, 0] + g[:, 1] * im[:, 1]) + g[:, 2] * im[:, 2]
-            Pfx, T = np.zeros(64, f32), np.ones(64, f32)
-            for applied, alpha, Gexp, dx, dy, i, con, o, mk in DR._walk_f32(buf, W, H, tile, cx, cy, zero):
-                applied = applied & inside
-                if not applied.any():
-                    continue
+
+            def entry(i, dx, dy, w):
                 n = n32[i]
-                u = (g[:, 0] * n[0] + g[:, 1] * n[1]) + g[:, 2] * n[2]
-                w = alpha * T
-                Pfx = np.where(applied, Pfx + w * u, Pfx)
-                R = total - Pfx
-                om = f32(1) - alpha
-                q = T * u if drop_suffix else T * u - R / om
-                gd = Gexp * q
-                h = o * gd
-                hx, hy = h * dx, h * dy
-                vals = np.stack([hx, hy, hx * dx, hx * dy, hy * dy, gd, w * g[:, 0], w * g[:, 1], w * g[:, 2]])
-                vals = np.where(applied[None, :], vals, f32(0))
-                T = np.where(applied, T * om, T)
-                r = np.cumsum(vals[:, :32], axis=1, dtype=f32)[:, -1] + np.cumsum(vals[:, 32:], axis=1, dtype=f32)[:, -1]
-                a_, b_, c_ = con
-                acc[i, 3] += (f32(2) * a_ * r[0] + b_ * r[1]) * half_w
-                acc[i, 4] += (f32(2) * c_ * r[1] + b_ * r[0]) * half_h
-                acc[i, 6] += f32(-0.5) * r[2]
-                acc[i, 7] += f32(-0.5) * r[3]
-                acc[i, 9] += f32(-0.5) * r[4]
-                acc[i, 10] += r[5]
-                dn[i] += r[6:9]
+                return (g[:, 0] * n[0] + g[:, 1] * n[1]) + g[:, 2] * n[2], (w * g[:, 0], w * g[:, 1], w * g[:, 2])
+
+            for i, tail in FWR.backward_block(fr, s, e, bx, by, inside, total, entry, acc, drop_suffix):
+                dn[i] += tail
     return acc, dn
 
 
 def layout(acc, dn, key):
-    if key == "dL_dnormals":
-        return _np(dn, np.float64).reshape(-1, 3)
-    return _np(acc, np.float64).reshape(-1, 16)[:, list(COLUMNS[key])]
+    return FWR.layout(acc, key, COLUMNS, dn)
 
 
 def backward_errors(acc, dn, r):
     """{key: worst per-Gaussian error in the key's scale}."""
-    return {k: B.worst(layout(acc, dn, k), r[k]) for k in OUTPUTS}
+    return FWR.backward_errors(acc, r, OUTPUTS, COLUMNS, dn)
 
 
 def spread(a, b, r):
     """The worst difference of two runs' (acc, dnormals) in the same units."""
-    worst = 0.0
-    for k in OUTPUTS:
-        d, sc = np.abs(layout(*a, k) - layout(*b, k)), r[k]["scale"]
-        sel = sc > 0
-        if sel.any():
-            worst = max(worst, float((d[sel] / sc[sel]).max()))
-    return worst
-
-
-criterion = DR.criterion
+    return FWR.spread(a, b, r, OUTPUTS, COLUMNS)
 
 
 def image_error(img, r):
     """max |img - image64| over the unmasked pixels (the normals are unit vectors: the unit is 1)."""
     d = np.abs(_np(img, np.float64).reshape(r["image"].shape) - r["image"])[~r["mask"]]
     return float(d.max()) if d.size else 0.0
-
-
-def rows_error(got, want, scale, keep=None):
-    """Worst |got - want| / scale over the kept rows; a component whose scale is 0 must be exactly 0 (inf otherwise)."""
-    got, want = _np(got, np.float64), np.asarray(want, np.float64)
-    d = np.abs(got - want)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        e = np.where(scale > 0, d / np.where(scale > 0, scale, 1.0), np.where(d != 0, np.inf, 0.0))
-    if keep is not None:
-        e = e[keep]
-    return float(e.max()) if e.size else 0.0
 
 
 # ---- (e) ----

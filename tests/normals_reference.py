@@ -104,7 +104,7 @@ def target_unit(target, R, dtype=np.float64):
     return np.where(t_ok[..., None], th, dtype(0)), t_ok
 
 
-def _gather(Dinv, dec, cam, g, dtype):
+def gather(Dinv, dec, cam, g, dtype):
     """The header's gather in `dtype`: (normals, gD, gA) for dL/dn = g (H, W, 3; rows of pixels that are not valid ignored)."""
     f = dtype
     valid, defined = dec["valid"], dec["defined"]
@@ -138,7 +138,7 @@ def loss_direction(case, dtype=np.float64):
 
 def _loss(case, dtype):
     g, th, ok, m = loss_direction(case, dtype)
-    n, gD, gA, *_ = _gather(case["Dinv"], case["dec"], case["cam"], g, dtype)
+    n, gD, gA, *_ = gather(case["Dinv"], case["dec"], case["cam"], g, dtype)
     terms = np.where(ok, m.astype(np.float64) * (1.0 - _dot(n.astype(np.float64), th.astype(np.float64))), 0.0)
     return {"normals": n, "valid": case["dec"]["valid"], "sums": (float(terms.sum()), float(np.where(ok, m, 0).astype(np.float64).sum())),
             "gD": gD, "gA": gA}
@@ -156,10 +156,10 @@ def restatement32(case):
 
 def closed_form_vjp(case, g, dtype=np.float64):
     """(gD, gA) of an arbitrary dL/dn by the header's gather."""
-    return _gather(case["Dinv"], case["dec"], case["cam"], g, dtype)[1:3]
+    return gather(case["Dinv"], case["dec"], case["cam"], g, dtype)[1:3]
 
 
-def _torch_normals(D, A, dec, cam):
+def torch_normals(D, A, dec, cam):
     """Float64 torch: unit normals (H, W, 3) differentiable in D and A, zeros where not valid."""
     F = torch.nn.functional
     defined, valid = torch.as_tensor(dec["defined"]), torch.as_tensor(dec["valid"])
@@ -178,7 +178,7 @@ def autograd_vjp(case, g):
     """(normals, gD, gA): d(sum g . n)/d(Dinv, A) by torch autograd in float64."""
     D = torch.tensor(np.asarray(case["Dinv"], np.float64), requires_grad=True)
     A = torch.tensor(case["dec"]["A"].astype(np.float64), requires_grad=True)
-    n = _torch_normals(D, A, case["dec"], case["cam"])
+    n = torch_normals(D, A, case["dec"], case["cam"])
     gD, gA = torch.autograd.grad((n * torch.as_tensor(np.asarray(g, np.float64))).sum(), (D, A))
     return n.detach().numpy(), gD.numpy(), gA.numpy()
 
@@ -190,7 +190,7 @@ def reference(case):
     m = np.ones(ok.shape) if case["mask"] is None else np.asarray(case["mask"], np.float64)
     D = torch.tensor(np.asarray(case["Dinv"], np.float64), requires_grad=True)
     A = torch.tensor(case["dec"]["A"].astype(np.float64), requires_grad=True)
-    n = _torch_normals(D, A, case["dec"], case["cam"])
+    n = torch_normals(D, A, case["dec"], case["cam"])
     terms = torch.as_tensor(np.where(ok, m, 0.0)) * (1.0 - (n * torch.as_tensor(th)).sum(-1))
     loss_sum = terms.sum()
     if ok.any():

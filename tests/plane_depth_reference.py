@@ -16,22 +16,17 @@ Test helper, not a test file.
             there.  Outputs with {"signed", "abs", "scale"} sums per Gaussian, as blend_grad_reference has them.
 
 The float32 restatement (numpy) takes nothing from float64.  Frames are frame_walk_frames dicts (frame_of_buffers turns a forward's
-buffers into one); ids outside [0, N) are skipped as the kernels skip them.  A fused multiply-add is the exact product and sum in
-extended precision rounded once to float32 (x87 long double where numpy has it: 64 bits hold the 48-bit product exactly, and the
-second rounding then changes a result only with probability 2^-40 per operation).
+buffers into one); the walk, the fused multiply-add and the backward's body are frame_walk_reference's, and what is written here is
+the stage's own: m and its clamp, u = g m, total = g image, and the three moments as the tail.
 """
-import json
-import os
-
 import numpy as np
 import torch
 
 import blend_grad_reference as B
-import distortion_reference as DR
+import frame_walk_reference as FWR
 
-GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "plane_depth_margins.json")
 f32 = np.float32
-EPS32 = float(np.finfo(np.float32).eps)
+EPS32 = FWR.EPS32
 MIN_COS, MAX_FLATNESS, NEAR, MAX_RATIO = f32(0.1), f32(0.5), f32(0.2), f32(4.0)
 MARGIN_CAP = 100 * EPS32          # every decision a test keeps lies farther than this from its threshold
 CLAMP_NEAR = MARGIN_CAP
@@ -39,25 +34,18 @@ OUTPUTS = ("dL_dmean2D", "dL_dconic", "dL_dopacity", "dL_dplane_moments")
 COLUMNS = {"dL_dmean2D": (3, 4), "dL_dconic": (6, 7, 8, 9), "dL_dopacity": (10,)}
 TOUCHED = (3, 4, 6, 7, 9, 10)
 UNTOUCHED = (0, 1, 2, 5, 8, 11, 12, 13, 14, 15)
-_np = DR._np
-_LD = np.longdouble if np.finfo(np.longdouble).nmant >= 63 else np.float64
-criterion = DR.criterion
+_np, fma32, criterion, rows_error, frame_of_buffers = FWR.to_np, FWR.fma32, FWR.criterion, FWR.rows_error, FWR.frame_of_buffers
 
 
 def golden():
     """tests/golden/plane_depth_margins.json: "E_f32" {frame: {output: the restatement's error on the CPU oracle's buffers}}, "floor"
     (the smallest positive one), "E_kernel" (what an MI355X run measured per frame, tools/record_plane_depth_margins.py: a record
     only) and "mesh_gap_min" (null: no threshold on the mesh bias, README "Plane depth")."""
-    with open(GOLDEN) as f:
-        return json.load(f)
-
-
-def fma32(a, b, c):
-    return (np.asarray(a, f32).astype(_LD) * np.asarray(b, f32).astype(_LD) + np.asarray(c, f32).astype(_LD)).astype(f32)
+    return FWR.golden("plane_depth_margins")
 
 
 # ---- (a), (d) ----
-def _steps(n, s, p, view, tx, ty, W, H, dt):
+def steps(n, s, p, view, tx, ty, W, H, dt):
     """Steps 1-6 of the header in dtype dt, left to right.  dict: pv, t, l, fallback, kx, ky, slopes."""
     n, s, p, V = _np(n, dt), _np(s, dt), _np(p, dt), _np(view, dt).reshape(4, 4)
     with np.errstate(all="ignore"):
@@ -75,14 +63,14 @@ def _steps(n, s, p, view, tx, ty, W, H, dt):
 
 def slopes_f32(n, s, p, view, tx, ty, W, H):
     """(slopes (N, 2) float32, fallback (N,) bool) by the header's (a)."""
-    r = _steps(n, s, p, view, tx, ty, W, H, f32)
+    r = steps(n, s, p, view, tx, ty, W, H, f32)
     return r["slopes"], r["fallback"]
 
 
 def slopes_backward(n, s, p, view, tx, ty, W, H, mom, dt=f32, fallback=None):
     """(the addend to dL_dmean3D (N, 3), dL_dnormals (N, 3)) by the header's (d) in dtype dt (float32: the restatement; float64 with
     the float32 `fallback` passed in: the header's formulas themselves)."""
-    r = _steps(n, s, p, view, tx, ty, W, H, dt)
+    r = steps(n, s, p, view, tx, ty, W, H, dt)
     fb = r["fallback"] if fallback is None else np.asarray(fallback, bool)
     pv, t, V, nn = r["pv"], np.where(fb, dt(1), r["t"]), r["V"], r["n"]
     kx, ky = r["kx"], r["ky"]
@@ -105,7 +93,7 @@ def slopes_backward(n, s, p, view, tx, ty, W, H, mom, dt=f32, fallback=None):
 def branch_margins(n, s, p, view):
     """(N,) float64: the smallest relative distance of a Gaussian's step-5 decisions from their thresholds, each in units of the
     magnitudes the float32 comparison rounds against (inf for the exact zero normal, which decides alone)."""
-    r = _steps(n, s, p, view, 1.0, 1.0, 1, 1, np.float64)
+    r = steps(n, s, p, view, 1.0, 1.0, 1, 1, np.float64)
     pv, nn = r["pv"], r["n"]
     with np.errstate(all="ignore"):
         near = np.abs(pv[:, 2] - float(NEAR)) / np.maximum(np.abs(_np(p, np.float64)).max(1) + 1.0, float(NEAR))
@@ -115,13 +103,13 @@ def branch_margins(n, s, p, view):
     return np.where(nn.any(1), m, np.inf)
 
 
-def _pixel_of(pv, tx, ty, W, H):
+def pixel_of(pv, tx, ty, W, H):
     return ((pv[:, 0] / (pv[:, 2] * tx) + 1.0) * W - 1.0) * 0.5, ((pv[:, 1] / (pv[:, 2] * ty) + 1.0) * H - 1.0) * 0.5
 
 
 def slopes_f64(n, s, p, view, tx, ty, W, H, fallback):
     """(N, 2) float64 slopes by the definition, the branch passed in."""
-    r = _steps(n, s, p, view, tx, ty, W, H, np.float64)
+    r = steps(n, s, p, view, tx, ty, W, H, np.float64)
     fb = np.asarray(fallback, bool)
     t = np.where(fb, 1.0, r["t"])
     return np.where(fb[:, None], 0.0, np.stack([r["n"][:, 0] * r["kx"] / t, r["n"][:, 1] * r["ky"] / t], 1))
@@ -142,7 +130,7 @@ def slopes_vjp_f64(n, s, p, view, tx, ty, W, H, fallback, mom):
     t = torch.where(fb, torch.ones_like(z), (nt * pv).sum(1))
     kx, ky = 2.0 * tx / W, 2.0 * ty / H
     gx, gy = nt[:, 0] * kx / t, nt[:, 1] * ky / t
-    x, y = _pixel_of(torch.stack([pv[:, 0], pv[:, 1], z], 1), tx, ty, W, H)
+    x, y = pixel_of(torch.stack([pv[:, 0], pv[:, 1], z], 1), tx, ty, W, H)
     A1, A2 = S[:, 1] + x.detach() * S[:, 0], S[:, 2] + y.detach() * S[:, 0]
     plane = invd * S[:, 0] + gx * (A1 - x * S[:, 0]) + gy * (A2 - y * S[:, 0])
     L = torch.where(fb, invd * S[:, 0], plane).sum()
@@ -157,17 +145,6 @@ def slopes_vjp_f64(n, s, p, view, tx, ty, W, H, fallback, mom):
     sn = np.where(f[:, None], 0.0, (Ra + Ma[:, None] * pva) / ta[:, None])
     sp = np.where(f[:, None], np.stack([0 * ia, 0 * ia, ia * ia * Sa[:, 0]], 1), Ma[:, None] * na / ta[:, None])
     return dmean.numpy(), dn.numpy(), sp @ Va.T, sn
-
-
-def rows_error(got, want, scale, keep=None):
-    """Worst |got - want| / scale over the kept rows; a component whose scale is 0 must be exactly 0 (inf otherwise)."""
-    got, want = _np(got, np.float64), np.asarray(want, np.float64)
-    d = np.abs(got - want)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        e = np.where(scale > 0, d / np.where(scale > 0, scale, 1.0), np.where(d != 0, np.inf, 0.0))
-    if keep is not None:
-        e = e[keep]
-    return float(e.max()) if e.size else 0.0
 
 
 def draw_gaussians(N, view, seed=5):
@@ -199,51 +176,9 @@ def draw_gaussians(N, view, seed=5):
     return n.astype(f32), s.astype(f32), p, special
 
 
-# ---- frames ----
-def frame_of_buffers(nb, W, H, invd):
-    """A frame_walk_frames dict over a forward's buffers (numpy or torch) and the (N,) float32 inverse depths the kernel reads."""
-    pl = _np(nb["point_list"]).reshape(-1)
-    xy = _np(nb["points_xy_image"], f32).reshape(-1, 2)
-    return dict(W=W, H=H, N=xy.shape[0], D=int(pl.shape[0]), xy=xy, co=_np(nb["conic_opacity"], f32).reshape(-1, 4), invd=_np(invd, f32).reshape(-1),
-                point_list=pl, ranges=_np(nb["ranges"]).reshape(-1, 2), n_contrib=_np(nb["n_contrib"]).reshape(H, W))
-
-
+# ---- (b), (c): the restatement ----
 def inv_depth_of_buffers(nb):
-    return DR.inv_depth(nb, f32)
-
-
-def _tiles(fr):
-    gx = (fr["W"] + 15) // 16
-    for tile, (s, e) in enumerate(fr["ranges"]):
-        s, e = min(max(int(s), 0), fr["D"]), min(max(int(e), 0), fr["D"])
-        if e <= s:
-            continue
-        tx, ty = tile % gx, tile // gx
-        ys, xs = np.meshgrid(np.arange(ty * 16, ty * 16 + 16), np.arange(tx * 16, tx * 16 + 16), indexing="ij")   # the whole tile
-        yield tile, s, e, xs.ravel(), ys.ravel()
-
-
-def _walk_f32(fr, s, e, xs, ys, inside):
-    """The header's weights of one tile's list for the pixels (xs, ys), float32: yields per list position with an id in [0, N)
-    (applied (P,) bool, alpha, G, dx, dy, id, conic' (a', b', c'), opacity)."""
-    xy, co = fr["xy"], fr["co"]
-    idx = fr["point_list"][s:e].astype(np.int64)
-    cx, cy = np.where(inside, xs, 0), np.where(inside, ys, 0)
-    nc = np.where(inside, np.clip(fr["n_contrib"][cy, cx].astype(np.int64), 0, e - s), 0)
-    px, py = xs.astype(f32), ys.astype(f32)
-    for k in range(int(nc.max()) if len(xs) else 0):
-        i = int(idx[k])
-        if i < 0 or i >= fr["N"]:
-            continue
-        a_, b_, c_ = f32(-0.5) * co[i, 0], -co[i, 1], f32(-0.5) * co[i, 2]
-        dx, dy = xy[i, 0] - px, xy[i, 1] - py
-        power = (a_ * dx * dx + c_ * dy * dy) + b_ * dx * dy
-        with np.errstate(under="ignore", over="ignore"):
-            G = np.exp(power, dtype=f32)
-            alpha = np.minimum(f32(0.99), co[i, 3] * G)
-        applied = (k < nc) & ~(power > 0) & ~(alpha < f32(1.0 / 255.0))
-        if applied.any():
-            yield applied, alpha, G, dx, dy, i, (a_, b_, c_), co[i, 3]
+    return FWR.inv_depth(nb, f32)
 
 
 def _m32(fr, slopes, i, dx, dy):
@@ -259,11 +194,11 @@ def render_f32(fr, slopes):
     W, H = fr["W"], fr["H"]
     sl = _np(slopes, f32).reshape(-1, 2)
     out, Tf = np.zeros((H, W), f32), np.ones((H, W), f32)
-    for tile, s, e, xs, ys in _tiles(fr):
+    for tile, s, e, xs, ys in FWR.tiles(fr):
         inside = (xs < W) & (ys < H)
         xs_, ys_ = xs[inside], ys[inside]
         acc, T = np.zeros(len(xs_), f32), np.ones(len(xs_), f32)
-        for applied, alpha, G, dx, dy, i, con, o in _walk_f32(fr, s, e, xs_, ys_, np.ones(len(xs_), bool)):
+        for applied, alpha, G, dx, dy, i, *_ in FWR.walk_f32(fr, s, e, xs_, ys_, np.ones(len(xs_), bool)):
             m, _ = _m32(fr, sl, i, dx, dy)
             w = alpha * T
             T = np.where(applied, T * (f32(1) - alpha), T)
@@ -278,41 +213,17 @@ def render_backward_f32(fr, slopes, g, image, drop_suffix=False):
     W, H, N = fr["W"], fr["H"], fr["N"]
     sl, g32, img = _np(slopes, f32).reshape(-1, 2), _np(g, f32).reshape(H, W), _np(image, f32).reshape(H, W)
     acc, mom = np.zeros((N, 16), f32), np.zeros((N, 3), f32)
-    half_w, half_h = f32(0.5) * f32(W), f32(0.5) * f32(H)
-    for tile, s, e, xs, ys in _tiles(fr):
-        for blk in range(4):
-            sel = ((xs % 16) // 8 == blk % 2) & ((ys % 16) // 8 == blk // 2)
-            bx, by = xs[sel], ys[sel]
-            inside = (bx < W) & (by < H)
-            cx, cy = np.where(inside, bx, 0), np.where(inside, by, 0)
-            gg = np.where(inside, g32[cy, cx], f32(0))
-            total = gg * np.where(inside, img[cy, cx], f32(0))
-            Pfx, T = np.zeros(64, f32), np.ones(64, f32)
-            for applied, alpha, Gexp, dx, dy, i, con, o in _walk_f32(fr, s, e, bx, by, inside):
+    for tile, s, e, xs, ys in FWR.tiles(fr):
+        for bx, by, inside in FWR.blocks(xs, ys, W, H):
+            gg = FWR.block_values(g32, bx, by, inside)
+
+            def entry(i, dx, dy, w):
                 m, clamped = _m32(fr, sl, i, dx, dy)
-                with np.errstate(all="ignore"):
-                    u = gg * m
-                    w = alpha * T
-                    Pfx = np.where(applied, Pfx + w * u, Pfx)
-                    R = total - Pfx
-                    om = f32(1) - alpha
-                    q = T * u if drop_suffix else T * u - R / om
-                    gd = Gexp * q
-                    h = o * gd
-                    hx, hy = h * dx, h * dy
-                    wg = np.where(clamped, f32(0), w * gg)
-                    vals = np.stack([hx, hy, hx * dx, hx * dy, hy * dy, gd, wg, wg * (-dx), wg * (-dy)])
-                vals = np.where(applied[None, :], vals, f32(0))
-                T = np.where(applied, T * om, T)
-                r = np.cumsum(vals[:, :32], axis=1, dtype=f32)[:, -1] + np.cumsum(vals[:, 32:], axis=1, dtype=f32)[:, -1]
-                a_, b_, c_ = con
-                acc[i, 3] += (f32(2) * a_ * r[0] + b_ * r[1]) * half_w
-                acc[i, 4] += (f32(2) * c_ * r[1] + b_ * r[0]) * half_h
-                acc[i, 6] += f32(-0.5) * r[2]
-                acc[i, 7] += f32(-0.5) * r[3]
-                acc[i, 9] += f32(-0.5) * r[4]
-                acc[i, 10] += r[5]
-                mom[i] += r[6:9]
+                wg = np.where(clamped, f32(0), w * gg)
+                return gg * m, (wg, wg * (-dx), wg * (-dy))
+
+            for i, tail in FWR.backward_block(fr, s, e, bx, by, inside, gg * FWR.block_values(img, bx, by, inside), entry, acc, drop_suffix):
+                mom[i] += tail
     return acc, mom
 
 
@@ -322,7 +233,7 @@ def yardstick(nb, W, H, invd, slopes, g):
     the masked pixels (the caller feeds the kernel r["g"]).  Returns dict: image (H, W) float64, coverage (H, W), mask (H, W) bool,
     g, clamped (how many applied (pixel, entry) pairs were clamped), clamp_margin (the smallest kept distance of a clamp decision
     from its threshold, in units of invd), and one {"signed", "abs", "scale"} dict per OUTPUTS key."""
-    xy, co, pl, rg = DR._arrays(nb)
+    xy, co, pl, rg = FWR.arrays(nb)
     N = xy.shape[0]
     m0, sl = _np(invd, np.float64).reshape(-1), _np(slopes, np.float64).reshape(-1, 2)
     m032, sl32, xy32 = _np(invd, f32).reshape(-1), _np(slopes, f32).reshape(-1, 2), _np(nb["points_xy_image"], f32).reshape(-1, 2)
@@ -391,25 +302,17 @@ def yardstick(nb, W, H, invd, slopes, g):
 
 
 def layout(acc, mom, key):
-    if key == "dL_dplane_moments":
-        return _np(mom, np.float64).reshape(-1, 3)
-    return _np(acc, np.float64).reshape(-1, 16)[:, list(COLUMNS[key])]
+    return FWR.layout(acc, key, COLUMNS, mom)
 
 
 def backward_errors(acc, mom, r):
     """{key: worst per-Gaussian error in the key's scale}."""
-    return {k: B.worst(layout(acc, mom, k), r[k]) for k in OUTPUTS}
+    return FWR.backward_errors(acc, r, OUTPUTS, COLUMNS, mom)
 
 
 def spread(a, b, r):
     """The worst difference of two runs' (acc, moments) in the same units."""
-    worst = 0.0
-    for k in OUTPUTS:
-        d, sc = np.abs(layout(*a, k) - layout(*b, k)), r[k]["scale"]
-        sel = sc > 0
-        if sel.any():
-            worst = max(worst, float((d[sel] / sc[sel]).max()))
-    return worst
+    return FWR.spread(a, b, r, OUTPUTS, COLUMNS)
 
 
 def image_error(img, r, invd):

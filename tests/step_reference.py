@@ -237,10 +237,10 @@ def consistency_images(frame, lam_nc, alpha_min):
     valid = dec["valid"].astype(np.float32)
     nimg = np.asarray(_np64(frame["nimg"], (H, W, 3)), np.float32)
     with torch.no_grad():
-        nd = NR._torch_normals(torch.as_tensor(d32.astype(np.float64)), torch.as_tensor(dec["A"].astype(np.float64)), dec, cam).numpy()
+        nd = NR.torch_normals(torch.as_tensor(d32.astype(np.float64)), torch.as_tensor(dec["A"].astype(np.float64)), dec, cam).numpy()
     r = NRR.consistency_f64(nimg, nd, valid, None, lam_nc, W, H)
     _, gD, gA = NR.autograd_vjp(case, r["gnd"])
-    nd32 = NR._gather(d32, dec, cam, np.zeros((H, W, 3), np.float32), np.float32)[0]
+    nd32 = NR.gather(d32, dec, cam, np.zeros((H, W, 3), np.float32), np.float32)[0]
     _, gN32, gnd32, _ = NRR.consistency_f32(nimg, nd32, valid, None, lam_nc, W, H)
     keep = ~r["near"]
     rel = lambda a32, a64: float(np.abs(a32 - a64)[keep].max() / max(np.abs(a64).max(), 1e-300))
@@ -282,7 +282,7 @@ def objective(img, dinv, fT, frame, tg, cfg, dist=None, nimg=None):
         dec = NR.decide(d32, t32, cam, cfg.get("alpha_min", NR.ALPHA_MIN))
         th, t_ok = NR.target_unit(np.asarray(_np64(tg["normal_target"], (H, W, 3)), np.float32), tg.get("normal_rot"))
         ok = torch.as_tensor(dec["valid"] & t_ok)
-        n = NR._torch_normals(dinv, 1.0 - fT, dec, cam)
+        n = NR.torch_normals(dinv, 1.0 - fT, dec, cam)
         L = L + float(np.float32(lam_n / (W * H))) * torch.where(ok, 1.0 - (n * torch.as_tensor(th)).sum(-1), torch.zeros_like(dinv)).sum()
     lam_dist, lam_nc = active_weights(cfg)
     if lam_dist > 0.0:
@@ -295,7 +295,7 @@ def objective(img, dinv, fT, frame, tg, cfg, dist=None, nimg=None):
         n32 = np.asarray(_np64(frame["nimg"], (H, W, 3)), np.float32)
         L2 = (n32[..., 0] * n32[..., 0] + n32[..., 1] * n32[..., 1]) + n32[..., 2] * n32[..., 2]
         counted = torch.as_tensor(dec["valid"] & (L2 >= NRR.MIN_LENGTH * NRR.MIN_LENGTH))
-        nd = NR._torch_normals(dinv, 1.0 - fT, dec, cam)
+        nd = NR.torch_normals(dinv, 1.0 - fT, dec, cam)
         ln = torch.where(counted, nimg.norm(dim=2), torch.ones_like(dinv))
         L = L + lam_nc / (W * H) * torch.where(counted, 1.0 - (nd * nimg).sum(-1) / ln, torch.zeros_like(dinv)).sum()
     return L

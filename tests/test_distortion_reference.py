@@ -21,6 +21,7 @@ import torch
 import blend_grad_reference as B
 import distortion_reference as DR
 import features_reference as FR
+import frame_walk_reference as FWR
 
 STRAIGHT_THROUGH_CAP = True
 _CASES = {}
@@ -48,7 +49,7 @@ def oracle_case(oracle, scenes, cameras, name):
 def autograd_of_the_double_sum(c, straight_through):
     """{output: (N, width) float64} by torch autograd, in the kernel's units (mean2D x 0.5 (W, H), conic b halved)."""
     buf, W, H, r = c["buf"], c["W"], c["H"], c["r"]
-    xy0, co0, _, _ = DR._arrays(buf)
+    xy0, co0, _, _ = FWR.arrays(buf)
     xy = torch.tensor(xy0, requires_grad=True)
     con = torch.tensor(co0[:, :3].copy(), requires_grad=True)
     op = torch.tensor(co0[:, 3].copy(), requires_grad=True)

@@ -37,7 +37,7 @@ import torch
 
 from conftest import ROOT, backward_kwargs, lego_camera, pkg, sub
 import blend_grad_reference as B
-import distortion_reference as DR
+import frame_walk_reference as FWR
 import features_reference as FR
 import normal_render_reference as NR
 import parity
@@ -143,7 +143,7 @@ def test_gaussian_normals_and_backward_against_float64(N):
     E_k = NR.rows_error(parity.to_np(a), dq64, scale, keep)
     E_32 = NR.rows_error(NR.normals_backward_f32(s, q, p, view, g), dq64, scale, keep)
     _row(test="gaussian_normals_backward", N=N, E_kernel=E_k, E_f32=E_32)
-    assert DR.criterion(E_k, E_32, 0.0, 0.5 * NR.EPS32), (E_k, E_32)      # (floor: one rounding of the result in its scale)
+    assert FWR.criterion(E_k, E_32, 0.0, 0.5 * NR.EPS32), (E_k, E_32)      # (floor: one rounding of the result in its scale)
     assert not parity.to_np(a)[~r["ok"]].any()
     pre = torch.rand((N, 4), device=dev)
     added = nr.gaussian_normals_backward(gd, sd, qd, pd, view, dL_drot=pre.clone())
@@ -221,7 +221,7 @@ def test_backward_against_float64(name):
     _row(test="backward", case=name, E_kernel=Ek, E_f32=E32, E_f32_source=source, E_spread=E_s, floor=floor,
          E_f32_here=NR.backward_errors(f["acc32"], f["dn32"], r))
     for k in NR.OUTPUTS:
-        assert DR.criterion(Ek[k], E32[k], E_s, floor), (k, Ek[k], E32[k], E_s)
+        assert FWR.criterion(Ek[k], E32[k], E_s, floor), (k, Ek[k], E32[k], E_s)
     assert all(np.abs(runs[0][0][:, c]).max() > 0 for c in NR.TOUCHED) and np.abs(runs[0][1]).max() > 0
 
 
@@ -244,7 +244,7 @@ def test_backward_cross_checks_against_the_existing_calls(name):
     d = float((np.abs(runs[0][1] - fb[0])[sel] / sc[sel]).max())
     assert not np.abs(runs[0][1])[~sel].any() and not np.abs(fb[0])[~sel].any()
     _row(test="cross_features_backward", case=name, difference=d, E_f32=E32["dL_dnormals"], spread=E_s + s_feat)
-    assert DR.criterion(d, E32["dL_dnormals"], E_s + s_feat, floor), (d, E_s, s_feat)
+    assert FWR.criterion(d, E32["dL_dnormals"], E_s + s_feat, floor), (d, E_s, s_feat)
     # 2. the six columns are what the existing backward adds for colour := the normals, background 0, dL_dpixels = G
     kw = backward_kwargs(f["sc"], f["cam"], f["kw"], f["buf"], f["Gd"])
     kw.update(rgb=f["n"], background=np.zeros(3, np.float32), geom_buffer=dict(kw["geom_buffer"], rgb=f["n"]))
@@ -259,7 +259,7 @@ def test_backward_cross_checks_against_the_existing_calls(name):
         scale = r[k]["scale"]
         sel = scale > 0
         worst[k] = float((np.abs(NR.layout(*runs[0], k) - NR.layout(*old[0], k))[sel] / scale[sel]).max())
-        assert DR.criterion(worst[k], E32[k], E_s + s_old, floor), (k, worst[k], E32[k], E_s, s_old)
+        assert FWR.criterion(worst[k], E32[k], E_s + s_old, floor), (k, worst[k], E32[k], E_s, s_old)
     _row(test="cross_existing_backward", case=name, difference=worst, spread=E_s + s_old)
     # 3. the untouched columns are bit for bit the plain call's (no colour cotangent: a zero alpha image alone)
     plain = _backward(f, None, dL_dalpha_image=torch.zeros((H, W), device=f["dev"]))

@@ -41,7 +41,7 @@ import pytest
 import torch
 
 from conftest import ROOT, backward_kwargs, lego_camera, pkg, sub
-import distortion_reference as DR
+import frame_walk_reference as FWR
 import features_reference as FR
 import frame_walk_frames as FW
 import median_depth_reference as M
@@ -101,7 +101,7 @@ def test_slopes_and_backward_against_float64(N):
     E_32 = (PD.rows_error(rm, dmean64, sc_mean), PD.rows_error(rn, dn64, sc_n))
     _row(test="slopes_backward", N=N, E_kernel=E_k, E_f32=E_32)
     for ek, e32 in zip(E_k, E_32):
-        assert DR.criterion(ek, e32, 0.0, 0.5 * EPS32), (ek, e32)                    # (floor: one rounding of the result in its scale)
+        assert FWR.criterion(ek, e32, 0.0, 0.5 * EPS32), (ek, e32)                    # (floor: one rounding of the result in its scale)
     assert not parity.to_np(a[1])[fb].any()
     pre = torch.rand((N, 3), device=nd.device)
     poisoned = torch.full((N, 3), float("nan"), device=nd.device)
@@ -278,7 +278,7 @@ def test_image_and_backward_against_float64(name):
     _row(test="backward", case=name, E_kernel=Ek, E_f32=E32, E_f32_source=source, E_spread=E_s, floor=floor,
          E_f32_here=PD.backward_errors(f["acc32"], f["mom32"], r))
     for k in PD.OUTPUTS:
-        assert DR.criterion(Ek[k], E32[k], E_s, floor), (k, Ek[k], E32[k], E_s)
+        assert FWR.criterion(Ek[k], E32[k], E_s, floor), (k, Ek[k], E32[k], E_s)
     assert all(np.abs(runs[0][0][:, c]).max() > 0 for c in PD.TOUCHED) and np.abs(runs[0][1]).max() > 0
     # the untouched columns are bit for bit the plain call's (no colour cotangent: a zero alpha image alone), column 11 included
     plain = _backward(f, None, dL_dalpha_image=torch.zeros((H, W), device=dev))

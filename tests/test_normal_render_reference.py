@@ -18,7 +18,7 @@ import pytest
 import torch
 
 import blend_grad_reference as B
-import distortion_reference as DR
+import frame_walk_reference as FWR
 import features_reference as FR
 import normal_render_reference as NR
 import normals_reference as NDR
@@ -43,7 +43,7 @@ def oracle_case(oracle, scenes, cameras, name):
 def autograd_dense(c):
     """{output: (N, width) float64} by torch autograd of sum_p G[p] . (w(p) @ normals), in the kernel's units."""
     buf, W, H, r = c["buf"], c["W"], c["H"], c["r"]
-    xy0, co0, pl, rg = DR._arrays(buf)
+    xy0, co0, pl, rg = FWR.arrays(buf)
     xy = torch.tensor(xy0, requires_grad=True)
     con = torch.tensor(co0[:, :3].copy(), requires_grad=True)
     op = torch.tensor(co0[:, 3].copy(), requires_grad=True)

@@ -61,7 +61,7 @@ def _loss64(c, D, T):
     th, t_ok = R.target_unit(c["target"], c["R"])
     ok = c["dec"]["valid"] & t_ok
     m = np.ones(ok.shape) if c["mask"] is None else c["mask"].astype(np.float64)
-    n = R._torch_normals(torch.as_tensor(D), torch.as_tensor(1.0 - T), c["dec"], c["cam"]).numpy()
+    n = R.torch_normals(torch.as_tensor(D), torch.as_tensor(1.0 - T), c["dec"], c["cam"]).numpy()
     return float((np.where(ok, m, 0.0) * (1.0 - (n * th).sum(-1))).sum()) * c["weight32"]
 
 

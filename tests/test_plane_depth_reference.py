@@ -22,7 +22,7 @@ import pytest
 import torch
 
 import blend_grad_reference as B
-import distortion_reference as DR
+import frame_walk_reference as FWR
 import features_reference as FR
 import normal_render_reference as NR
 import plane_depth_reference as PD
@@ -86,7 +86,7 @@ def autograd_dense(c):
     """{output: (N, width) float64} by torch autograd of sum_p g[p] sum_k w_k(p) m_k(p) in the kernel's units: m from leaves
     (invd, gx, gy) and the STAGED xy held constant in it, the float32 clamp decisions of the yardstick's rule."""
     nb, W, H, r = c["nb"], c["W"], c["H"], c["r"]
-    xy0, co0, pl, rg = DR._arrays(nb)
+    xy0, co0, pl, rg = FWR.arrays(nb)
     xy = torch.tensor(xy0, requires_grad=True)
     con = torch.tensor(co0[:, :3].copy(), requires_grad=True)
     op = torch.tensor(co0[:, 3].copy(), requires_grad=True)
@@ -198,14 +198,14 @@ def test_slopes_branches_and_their_vjp(cameras, N):
     for row in special:
         assert fb[row] and not sl[row].any(), (row, special[row])
     assert not sl[fb].any() and (N < 9 or 0 < fb.sum() < N) and np.abs(sl[~fb]).min(initial=1.0) > 0
-    fb64 = PD._steps(n, s, p, view, tx, ty, W, H, np.float64)["fallback"]
+    fb64 = PD.steps(n, s, p, view, tx, ty, W, H, np.float64)["fallback"]
     assert np.array_equal(fb, fb64)
     sl64 = PD.slopes_f64(n, s, p, view, tx, ty, W, H, fb)
     assert np.abs(sl - sl64).max() <= 8 * PD.EPS32 * np.abs(sl64).max()
     # the slopes ARE the plane: m(p) = (n . r(p)) / (n . p_v) at any pixel, from invd at the projected centre
     V = view.astype(np.float64).reshape(4, 4)
     pv = p.astype(np.float64) @ V[:3, :3] + V[3, :3]
-    x, y = PD._pixel_of(pv, tx, ty, W, H)
+    x, y = PD.pixel_of(pv, tx, ty, W, H)
     for px, py in ((0.0, 0.0), (49.0, 36.0), (13.0, 29.0)):
         ray = np.array([((2 * px + 1) / W - 1) * tx, ((2 * py + 1) / H - 1) * ty, 1.0])
         k = ~fb
