@@ -276,6 +276,13 @@ PLANE_DEPTH_MAX_FLATNESS = 0.5      # GSR_PLANE_DEPTH_MAX_FLATNESS
 PLANE_DEPTH_NEAR = 0.2              # GSR_PLANE_DEPTH_NEAR (a float32 constant: 0.2f)
 PLANE_DEPTH_MAX_RATIO = 4.0         # GSR_PLANE_DEPTH_MAX_RATIO
 
+# include/gsr_plane_median.h: the ray-plane intersection depth under the median rule over a frame's lists (the frame struct is
+# gsr_distortion.h's, the slopes gsr_plane_depth.h's), and its gradient into the plane moments (its own header, so its own table)
+PLANE_MEDIAN_EXPORTS = {
+    "gsr_pmed_forward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp]),
+    "gsr_pmed_backward": (C.c_int, [C.POINTER(GsrDistortionFrame), vp, vp, vp, vp, vp]),
+}
+
 # include/gsr_normal_render.h: the Gaussians' own normals, their image over a frame's lists with its gradient into the backward's
 # accumulator records, and the depth-normal consistency term (its own header, so its own table)
 NORMAL_RENDER_EXPORTS = {
@@ -386,7 +393,8 @@ def lib():
                                   + list(FEATURES_EXPORTS.items()) + list(NORMALS_EXPORTS.items())
                                   + list(TSDF_EXPORTS.items()) + list(DISTORTION_EXPORTS.items())
                                   + list(NORMAL_RENDER_EXPORTS.items()) + list(MESH_EVAL_EXPORTS.items())
-                                  + list(MEDIAN_DEPTH_EXPORTS.items()) + list(PLANE_DEPTH_EXPORTS.items())):
+                                  + list(MEDIAN_DEPTH_EXPORTS.items()) + list(PLANE_DEPTH_EXPORTS.items())
+                                  + list(PLANE_MEDIAN_EXPORTS.items())):
             fn = getattr(h, name)
             fn.restype, fn.argtypes = res, args
         if h.gsr_abi_version() != 7:

@@ -11,6 +11,14 @@ which its own ray meets that plane, m_k(p) = invd_k + gx_k (p.x - x_k) + gy_k (p
     z = tsdf.depth_from_buffers(pd, buffers["final_Ts"])                 # (H, W) view depth for TSDF fusion
     grads = backward(..., dL_dplane_depth=g, plane_slopes=s, plane_depth_image=pd, gaussian_normals=n)
 
+Under the median rule (include/gsr_plane_median.h: the plane of the ONE Gaussian at which the transmittance falls through one half, the
+depth RaDe-GS and GOF fuse) the image and its gradient need no stage of backward():
+
+    med, contrib = render_plane_median_depth(s, buffers, H, W)           # (H, W) float32 1 / depth and (H, W) int32 list position
+    z = median_depth.view_depth(med, buffers["final_Ts"])                # (H, W) view depth for TSDF fusion
+    grads = backward_view(params, camera, bg, buffers, dL_dpixels)       # the step's other terms
+    plane_median_gradients(params, camera, buffers, g, contrib, s, n, grads=grads)     # ADDS into grads["dL_dmean3D"], grads["dL_drot"]
+
 A Gaussian falls back to its centre depth when its normal is zero, it lies at or behind the near plane, the ray to its centre grazes
 its plane, or it is not flat (smallest scale above half the middle one).  The image drops in wherever the forward's depth image
 does: loss.depth_loss_and_gradient, loss.normal_consistency_loss_and_gradients.  The forward gives the same bits every call.  Its
@@ -119,6 +127,74 @@ def render_view_plane_depth(params, camera, buffers):
     n = _normal_render.gaussian_normals(params["scales"], params["rotations"], params["positions"], camera)
     s = plane_slopes(n, params["scales"], params["positions"], camera)
     return render_plane_depth(s, buffers, camera["height"], camera["width"]), s, n
+
+
+# ---- the plane depth under the median rule (include/gsr_plane_median.h) ----
+def render_plane_median_depth(slopes, buffers, image_height, image_width, out=None, use_block_masks=True):
+    """(med, contrib): (H, W) float32, the inverse depth at which the pixel's ray meets the plane of the ONE Gaussian at which the
+    transmittance falls through one half (median_depth's rule, m_k(p) of render_plane_depth held to [invd_k / 4, 4 invd_k]), and
+    (H, W) int32, that Gaussian's 1-based position in the tile's list -- bit for bit median_depth.render_median_depth's second result;
+    0 and a value of 0 where no entry was applied.  At slopes 0 `med` is bit for bit that call's first result.
+    median_depth.view_depth(med, final_Ts) turns it into view depth for TSDF fusion.  `out`: a caller-owned pair to write into (every
+    element is written).  use_block_masks=False walks without the forward's block masks (the same bits either way)."""
+    fr = _frame.Frame.from_buffers(buffers, image_height, image_width, use_block_masks, inv_depth=True)
+    check_slopes(slopes, fr.N)
+    med, contrib = fr.outputs(out, [(fr.H, fr.W), (fr.H, fr.W)], (slopes,), pair="(plane_median_inv_depth, plane_median_contrib)",
+                              dtypes=(torch.float32, torch.int32))
+    if fr.N == 0:
+        return med.zero_(), contrib.zero_()
+    fr.launch("gsr_pmed_forward", _host.ptr(slopes), _host.ptr(med), _host.ptr(contrib), written=(med, contrib))
+    return med, contrib
+
+
+def plane_median_depth_backward(dL_dmedian, contrib, slopes, buffers, image_height, image_width, out=None, accumulate=False):
+    """dL_dplane_moments (N, 3) float32: per pixel whose chosen entry is not clamped, (g, g (p.x - x_k), g (p.y - y_k)) with
+    g = dL_dmedian[p], summed over the pixels that chose Gaussian k -- the moments plane_slopes_backward consumes, with weight 1 at the
+    chosen entry where backward()'s plane stage has w.  `contrib`: render_plane_median_depth's second result.  `out`: a caller-owned
+    (N, 3) tensor; it is cleared first unless accumulate=True, which ADDS into it (backward()'s `dL_dplane_moments`, say: everything
+    behind the moments is linear in them, so the two plane terms can share one buffer)."""
+    fr = _frame.Frame.from_buffers(buffers, image_height, image_width, False, inv_depth=True)
+    check_slopes(slopes, fr.N)
+    if not (_args.is_dev(dL_dmedian, torch.float32) and tuple(dL_dmedian.shape) == (fr.H, fr.W) and dL_dmedian.is_contiguous()
+            and dL_dmedian.data_ptr() % 16 == 0):
+        raise ValueError(f"dL_dmedian must be a contiguous, 16-byte aligned float32 device tensor of shape ({fr.H}, {fr.W})")
+    if not (_args.is_dev(contrib, torch.int32) and tuple(contrib.shape) == (fr.H, fr.W) and contrib.is_contiguous() and contrib.data_ptr() % 16 == 0):
+        raise ValueError(f"contrib must be a contiguous, 16-byte aligned int32 device tensor of shape ({fr.H}, {fr.W}) "
+                         "(render_plane_median_depth()'s second result)")
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs out, the (N, 3) tensor to add into")
+    out, = fr.outputs(out, [(fr.N, 3)], (slopes, dL_dmedian, contrib))
+    if not accumulate:
+        out.zero_()
+    if fr.N == 0:
+        return out
+    fr.launch("gsr_pmed_backward", _host.ptr(slopes), _host.ptr(dL_dmedian), _host.ptr(contrib), _host.ptr(out), written=(out,))
+    return out
+
+
+def plane_median_gradients(params, camera, buffers, dL_dmedian, contrib, slopes, normals, grads=None):
+    """(dL_dmean3D, dL_drot, moments): the gradient of sum_p dL_dmedian[p] med[p] (render_plane_median_depth) with respect to the
+    positions and rotations of `params`, in three calls -- plane_median_depth_backward, plane_slopes_backward,
+    normal_render.gaussian_normals_backward -- which ADD into grads["dL_dmean3D"] and grads["dL_drot"] of a backward_view result (so the
+    term joins a step's other gradients after backward_view), or into fresh zero tensors.  The median's choice, every Gaussian's branch
+    and the clamp are held constant; no stage of backward() is involved."""
+    H, W = camera["height"], camera["width"]
+    dmean = drot = None
+    if grads is not None:
+        if not (isinstance(grads, dict) and "dL_dmean3D" in grads and "dL_drot" in grads):
+            raise ValueError("grads must be a backward_view() result (a dict with dL_dmean3D and dL_drot) or None")
+        dmean, drot = grads["dL_dmean3D"], grads["dL_drot"]
+    moments = plane_median_depth_backward(dL_dmedian, contrib, slopes, buffers, H, W)
+    dmean, dn = plane_slopes_backward(moments, normals, params["scales"], params["positions"], camera, dL_dmean3D=dmean)
+    drot = _normal_render.gaussian_normals_backward(dn, params["scales"], params["rotations"], params["positions"], camera, dL_drot=drot)
+    return dmean, drot, moments
+
+
+def render_view_plane_median_depth(params, camera, buffers):
+    """(med, contrib, slopes, normals) of a frame forward.render_view() drew from `params` (positions, scales, rotations)."""
+    n = _normal_render.gaussian_normals(params["scales"], params["rotations"], params["positions"], camera)
+    s = plane_slopes(n, params["scales"], params["positions"], camera)
+    return render_plane_median_depth(s, buffers, camera["height"], camera["width"]) + (s, n)
 
 
 def check_gradient_triple(dL_dplane_depth, plane_slopes, plane_depth_image, gaussian_normals):

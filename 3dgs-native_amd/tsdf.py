@@ -219,15 +219,22 @@ def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, ha
     the transmittance falls through one half, where "expected" is the blended inverse depth over the coverage.
     plane_depth=True is another axis, the depth MODEL under the expected blend: every view fuses depth_from_buffers of
     plane_depth.render_plane_depth (include/gsr_plane_depth.h: a flat Gaussian contributes the depth at which the pixel's ray meets its
-    plane, not the depth of its centre).  It needs `params`, the dict `render` draws from (positions, scales, rotations), and raises
-    with depth_mode="median": the plane depth under the median rule is not built."""
+    plane, not the depth of its centre).  plane_depth="median" is that model under the median rule: every view fuses
+    median_depth.view_depth of plane_depth.render_plane_median_depth (include/gsr_plane_median.h: the plane of the one Gaussian at which
+    the transmittance falls through one half, what RaDe-GS and GOF fuse).  Both need `params`, the dict `render` draws from (positions,
+    scales, rotations).  depth_mode stays the CENTRE-depth axis: depth_mode="median" raises with any plane_depth -- the plane depth
+    under the median rule is plane_depth="median"."""
     if depth_mode not in DEPTH_MODES:
         raise ValueError(f"fuse_views: depth_mode must be one of {DEPTH_MODES} (got {depth_mode!r})")
+    if not (isinstance(plane_depth, bool) or (isinstance(plane_depth, str) and plane_depth == "median")):
+        raise ValueError(f"fuse_views: plane_depth must be False, True or 'median' (got {plane_depth!r})")
     if plane_depth and depth_mode != "expected":
-        raise ValueError("fuse_views: plane_depth=True blends the plane depth under the expected rule: it does not combine with "
-                         f"depth_mode={depth_mode!r}")
+        raise ValueError(f"fuse_views: plane_depth={plane_depth!r} does not combine with depth_mode={depth_mode!r}, the centre-depth axis: "
+                         "plane_depth=True blends the plane depth under the expected rule, and the plane depth under the median rule is "
+                         "plane_depth='median'")
     if plane_depth and not (isinstance(params, dict) and all(k in params for k in ("positions", "scales", "rotations"))):
-        raise ValueError("fuse_views: plane_depth=True needs params, the dict with positions, scales and rotations that render() draws from")
+        raise ValueError(f"fuse_views: plane_depth={plane_depth!r} needs params, the dict with positions, scales and rotations that render() "
+                         "draws from")
     cameras = list(cameras)
     if not cameras:
         raise ValueError("fuse_views: needs at least one camera")
@@ -248,8 +255,11 @@ def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, ha
         for c in batch:
             image, depth, buffers = render(c)
             H, W = c["height"], c["width"]
-            if plane_depth:
-                pd = _plane_depth.render_view_plane_depth(params, c, buffers)[0]
+            if plane_depth == "median":
+                med = _plane_depth.render_view_plane_median_depth(params, c, buffers)[0]
+                depths.append(_median_depth.view_depth(med, buffers["final_Ts"].reshape(H, W), alpha_min))
+            elif plane_depth:
+                pd =_plane_depth.render_view_plane_depth(params, c, buffers)[0]
                 depths.append(depth_from_buffers(pd, buffers["final_Ts"].reshape(H, W), alpha_min))
             elif depth_mode == "median":
                 med, _ = _median_depth.render_median_depth(buffers, H, W)
@@ -265,5 +275,5 @@ def fuse_views(render, cameras, voxel_size=None, resolution=256, centre=None, ha
     if depth_mode != "expected":
         info["depth_mode"] = depth_mode
     if plane_depth:
-        info["plane_depth"] = True
+        info["plane_depth"] = plane_depth
     return verts, faces, cols, info

@@ -15,8 +15,9 @@ within X aside as outliers (the DTU convention); --crop keeps the points inside 
 renders them from orbiting cameras, fuses the depth into a TSDF volume of --resolution voxels per side, extracts the mesh and
 evaluates it against the torus: the bias of render -> TSDF -> mesh, reported in voxels.  --depth-mode median fuses the median depth
 (median_depth.py: the Gaussian at which the transmittance falls through one half) instead of the expected inverse depth;
---depth-mode plane fuses the ray-plane intersection depth (plane_depth.py), and --demo-flat RATIO makes the demo's Gaussians discs on
-the torus, which that depth needs: an isotropic Gaussian has no plane and keeps its centre depth.
+--depth-mode plane fuses the ray-plane intersection depth (plane_depth.py), --depth-mode plane-median that depth under the median rule,
+and --demo-flat RATIO makes the demo's Gaussians discs on the torus, which both need: an isotropic Gaussian has no plane and keeps its
+centre depth.
 """
 import argparse
 import importlib
@@ -104,7 +105,7 @@ def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print, de
     P = gsr.point_cloud.gaussians_from_points(start.cpu().numpy(), opacity=0.9, device="cuda")
     if flat is not None:
         P = flat_discs(P, R, flat)
-    plane = depth_mode == "plane"
+    plane = {"plane": True, "plane-median": "median"}.get(depth_mode, False)       # tsdf.fuse_views' keyword of its own
     cams = orbit_cameras(gsr, views, 3.0, image_size, 0.6911112070083618)
     bg = np.zeros(3, np.float32)
     mverts, mfaces, _, info = gsr.tsdf.fuse_views(lambda c: gsr.render_view(P, c, bg), cams, resolution=resolution, centre=(0.0, 0.0, 0.0), half_side=half,
@@ -116,6 +117,8 @@ def demo_torus(gsr, resolution, views, points, image_size, seed=0, log=print, de
     m = evaluate_mesh(gsr, mverts, mfaces, verts, faces, samples=200_000, seed=seed + 1, thresholds=(h, 2 * h, 4 * h), log=log)
     m.update(demo="torus", depth_mode=depth_mode, resolution=info["resolution"], views=views, voxel_size=h, triangles=info["triangles"], vertices=info["vertices"],
              gaussians=int(start.shape[0]), image_size=image_size, flat=flat, accuracy_voxels=m["accuracy"] / h, completeness_voxels=m["completeness"] / h)
+    if plane:
+        m["plane_depth"] = info["plane_depth"]                  # fuse_views' own record of the keyword: True, or "median"
     log(f"demo torus ({depth_mode} depth): {m['gaussians']} Gaussians, {views} views of {image_size}^2 into {m['resolution']}^3 voxels of {h:.5f}: accuracy "
         f"{m['accuracy_voxels']:.3f} voxels, completeness {m['completeness_voxels']:.3f} voxels, {m['triangles']} triangles")
     return m
@@ -139,11 +142,12 @@ def main():
     ap.add_argument("--views", type=int, default=32, metavar="V", help="--demo: orbit views")
     ap.add_argument("--demo-points", type=int, default=100_000, metavar="N", help="--demo: Gaussians on the torus")
     ap.add_argument("--demo-image", type=int, default=256, metavar="PX", help="--demo: image side")
-    ap.add_argument("--depth-mode", choices=["expected", "median", "plane"], default="expected", help="--demo: the depth the volume is fused "
-                    "from (plane: the ray-plane intersection depth under the expected blend, plane_depth.py)")
+    ap.add_argument("--depth-mode", choices=["expected", "median", "plane", "plane-median"], default="expected", help="--demo: the depth the "
+                    "volume is fused from (plane: the ray-plane intersection depth under the expected blend, plane-median: under the median "
+                    "rule, plane_depth.py)")
     ap.add_argument("--demo-flat", type=float, default=None, metavar="RATIO", help="--demo: turn the Gaussians into discs on the torus: normal = "
                     "the torus's analytic normal, in-plane scales = the kNN scale, thickness = RATIO times it.  Without it the demo's "
-                    "isotropic Gaussians all fall back to their centre depth and --depth-mode plane measures nothing")
+                    "isotropic Gaussians all fall back to their centre depth and --depth-mode plane / plane-median measure nothing")
     args = ap.parse_args()
     if args.demo is None and (args.mesh is None or args.gt is None):
         ap.error("--mesh and --gt are required (or --demo torus)")

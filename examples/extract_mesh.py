@@ -11,7 +11,9 @@ truncation distance (default 4 voxels), --depth-max drops far depths, --min-weig
 observed with weight K.  Extraction is offline: it reads the triangle count back once, and welds on the host.
 --depth-mode median fuses the median depth (median_depth.py: the depth of the Gaussian at which the transmittance falls through one
 half, what the surface methods fuse bounded scenes from) instead of the expected inverse depth over the coverage; --depth-mode plane
-fuses the ray-plane intersection depth (plane_depth.py: a flat Gaussian contributes the depth at which the pixel's ray meets its plane).
+fuses the ray-plane intersection depth (plane_depth.py: a flat Gaussian contributes the depth at which the pixel's ray meets its plane);
+--depth-mode plane-median fuses that depth under the median rule (the plane of the one Gaussian at which the transmittance falls
+through one half: what RaDe-GS and GOF fuse).
 --gt G.ply evaluates the mesh right away against a ground truth in the same frame (accuracy, completeness, F-score: eval_mesh.py).
 """
 import argparse
@@ -45,8 +47,8 @@ def mesh_from_model(gsr, P, cams, out, bg=None, mode_kw=None, log=print, **fuse)
     def render(c):
         return gsr.render_view(P, c, bg, **(mode_kw or {}))
     t0 = time.perf_counter()
-    if fuse.get("depth_mode") == "plane":                      # the depth model, not a blending rule: tsdf.fuse_views' keyword of its own
-        fuse = dict(fuse, depth_mode="expected", plane_depth=True, params=P)
+    if fuse.get("depth_mode") in ("plane", "plane-median"):    # the depth model, not a blending rule: tsdf.fuse_views' keyword of its own
+        fuse = dict(fuse, depth_mode="expected", plane_depth=True if fuse["depth_mode"] == "plane" else "median", params=P)
     verts, faces, cols, info = gsr.tsdf.fuse_views(render, cams, **fuse)
     torch.cuda.synchronize()
     info["fuse_extract_weld_s"] = round(time.perf_counter() - t0, 3)
@@ -70,7 +72,8 @@ def main():
     ap.add_argument("--min-weight", type=float, default=1.0, metavar="K")
     ap.add_argument("--center", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     ap.add_argument("--half-side", type=float, default=None, metavar="E")
-    ap.add_argument("--depth-mode", choices=["expected", "median", "plane"], default="expected", help="the depth the volume is fused from")
+    ap.add_argument("--depth-mode", choices=["expected", "median", "plane", "plane-median"], default="expected",
+                    help="the depth the volume is fused from")
     ap.add_argument("--out", default="mesh.ply")
     ap.add_argument("--record", default=None, metavar="FILE", help="write the run's figures (resolution, triangles, seconds) as one JSON line")
     ap.add_argument("--gt", default=None, metavar="G.ply", help="evaluate the mesh against this ground truth in the same frame (examples/eval_mesh.py)")

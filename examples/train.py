@@ -58,6 +58,12 @@ with --lambda-normal-consistency, takes that term's depth normals from it too; t
 opacities through a stage of the backward.  The summary then has train_plane_depth_l1_mean.  --mesh-depth plane makes --mesh-out fuse
 the plane depth.
 
+Plane depth under the median rule (include/gsr_plane_median.h, plane_depth.py): --depth-render plane-median takes --lambda-depth's L1 on
+the inverse depth at which the pixel's ray meets the plane of the ONE Gaussian at which the transmittance falls through one half (what
+RaDe-GS and GOF fuse), masked like --depth-render median.  Its gradient reaches that Gaussian's position and rotation and needs no
+stage of the backward: plane_depth.plane_median_gradients adds it to the view's gradients after backward_view.  The summary then has
+train_plane_median_depth_l1_mean.  --mesh-depth plane-median makes --mesh-out fuse that depth.
+
 Pose refinement (include/gsr_camera_grads.h, pose.py): --optimize-poses keeps a pose correction xi = (rho, phi) per view and
 trains it with Adam (--pose-lr) on backward(camera_grad=True)'s camera gradients beside the Gaussians; each step reads that view's
 35 camera floats back to the host (one wait per view and iteration).  --pose-noise-deg / --pose-noise-trans (seed --pose-seed)
@@ -306,14 +312,16 @@ def perturb_depth_targets(depth_targets, noise, seed):
     return out
 
 
-def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None, median=False, plane=False):
+def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_targets=None, median=False, plane=False, plane_median=False):
     """Mean masked inverse-depth L1 (sum |D - t| [t > 0] / (W H), as depth_loss) and mean alpha L1 over the views; None without targets.
     Third: with depth targets, {"train_depth_corr_mean": the mean Pearson correlation rho of the rendered inverse depth with the
     targets as given, "train_depth_fit": each view's (s, b) of render ~ s target + b (include/gsr_depth_corr.h)}, and with
     clean_depth_targets (--depth-noise) "train_depth_l1_clean_mean", the first score against the unperturbed targets; with `median`
     (--depth-render median) "train_median_depth_l1_mean", the first score of the median inverse depth over the pixels that have one;
-    with `plane` (--depth-render plane) "train_plane_depth_l1_mean", the first score of the plane-depth image."""
-    dl, al, dc, dm, dp = [], [], [], [], []
+    with `plane` (--depth-render plane) "train_plane_depth_l1_mean", the first score of the plane-depth image; with `plane_median`
+    (--depth-render plane-median) "train_plane_median_depth_l1_mean", the first score of the plane depth under the median rule over the
+    pixels that have one."""
+    dl, al, dc, dm, dp, dpm = [], [], [], [], [], []
     fits = torch.zeros((len(cams), 4), device=P["positions"].device) if depth_targets is not None else None
     for k, c in enumerate(cams):
         _, dep, buf = gsr.render_view(P, c, bg, **mode_kw)
@@ -328,6 +336,10 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_t
             if plane:
                 pd = gsr.plane_depth.render_view_plane_depth(P, c, buf)[0]
                 dp.append(float(gsr.loss.depth_loss_and_gradients(pd.reshape(t.shape), t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
+            if plane_median:
+                med, contrib = gsr.plane_depth.render_view_plane_median_depth(P, c, buf)[:2]
+                mask = ((t > 0) & (contrib > 0).reshape(t.shape)).float()
+                dpm.append(float(gsr.loss.depth_loss_and_gradients(med.reshape(t.shape), t, mask, want_grad=False)[0].item()) / t.numel())
             if clean_depth_targets is not None:
                 t = clean_depth_targets[k]
                 dc.append(float(gsr.loss.depth_loss_and_gradients(dep, t, (t > 0).float(), want_grad=False)[0].item()) / t.numel())
@@ -344,6 +356,8 @@ def aux_scores(P, cams, depth_targets, alpha_targets, bg, mode_kw, clean_depth_t
             extra["train_median_depth_l1_mean"] = float(np.mean(dm))
         if dp:
             extra["train_plane_depth_l1_mean"] = float(np.mean(dp))
+        if dpm:
+            extra["train_plane_median_depth_l1_mean"] = float(np.mean(dpm))
     return (float(np.mean(dl)) if dl else None), (float(np.mean(al)) if al else None), extra
 
 
@@ -426,7 +440,7 @@ def finish(run, wall):
         summary["exposure_final"] = expo.state_dict()["E"]
         summary["exposure_steps"] = list(expo.steps)
     d_l1, a_l1, d_extra = aux_scores(P, cams, V.depth_targets, V.alpha_targets, bg, mode_kw, V.clean_depth_targets, median=args.depth_render == "median",
-                                      plane=args.depth_render == "plane")
+                                      plane=args.depth_render == "plane", plane_median=args.depth_render == "plane-median")
     if args.depth_render != "expected":
         summary["depth_render"] = args.depth_render
     if d_l1 is not None:
@@ -534,11 +548,13 @@ def parse_args(argv=None):
                     "own units.  pearson: 1 - the Pearson correlation of the rendered inverse depth with the target over the mask "
                     "(include/gsr_depth_corr.h), for relative targets: inverse depth known only up to an unknown scale a > 0 and shift b "
                     "per image (t -> a t + b), as monocular depth networks give it.  Needs --lambda-depth > 0; not divided by W H")
-    ap.add_argument("--depth-render", default="expected", choices=["expected", "median", "plane"], help="the rendered inverse depth --lambda-depth's "
+    ap.add_argument("--depth-render", default="expected", choices=["expected", "median", "plane", "plane-median"], help="the rendered inverse depth --lambda-depth's "
                     "L1 is taken on: the forward's expected inverse depth, or the median inverse depth (include/gsr_median_depth.h: the "
                     "Gaussian at which the transmittance falls through one half), masked to the pixels that have one; its gradient is a "
                     "stage of the backward; or the plane depth (include/gsr_plane_depth.h: every flat Gaussian contributes the depth at which the "
-                    "pixel's ray meets its plane), which --lambda-normal-consistency then takes its depth normals from too.  Needs --depth-loss l1")
+                    "pixel's ray meets its plane), which --lambda-normal-consistency then takes its depth normals from too; or the plane depth "
+                    "under the median rule (include/gsr_plane_median.h: the plane of the one Gaussian the median chooses), masked like median, "
+                    "its gradient added after the backward.  Needs --depth-loss l1")
     ap.add_argument("--depth-noise", type=float, default=0.0, metavar="S", help="make every depth target relative once, at load: "
                     "a_v t + b_v on its masked pixels, a_v = exp(U(-S, S)), b_v = U(0, S) * mean(t over the mask) per view; the summary "
                     "then also scores the depth against the clean targets (train_depth_l1_clean_mean)")
@@ -573,8 +589,9 @@ def parse_args(argv=None):
     ap.add_argument("--mesh-out", default=None, metavar="FILE", help="after the last iteration, fuse depth and colour renders of the training "
                     "views into a TSDF volume and write the extracted triangle mesh (include/gsr_tsdf.h; what examples/extract_mesh.py does). "
                     "Off by default; training itself is unchanged")
-    ap.add_argument("--mesh-depth", default="expected", choices=["expected", "median", "plane"], help="the depth --mesh-out fuses: the expected "
-                    "inverse depth over the coverage, or the median depth (include/gsr_median_depth.h)")
+    ap.add_argument("--mesh-depth", default="expected", choices=["expected", "median", "plane", "plane-median"], help="the depth --mesh-out fuses: "
+                    "the expected inverse depth over the coverage, the median depth (include/gsr_median_depth.h), the plane depth "
+                    "(include/gsr_plane_depth.h) or the plane depth under the median rule (include/gsr_plane_median.h)")
     ap.add_argument("--mesh-resolution", type=int, default=256, metavar="R", help="voxels per side of --mesh-out's volume")
     ap.add_argument("--mesh-min-weight", type=float, default=1.0, metavar="K", help="--mesh-out keeps cells whose corners all have weight K")
     ap.add_argument("--optimize-poses", action="store_true", help="refine each view's pose with Adam on the camera gradients "
@@ -686,6 +703,7 @@ def check_args(args):
         (args.depth_loss == "pearson" and not args.lambda_depth > 0.0, "--depth-loss pearson needs --lambda-depth > 0 (its weight)"),
         (args.depth_render == "median" and args.depth_loss != "l1", "--depth-render median needs --depth-loss l1"),
         (args.depth_render == "plane" and args.depth_loss != "l1", "--depth-render plane needs --depth-loss l1"),
+        (args.depth_render == "plane-median" and args.depth_loss != "l1", "--depth-render plane-median needs --depth-loss l1"),
         (not (args.depth_noise >= 0.0 and finite(args.depth_noise)), "--depth-noise must be >= 0 and finite"),
         (args.depth_noise > 0.0 and args.dataset and not args.depth_dir,
          "--depth-noise with --dataset needs --depth-dir (there is no depth target to perturb)"),
@@ -923,7 +941,7 @@ def train_view(run, it, v, alone, capacity=None):
         run.ssim_of[v] = ssim_sum / (mean_of / 3.0)                     # (a re-run of an overflowed view replaces its entry)
     else:
         loss_sum, dpix = gsr.loss.l1_loss_and_gradients(img, V.targets[v], loss_out=loss_out, weights=w_v)
-    kw = {}
+    kw, plane_median = {}, None
     if args.lambda_depth > 0.0 and args.depth_loss == "pearson":        # lambda_d (1 - rho): blind to the target's scale and shift
         kw["dL_ddepth_image"] = gsr.loss.depth_corr_loss_and_gradients(dep, V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
     elif args.lambda_depth > 0.0 and args.depth_render == "median":     # the same L1 on the median inverse depth, where a pixel has one
@@ -932,6 +950,11 @@ def train_view(run, it, v, alone, capacity=None):
         mask = V.depth_masks[v] * (contrib > 0).reshape(t.shape)         # the target's mask and "this pixel has a median"
         kw["dL_dmedian_depth"] = gsr.loss.depth_loss_and_gradients(med.reshape(t.shape), t, mask, args.lambda_depth)[1]
         kw["median_contributor"] = contrib
+    elif args.lambda_depth > 0.0 and args.depth_render == "plane-median":   # the same L1 on the plane depth under the median rule, masked as above
+        pm_med, pm_contrib, pm_s, pm_n = gsr.plane_depth.render_view_plane_median_depth(P, c, buf)
+        t = V.depth_targets[v]
+        mask = V.depth_masks[v] * (pm_contrib > 0).reshape(t.shape)
+        plane_median = (gsr.loss.depth_loss_and_gradients(pm_med.reshape(t.shape), t, mask, args.lambda_depth)[1], pm_contrib, pm_s, pm_n)
     elif args.lambda_depth > 0.0 and args.depth_render == "plane":      # the same L1 on the plane-depth image; its gradient is a stage of the backward
         plane_img, plane_s, plane_n = gsr.plane_depth.render_view_plane_depth(P, c, buf)
         g_plane = gsr.loss.depth_loss_and_gradients(plane_img.reshape(V.depth_targets[v].shape), V.depth_targets[v], V.depth_masks[v], args.lambda_depth)[1]
@@ -976,6 +999,9 @@ def train_view(run, it, v, alone, capacity=None):
         kw["geom_buffer"] = {"depths": buf["depths"]}
     g = gsr.backward_view(P, c, bg, buf, dpix, sh_gradient="factored" if run.factored else "dense", camera_grad=args.optimize_poses,
                           **kw, **run.abs_kw, **mode_kw)
+    if plane_median is not None:                                        # no stage of the backward: three calls ADD into g's means and rotations
+        g_pm, pm_contrib, pm_s, pm_n = plane_median
+        gsr.plane_depth.plane_median_gradients(P, c, buf, g_pm.reshape(c["height"], c["width"]).contiguous(), pm_contrib, pm_s, pm_n, grads=g)
     if run.screen_stats and capacity is None:                           # this view's statistics, on this view's stream
         run.model.stats.update(buf["radii"], g, use_abs=args.absgrad)
     if expo is not None:                                                # one single-wave launch; no read-back
