@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256) void distortion_kernel(FrameK f, const float *
 
     float T = 1.0f;
     walk.run<2>(
-        f, [&](int id, float4 &rb) { rb.w = invd[(size_t)id * invd_stride]; },
+        f, DepthFill{invd, invd_stride, nullptr},
         [&](const float4 &ra, const float4 &rb, float dx, float dy, float G, float t, bool applied) {
             if (BWD) {
                 if (__builtin_amdgcn_ballot_w64(applied) != 0ull) {
@@ -85,20 +85,11 @@ __global__ __launch_bounds__(256) void distortion_kernel(FrameK f, const float *
     }
 }
 
-// NULL, DIMS, ALIGN, in the header's order; GSR_OK when the call may be enqueued
-int check(const GsrDistortionFrame *fr, const void *a, const void *b, const void *c)
-{
-    if (frame_has_null(fr) || !fr->inv_depth || !a || !b || !c) return GSR_E_NULL;
-    if (!frame_dims_ok(fr) || fr->inv_depth_stride < 1) return GSR_E_DIMS;
-    if (!frame_aligned(fr) || !gsr_aligned4(fr->inv_depth) || !all_aligned16(a, b, c)) return GSR_E_ALIGN;
-    return GSR_OK;
-}
-
 } // namespace
 
 extern "C" int gsr_distortion_forward(const GsrDistortionFrame *frame, float *dist, float *moments, void *stream)
 {
-    const int rc = check(frame, dist, moments, moments);
+    const int rc = check_frame(frame, dist, moments);
     if (rc != GSR_OK) return rc;
     const FrameK k = frame_k(frame);
     // a frame with D = 0 walks nothing: every pixel is written as 0
@@ -110,7 +101,7 @@ extern "C" int gsr_distortion_forward(const GsrDistortionFrame *frame, float *di
 extern "C" int gsr_distortion_backward(const GsrDistortionFrame *frame, const float *dL_ddist, const float *moments, float *accumulators,
                                        void *stream)
 {
-    const int rc = check(frame, dL_ddist, moments, accumulators);
+    const int rc = check_frame(frame, dL_ddist, moments, accumulators);
     if (rc != GSR_OK) return rc;
     const FrameK k = frame_k(frame);
     if (k.D == 0) return GSR_OK; // nothing was blended: nothing to add

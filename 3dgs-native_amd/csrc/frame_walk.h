@@ -1,14 +1,14 @@
 // frame_walk.h -- the replay of the forward blend's weights over a finished frame's tile lists ("The frame-list walk"):
 // what features.hip, distortion.hip and normal_render.hip share.  Like fixed_sum.h, everything sits in the including file's
-// anonymous namespace.  Host part: the frame as a kernel argument and the three phases of its checks.  Device part: FrameWalk (the
-// block, the bounds, staging, compaction, the pipelined walk and the weight expression) and ValueTile (the backwards' transposed
-// flush into the accumulator records).
+// anonymous namespace.  Host part: the frame as a kernel argument, the three phases of its checks and the entry points' whole check.
+// Device part: FrameWalk (the block, the bounds, staging, compaction, the pipelined walk and the weight expression), ValueTile (the
+// backwards' transposed flush into the accumulator records) and what the depth stages stage and evaluate (DepthFill, plane_inv_depth).
 #pragma once
 #include <algorithm>
 #include <type_traits>
 
 #include "gsr_internal.h"
-#include "gsr_features.h"
+#include "gsr_plane_depth.h" // (and through it GsrDistortionFrame and GsrFeaturesFrame)
 
 namespace {
 
@@ -65,6 +65,20 @@ bool all_aligned16(const P *...p)
 {
     return (gsr_aligned16(p) && ...);
 }
+// An entry point's whole check over its frame and its own pointers: NULL, DIMS, ALIGN, in the headers' order; GSR_OK when the call
+// may be enqueued.  A GsrDistortionFrame's inv_depth joins each phase.
+template <class Frame, class... P>
+int check_frame(const Frame *fr, const P *...p)
+{
+    constexpr bool INVD = std::is_same<Frame, GsrDistortionFrame>::value;
+    if (frame_has_null(fr) || (!p || ...)) return GSR_E_NULL;
+    if constexpr (INVD) if (!fr->inv_depth) return GSR_E_NULL;
+    if (!frame_dims_ok(fr)) return GSR_E_DIMS;
+    if constexpr (INVD) if (fr->inv_depth_stride < 1) return GSR_E_DIMS;
+    if (!frame_aligned(fr) || !all_aligned16(p...)) return GSR_E_ALIGN;
+    if constexpr (INVD) if (!gsr_aligned4(fr->inv_depth)) return GSR_E_ALIGN;
+    return GSR_OK;
+}
 
 // ---- device ----
 constexpr int BATCH = 256;   // list entries staged per round
@@ -90,6 +104,29 @@ __device__ __forceinline__ float blend_forward_weight(const float4 &ra, const fl
     G = fast_exp(power);
     const float alpha = fminf(0.99f, rb.y * G);
     return power > 0.0f ? 0.0f : alpha;
+}
+
+// The depth stages' `fill` for run(): 1 / depth in the spare float of the second word and, with three words, the two slopes in the third.
+struct DepthFill {
+    const float *invd;
+    long long invd_stride;
+    const float *slopes; // [N][2]; unused with two words
+    __device__ __forceinline__ void operator()(int id, float4 &rb) const { rb.w = invd[(size_t)id * invd_stride]; }
+    __device__ __forceinline__ void operator()(int id, float4 &rb, float4 &rc) const
+    {
+        (*this)(id, rb);
+        const float2 sl = reinterpret_cast<const float2 *>(slopes)[id];
+        rc = make_float4(sl.x, sl.y, 0.f, 0.f);
+    }
+};
+
+// The plane's inverse depth at a pixel (include/gsr_plane_depth.h): mr = m0 - gx dx - gy dy in two fused multiply-adds, dx and dy as
+// blend_forward_weight forms them, and m = mr clamped to [m0 / 4, m0 * GSR_PLANE_DEPTH_MAX_RATIO].  Returns m; "not clamped" is
+// m == mr.  Every stage that promises another the same m or the same clamp decision, bit for bit, calls this.
+__device__ __forceinline__ float plane_inv_depth(float m0, float gx, float gy, float dx, float dy, float &mr)
+{
+    mr = __builtin_fmaf(-gx, dx, __builtin_fmaf(-gy, dy, m0));
+    return fminf(fmaxf(mr, m0 * 0.25f), m0 * GSR_PLANE_DEPTH_MAX_RATIO);
 }
 
 // run()'s default `open`: no pixel ever closes, the walk runs to the tile's largest n_contrib

@@ -216,15 +216,6 @@ __global__ __launch_bounds__(GSR_SUM_THREADS) void consistency_finish_kernel(con
     if (threadIdx.x < 2) sums[threadIdx.x] = (float)b.pairwise(threadIdx.x);
 }
 
-// NULL, DIMS, ALIGN, in the header's order; GSR_OK when the call may be enqueued
-int check_frame(const GsrFeaturesFrame *fr, const void *a, const void *b, const void *c, const void *d, const void *e)
-{
-    if (frame_has_null(fr) || !a || !b || !c || !d || !e) return GSR_E_NULL;
-    if (!frame_dims_ok(fr)) return GSR_E_DIMS;
-    if (!frame_aligned(fr) || !all_aligned16(a, b, c, d, e)) return GSR_E_ALIGN;
-    return GSR_OK;
-}
-
 int check_gaussians(int64_t N, const float *scales, const float *rots, const float *means, const float *view, const void *a, const void *b)
 {
     if (!scales || !rots || !means || !view || !a || !b) return GSR_E_NULL;
@@ -266,7 +257,7 @@ extern "C" int gsr_gaussian_normals_backward(int64_t N, const float *scales, con
 
 extern "C" int gsr_normal_render_forward(const GsrFeaturesFrame *frame, const float *normals, float *out, void *stream)
 {
-    const int rc = check_frame(frame, normals, out, out, out, out);
+    const int rc = check_frame(frame, normals, out);
     if (rc != GSR_OK) return rc;
     const FrameK k = frame_k(frame);
     // a frame with D = 0 walks nothing: every pixel is written as 0

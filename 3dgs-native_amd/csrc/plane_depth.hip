@@ -95,15 +95,10 @@ __global__ __launch_bounds__(256) void plane_depth_kernel(FrameK f, const float 
 
     float T = 1.0f;
     walk.run<3>(
-        f,
-        [&](int id, float4 &rb, float4 &rc) {
-            rb.w = invd[(size_t)id * invd_stride];
-            const float2 sl = *reinterpret_cast<const float2 *>(slopes + (size_t)id * 2);
-            rc = make_float4(sl.x, sl.y, 0.f, 0.f);
-        },
+        f, DepthFill{invd, invd_stride, slopes},
         [&](const float4 &ra, const float4 &rb, const float4 &rc, float dx, float dy, float G, float t, bool applied) {
-            const float mr = __builtin_fmaf(-rc.x, dx, __builtin_fmaf(-rc.y, dy, rb.w));
-            const float m = fminf(fmaxf(mr, rb.w * 0.25f), rb.w * GSR_PLANE_DEPTH_MAX_RATIO);
+            float mr;
+            const float m = plane_inv_depth(rb.w, rc.x, rc.y, dx, dy, mr);
             if (BWD) {
                 if (__builtin_amdgcn_ballot_w64(applied) != 0ull) {
                     float v[VALS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -137,15 +132,6 @@ __global__ __launch_bounds__(256) void plane_depth_kernel(FrameK f, const float 
     } else if (inside) {
         img[pix] = o;
     }
-}
-
-// NULL, DIMS, ALIGN, in the header's order; GSR_OK when the call may be enqueued
-int check_frame(const GsrDistortionFrame *fr, const void *a, const void *b, const void *c, const void *d, const void *e)
-{
-    if (frame_has_null(fr) || !fr->inv_depth || !a || !b || !c || !d || !e) return GSR_E_NULL;
-    if (!frame_dims_ok(fr) || fr->inv_depth_stride < 1) return GSR_E_DIMS;
-    if (!frame_aligned(fr) || !gsr_aligned4(fr->inv_depth) || !all_aligned16(a, b, c, d, e)) return GSR_E_ALIGN;
-    return GSR_OK;
 }
 
 int check_gaussians(int64_t N, const float *normals, const float *scales, const float *means, const float *view, float tan_fovx, float tan_fovy,
@@ -193,7 +179,7 @@ extern "C" int gsr_plane_slopes_backward(int64_t N, const float *normals, const 
 
 extern "C" int gsr_plane_depth_forward(const GsrDistortionFrame *frame, const float *slopes, float *out, void *stream)
 {
-    const int rc = check_frame(frame, slopes, out, out, out, out);
+    const int rc = check_frame(frame, slopes, out);
     if (rc != GSR_OK) return rc;
     const FrameK k = frame_k(frame);
     // a frame with D = 0 walks nothing: every pixel is written as 0

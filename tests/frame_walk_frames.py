@@ -1,5 +1,6 @@
 """Frames built on the host from a seed, for the stages that replay the forward blend's weights over a finished frame's tile lists
-(csrc/frame_walk.h: features.hip, distortion.hip, normal_render.hip), and the eight kernels behind the C ABI on such a frame.
+(csrc/frame_walk.h: features.hip, distortion.hip, normal_render.hip and, as DEPTH_STAGES, plane_depth.hip and the two depth models
+of median_depth.hip), and their kernels behind the C ABI on such a frame.
 The kernels clip everything they read, so any n_contrib within a tile's range, any mask bytes and any ids make a valid frame; the
 blend forward is not run.  Shared by tools/frame_walk_bits.py and tests/test_gpu_frame_walk.py."""
 import ctypes as C
@@ -13,6 +14,7 @@ _lib, _host = gsr._lib, gsr._host
 
 LENS = (0, 1, 255, 256, 257, 640)     # list lengths, cycled over the tiles: no batch, one (partial, full), two, three
 STAGES = ("features", "distortion", "normal_render")
+DEPTH_STAGES = ("plane_depth", "median_depth", "plane_median")   # for tools/frame_walk_bits.py; the contracts of tests/test_gpu_frame_walk.py run over STAGES
 # the backwards end in float atomics: their bits repeat only where no destination receives more than two addends -- one tile, every
 # Gaussian listed once, one or two waves with pixels (see build_frame's `blocks`)
 BACKWARD_SHAPES = {"8x8": dict(W=8, H=8), "16x8": dict(W=16, H=8), "16x16 two blocks": dict(W=16, H=16, empty_blocks=(1, 2))}
@@ -64,6 +66,10 @@ def build_frame(seed, W, H, lens=LENS, N=700, masks=None, bad_ids=True, once_per
               normals=(nrm / np.linalg.norm(nrm, axis=1, keepdims=True)).astype(np.float32), record_view=record_view,
               features=rng.normal(0, 1, (N, 64)).astype(np.float32), g_image=rng.normal(0, 1, (H, W, 64)).astype(np.float32),
               acc_seed=(rng.normal(0, 1, (N, 16)) * 1e-3).astype(np.float32), tile_len=tile_len, starts=starts)
+    # the plane stages' slopes, drawn last so that every array above keeps its values: of the size of 1/depth over a few pixels (some
+    # entries meet the clamp inside a tile), a fifth of the Gaussians at (0, 0) exactly
+    fr["slopes"] = (rng.normal(0, 0.15, (N, 2)) * invd[:, None]).astype(np.float32)
+    fr["slopes"][rng.random(N) < 0.2] = 0
     return fr
 
 
@@ -93,7 +99,7 @@ def past_every_pixel(fr):
 
 
 class DeviceFrame:
-    """A frame on the device and the eight kernels on it, through the C ABI."""
+    """A frame on the device and the kernels of STAGES and DEPTH_STAGES on it, through the C ABI."""
 
     def __init__(self, fr, dev=None):
         self.fr, self.dev = fr, dev or torch.device("cuda", 0)
@@ -109,7 +115,7 @@ class DeviceFrame:
             self.xy, self.co, self.invd = t(fr["xy"]), t(fr["co"]), t(fr["invd"])
             xy, co, invd, strides = self.xy.data_ptr(), self.co.data_ptr(), self.invd.data_ptr(), (2, 4, 1)
         self.point_list, self.ranges, self.n_contrib, self.masks = t(fr["point_list"]), t(fr["ranges"]), t(fr["n_contrib"]), t(fr["masks"])
-        self.normals = t(fr["normals"])
+        self.normals, self.slopes = t(fr["normals"]), t(fr["slopes"])
         common = (self.W, self.H, self.N, fr["D"], xy, strides[0], co, strides[1], _host.ptr(self.point_list), _host.ptr(self.ranges),
                   _host.ptr(self.n_contrib), _host.ptr(self.masks))
         self.frame = _lib.GsrFeaturesFrame(*common)
@@ -134,6 +140,17 @@ class DeviceFrame:
             dist, mom = self._new(self.H, self.W), self._new(self.H, self.W, 4)
             _lib.check(self.L.gsr_distortion_forward(C.byref(self.dframe), p(dist), p(mom), self.stream))
             return dist, mom
+        if stage == "plane_depth":
+            out = self._new(self.H, self.W)
+            _lib.check(self.L.gsr_plane_depth_forward(C.byref(self.dframe), p(self.slopes), p(out), self.stream))
+            return (out,)
+        if stage in ("median_depth", "plane_median"):
+            med, contrib = self._new(self.H, self.W), torch.full((self.H, self.W), -1, dtype=torch.int32, device=self.dev)
+            if stage == "median_depth":
+                _lib.check(self.L.gsr_median_depth_forward(C.byref(self.dframe), p(med), p(contrib), self.stream))
+            else:
+                _lib.check(self.L.gsr_pmed_forward(C.byref(self.dframe), p(self.slopes), p(med), p(contrib), self.stream))
+            return med, contrib
         out = self._new(self.H, self.W, 3)
         _lib.check(self.L.gsr_normal_render_forward(C.byref(self.frame), p(self.normals), p(out), self.stream))
         return (out,)
@@ -152,6 +169,18 @@ class DeviceFrame:
             g1 = g[:, :, 0].contiguous()
             _lib.check(self.L.gsr_distortion_backward(C.byref(self.dframe), p(g1), p(mom), p(acc), self.stream))
             return (acc,)
+        if stage in DEPTH_STAGES:   # the medians are fed their own forward's contributor image; the moments start from zeros
+            g1, mom = g[:, :, 0].contiguous(), torch.zeros((self.N, 3), device=self.dev)
+            if stage == "plane_depth":
+                (img,) = self.forward(stage)
+                _lib.check(self.L.gsr_plane_depth_backward(C.byref(self.dframe), p(self.slopes), p(g1), p(img), p(acc), p(mom), self.stream))
+                return mom, acc
+            _, contrib = self.forward(stage)
+            if stage == "median_depth":
+                _lib.check(self.L.gsr_median_depth_backward(C.byref(self.dframe), p(g1), p(contrib), p(acc), self.stream))
+                return (acc,)
+            _lib.check(self.L.gsr_pmed_backward(C.byref(self.dframe), p(self.slopes), p(g1), p(contrib), p(mom), self.stream))
+            return (mom,)
         (img,) = self.forward(stage)
         g3, dn = g[:, :, :3].contiguous(), self._new(self.N, 3)
         _lib.check(self.L.gsr_normal_render_backward(C.byref(self.frame), p(self.normals), p(g3), p(img), p(acc), p(dn), self.stream))

@@ -1,5 +1,5 @@
 """
-The plane depth under the median rule (csrc/plane_median.hip, include/gsr_plane_median.h) on the MI355X, against the float32
+The plane depth under the median rule (csrc/median_depth.hip, include/gsr_plane_median.h) on the MI355X, against the float32
 restatement and the float64 yardstick of tests/plane_median_reference.py.
 
   1. forward, on median_depth_reference.CASES, all nine (crossings at entry 1, over the first batch, at list positions 255-258, in the

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The bits of every stage that walks a finished frame's tile lists (csrc/frame_walk.h: features.hip, distortion.hip,
-normal_render.hip), for comparing two builds of the library: the eight kernels through the C ABI on frames built on the host from
-a seed (tests/frame_walk_frames.py), and one JSON line of name -> sha256 of each output buffer.
+normal_render.hip, plane_depth.hip and the two depth models of median_depth.hip), for comparing two builds of the library: their
+kernels through the C ABI only on frames built on the host from a seed (tests/frame_walk_frames.py: STAGES and DEPTH_STAGES), and one
+JSON line of name -> sha256 of each output buffer.
     GSR_LIB=ab/lib_parent.so python tools/frame_walk_bits.py > parent.json;  python tools/frame_walk_bits.py > new.json;  cmp parent.json new.json
 Forwards: masks NULL / all 0xFF / seeded random, 50 x 37 and 64 x 48 (partial tiles), lists of 0, 1, 255, 256, 257 and 640 entries,
 n_contrib anywhere within the list (multiples of 32, 4, 3 and not), ids < 0 and >= N, D = 0, features at C = 1, 3, 32, 33, 64, packed
@@ -32,7 +33,7 @@ def put(name, tensors):
 
 
 def stage_calls(tag, dev_frame, backward, seeded=False):
-    for stage in FW.STAGES:
+    for stage in FW.STAGES + FW.DEPTH_STAGES:
         for Cn in CHANNELS if stage == "features" else (3,):
             name = f"{stage}{' C=%d' % Cn if stage == 'features' else ''} {tag}"
             put(name + " forward", dev_frame.forward(stage, Cn))
