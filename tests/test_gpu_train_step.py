@@ -119,16 +119,18 @@ def config_of(key):
     return "/".join(parts[:2]) if parts[0] == "paths" else parts[0]
 
 
-def settle(worst):
+def settle(worst, path=None, note=None):
     """Print the worst ratios of a test and hold them to the record.  A configuration with no row at all on file has its rows
     appended (the file is created when absent); a configuration that is on file must have every key there, and none may exceed
-    10 x its recorded value.  Recorded values are never changed."""
+    10 x its recorded value.  Recorded values are never changed.  path, note: another test module's record and its "_note"."""
+    path = MARGINS if path is None else path
     print("\nworst ratios against the bounds: " + json.dumps({k: float(f"{v:.3g}") for k, v in sorted(worst.items())}))
-    doc = {"_note": "worst: the largest measured ratio of each assertion of tests/test_gpu_train_step.py against its bound (<= 1 passes), "
+    doc = {"_note": note or
+                    "worst: the largest measured ratio of each assertion of tests/test_gpu_train_step.py against its bound (<= 1 passes), "
                     "over the views and iterations of the configuration, measured on an MI355X against tests/step_reference.py.  It is "
                     "a record of what was measured, not the bound; a later run fails above 10 x a value", "worst": {}}
-    if os.path.exists(MARGINS):
-        with open(MARGINS) as f:
+    if os.path.exists(path):
+        with open(path) as f:
             doc = json.load(f)
     rec = doc["worst"]
     on_file = {config_of(k) for k in rec}
@@ -136,12 +138,12 @@ def settle(worst):
     for k, v in worst.items():
         if k in new:
             continue
-        assert k in rec, f"{k} has no recorded margin in {MARGINS}"
+        assert k in rec, f"{k} has no recorded margin in {path}"
         assert v <= 10.0 * max(rec[k], NOISE) or (rec[k] == 0.0 and v <= 1.0), f"{k}: ratio {v:.3g} against its bound, recorded {rec[k]:.3g}"
     if new:
         rec.update(new)
         doc["worst"] = {k: rec[k] for k in sorted(rec)}
-        with open(MARGINS, "w") as f:
+        with open(path, "w") as f:
             json.dump(doc, f, indent=1)
 
 
@@ -399,10 +401,12 @@ def check_view_gradients(call, v64, dense, worst):
     assert np.array_equal(call["out"]["_view_payload"][3 * n:3 * n + 3], np.asarray(call["cam"]["camera_center"], np.float32)[:3])
 
 
-def check_adam(run, after_adam, snap, G64, lrs, worst):
+def check_adam(run, after_adam, snap, G64, lrs, worst, sign_step_min=1e-6):
     """After iteration 0: the moments against adam_step of the float64 batch mean from zero moments, and the parameters' move
     (`after_adam`: the parameters as the Adam call left them; the step's density control then resets the opacities, as the
-    reference does at iteration 0)."""
+    reference does at iteration 0).  sign_step_min: the |G64| above which the float64 step itself is held to be lr against the sign
+    of g within 1 % of lr (a statement about the reference, not the kernel): the step is lr g / (|g| + eps + 1e-9), so the exact
+    threshold is 99 (eps + 1e-9) = 1.09e-6, a little above the `live` threshold of the kernel's check."""
     zeros = {k: np.zeros_like(snap["P"][k], np.float64) for k in A.GROUPS}
     G = {k: G64[k].reshape(snap["P"][k].shape) for k in A.GROUPS}
     P64, M64, V64 = A.adam_step(snap["P"], G, zeros, zeros, lrs, iteration=0)
@@ -427,7 +431,8 @@ def check_adam(run, after_adam, snap, G64, lrs, worst):
         keep(worst, "adam_step/" + k, move / 0.01)
         assert move <= 0.01, f"{k}: parameters off the float64 step by {move:.3g} lr"
         free = live & (np.abs(P64[k] - (snap["P"][k] - A._f(lrs[k]) * np.sign(G[k]))) <= 0.01 * A._f(lrs[k]))
-        assert k in ("scales", "rotations", "opacities") or free[live].mean() > 0.99, k        # a first Adam step: lr against the sign of g
+        signed = live & (g > sign_step_min)
+        assert k in ("scales", "rotations", "opacities") or free[signed].mean() > 0.99, k     # a first Adam step: lr against the sign of g
     reset = np.minimum(to_np(after_adam["opacities"]), np.float32(0.01))
     assert np.array_equal(to_np(run.model.params["opacities"]), reset), "iteration 0 ends with the reference's opacity reset"
 
@@ -537,8 +542,8 @@ def test_train_step_against_float64(name, monkeypatch):
 
 
 # ---------------------------------------------------------------------------------------------------------------- paths agree
-def first_step_grads(argv, monkeypatch):
-    T, run, rec = start(argv, monkeypatch)
+def first_step_grads(argv, monkeypatch, prepare=None):
+    T, run, rec = start(argv, monkeypatch, prepare)
     T.train_step(run, 0)
     torch.cuda.synchronize()
     return run, {k: to_np(run.model.grads[k]).astype(np.float64) for k in S.SMALL}
